@@ -6,9 +6,13 @@ For N > 1 the driver launches one rank per GPU with torch.distributed.run (RANK 
 environment); started by hand with --gpus N and no WORLD_SIZE, bench.py launches that command itself and relays its
 output.  The volume stiffness apply is element-independent, so ranks own disjoint Morton shards and the HEADLINE data
 path has NO collective (weak scaling: every rank owns one config-2 brick's worth of elements).  A step = one stiffness
-apply over the rank's whole shard, inputs resident in HBM.  On N > 1 ranks the line also carries, under "secondary",
+apply over the rank's whole shard, inputs resident in HBM.  With --full on N > 1 ranks the line also carries, under "secondary",
 the full operator and the Chebyshev iteration on config 2 SPLIT N ways (strong scaling) with the face-trace exchange
 over RCCL in C (csrc/d4est_hip_comm.hip) -- the replacement of d4est_ghost_data_exchange.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the result line.  --full adds the parity
+gate against the CPU oracle, the "secondary" numbers and the CPU baseline.  --dump-outputs DIR writes the last timed step's A u
+(float64 .npy; the inputs are seeded, so two builds can be compared output for output).
 
 Rank 0 prints ONE JSON line on stdout.  Everything else goes to stderr.
 """
@@ -80,6 +84,22 @@ def cpu_baseline(mesh, J, rst, u, budget_s=12.0):
                   "oracle/d4est_oracle.c (27-pass reference algorithm, naive row-major dgemm, gcc -O3 -march=native)"
                   % (sample.n_elements, mesh.n_elements, int(mesh.deg[0]), reps, cores),
     }
+
+
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_output(path, name, y, budget):
+    """--dump-outputs: the array the timed path hands its caller, as float64 DIR/<name>.npy.  Above the budget a fixed, seeded sample of
+    it instead, with its sorted indices in DIR/<name>_sample_index.npy (values and indices take half the budget each)."""
+    os.makedirs(path, exist_ok=True)
+    a = y.detach().cpu().numpy().astype(np.float64, copy=False).reshape(-1)
+    if a.nbytes > budget:
+        idx = np.sort(np.random.default_rng(20240607).choice(a.size, budget // 16, replace=False))
+        np.save(os.path.join(path, name + "_sample_index.npy"), idx.astype(np.float64))
+        a = a[idx]
+    np.save(os.path.join(path, name + ".npy"), a)
+    log("dumped %s (%d values) to %s" % (name, a.size, path))
 
 
 # bytes per DoF one iteration of the 5-iteration fused Chebyshev loop moves on top of full_operator_bytes_per_dof: + rhs 8 + p read 8 and
@@ -417,7 +437,15 @@ def main():
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--sharded-secondary", action="store_true",
                     help="N = 1 only: also run the N-rank secondary (RCCL transport, gather, rank-count invariance) on the single rank -- a rehearsal of its code path")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the parity gate against the CPU oracle, the secondary numbers (other operators, "
+                         "degrees, sizes and mesh classes, each gated), the CPU baseline and, on N > 1 ranks, the sharded secondaries "
+                         "(--no-check / --no-secondary / --no-cpu-baseline switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (A u of the headline apply) to DIR/<name>.npy as float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # `python bench.py --gpus N` by hand: become the launcher (before anything touches the GPU) and relay the ranks' output
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -488,8 +516,8 @@ def main():
     du = torch.from_numpy(u).to(dev)
     dAu = torch.empty_like(du)
 
-    # ---- parity gate on a sample before any timing is reported
-    if not args.no_check and rank == 0:
+    # ---- parity gate on a sample before any timing is reported (--full)
+    if args.full and not args.no_check and rank == 0:
         from tests import oracle_lib
         oracle = oracle_lib.load()
         plan.apply_stiffness_matrix(du, dAu)
@@ -529,6 +557,8 @@ def main():
         t = torch.tensor([elapsed, kernel_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kernel_ms = t[0].item(), t[1].item()
+    if args.dump_outputs:
+        dump_output(args.dump_outputs, "Au" if world == 1 else "Au_rank%d" % rank, dAu, DUMP_BUDGET_BYTES // world)
 
     dofs_per_rank = mesh.local_nodes
     total_dofs = dofs_per_rank * world
@@ -579,9 +609,9 @@ def main():
             "algorithmic_bytes_per_dof": bpd,
         },
     }
-    # ---- secondary, single-GPU only (reported, not the headline): the full operator A u (volume + SIPG faces,
+    # ---- secondary, single-GPU only (reported, not the headline; --full): the full operator A u (volume + SIPG faces,
     # d4est_laplacian_apply_aij) and one Chebyshev smoother iteration (apply + fused update), SURVEY.md section 8d
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         try:
             sides = mesh.build_sides(mp)
             plan.set_faces(sides, 10.0, 0)
@@ -1121,7 +1151,7 @@ def main():
     emitted, dog, emit_lock = [False], None, _threading.Lock()
     if world == 1 and args.sharded_secondary:
         out["sharded_rehearsal"] = sharded_secondary(args, rank, world, dev, stream, dist, torch)
-    if world > 1 and not args.no_secondary:
+    if args.full and world > 1 and not args.no_secondary:
         # strong-scaling secondaries with the RCCL exchange; a watchdog prints the headline alone if they do not finish
         import threading
 
@@ -1147,7 +1177,7 @@ def main():
         # of the secondary) and itself (stuck in the barrier) waiting for each other; the result line is written once either way
         if rank == 0:
             out["secondary"] = sec
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(mesh, J, rst, u)
     elif rank == 0:
         out["cpu_baseline"] = None

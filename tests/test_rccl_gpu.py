@@ -3,7 +3,7 @@ two ranks on one device): the library's own ncclCommInitRank, and the whole per-
 on the communicator's stream, event hand-over, unpack kernel -- with the rank as its own peer.  Wherever TWO OR MORE GPUs are visible
 test_two_ranks starts two fresh processes (one per GPU) and holds the sharded operator, Chebyshev loop and cg_eigs over real
 ncclSend / ncclRecv / ncclAllReduce to the one-rank results.  The multi-rank schedules are also covered over gloo (tests/test_parallel.py)
-and by bench.py --gpus N."""
+and by bench.py --gpus N --full."""
 import numpy as np
 import pytest
 
