@@ -27,6 +27,7 @@ SOURCES = [
     "d4est_hip_mgmatrix.hip",
     "d4est_hip_schwarz.hip",
     "d4est_hip_comm.hip",
+    "d4est_hip_estimator.hip",
 ]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]
@@ -108,7 +109,7 @@ def build_library(force=False, verbose=True, jobs=None, extra_flags=None):
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
     cmd = [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-Wall", "-shared", os.path.join(CSRC, COMPAT_SRC), "-o", COMPAT_LIB,
-           "-L" + HERE, "-ld4est_hip", "-Wl,-rpath,$ORIGIN"]
+           "-L" + HERE, "-ld4est_hip", "-ldl", "-Wl,-rpath,$ORIGIN"]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)

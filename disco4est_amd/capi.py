@@ -83,6 +83,11 @@ SIGNATURES = {
     "d4est_hip_schwarz_get_info": (None, [_vp, _vp, _vp]),
     "d4est_hip_plan_set_sipg": (None, [_vp, ctypes.c_double, ctypes.c_int]),
     "d4est_hip_plan_set_mortar_geometry": (None, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
+    "d4est_hip_plan_set_estimator": (None, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double]),
+    "d4est_hip_estimator_bi": (None, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "d4est_hip_plan_estimator_info": (ctypes.c_int, [_vp, _vp, _vp]),
+    "d4est_hip_plan_bndry_nodes": (ctypes.c_int, [_vp]),
+    "d4est_hip_plan_boundary_gather": (None, [_vp, _vp, _vp]),
     "d4est_hip_plan_set_dirichlet_values": (None, [_vp, _vp, ctypes.c_int]),
     "d4est_hip_plan_set_robin_values": (None, [_vp, _vp, _vp, ctypes.c_int]),
     "d4est_hip_plan_trace_size": (ctypes.c_longlong, [_vp]),
@@ -363,6 +368,36 @@ class Plan:
             self.lib.d4est_hip_plan_set_mortar_geometry(self.handle, *[a.ctypes.data_as(_vp) for a in arrs], 0)
         self.trace_size = self.lib.d4est_hip_plan_trace_size(self.handle)
         self.ghost_trace_size = self.lib.d4est_hip_plan_ghost_trace_size(self.handle)
+
+    def set_estimator(self, gradu_fcn, u_fcn, u_dirichlet_fcn, penalty_prefactor):
+        """request the a-posteriori error estimator (d4est_estimator_bi) with these penalty function ids (include/d4est_hip.h,
+        D4EST_HIP_EST_*); before set_faces (whose mortar factors also form the estimator's)"""
+        self.lib.d4est_hip_plan_set_estimator(self.handle, int(gradu_fcn), int(u_fcn), int(u_dirichlet_fcn), float(penalty_prefactor))
+
+    def estimator_bi(self, u, residual, diam, eta2, terms=None, ghost_trace=None, g=None):
+        """eta2[n_elements] (and terms[4 n_elements], term-major) of d4est_estimator_bi_compute.  u, residual: CUDA tensors of
+        local_nodes doubles; eta2 / terms / ghost_trace: CUDA tensors; diam (n_elements) and g (Dirichlet data on the boundary Lobatto
+        face nodes, set_dirichlet_values' layout; None = 0): numpy arrays or CUDA tensors"""
+        import torch
+        assert u.numel() == self.local_nodes and residual.numel() == self.local_nodes
+        assert eta2.numel() == self.n_elements and (terms is None or terms.numel() == 4 * self.n_elements)
+        dev = u.device
+
+        def on_dev(a):
+            if a is None or isinstance(a, torch.Tensor):
+                return a
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+
+        d_diam, d_g = on_dev(diam), on_dev(g)
+        assert d_diam.numel() == self.n_elements
+        if ghost_trace is not None:
+            assert ghost_trace.numel() == self.ghost_trace_size
+        self.lib.d4est_hip_estimator_bi(self.handle, _ptr(u), _ptr(ghost_trace) if ghost_trace is not None else None, _ptr(residual),
+                                        _ptr(d_diam), _ptr(d_g) if d_g is not None else None, _ptr(eta2),
+                                        _ptr(terms) if terms is not None else None)
+        if not isinstance(diam, torch.Tensor) or (g is not None and not isinstance(g, torch.Tensor)):
+            torch.cuda.current_stream(dev).synchronize() if self.torch_stream is None else self.torch_stream.synchronize()
+            self.lib.d4est_hip_device_synchronize()   # (the uploaded copies must outlive the launches)
 
     def set_dirichlet_values(self, g):
         if g is None:

@@ -559,6 +559,40 @@ void d4est_hip_plan_set_sipg(d4est_hip_plan_t* plan, double penalty_prefactor, i
   plan->sipg_penalty_fcn = penalty_fcn;
 }
 
+void d4est_hip_plan_set_estimator(d4est_hip_plan_t* plan, int gradu_fcn, int u_fcn, int u_dirichlet_fcn, double penalty_prefactor) {
+  check_plan(plan, "plan_set_estimator");
+  const int ids[3] = {gradu_fcn, u_fcn, u_dirichlet_fcn};
+  for (int i = 0; i < 3; ++i)
+    if (ids[i] < 0 || ids[i] > D4EST_HIP_EST_HOUSTON_U_DIRICHLET_MAXP_MINH) D4EST_HIP_ABORT("plan_set_estimator: unknown penalty function id %d", ids[i]);
+  if (plan->has_face_geometry) D4EST_HIP_ABORT("plan_set_estimator: call before plan_set_mortar_geometry (the estimator's factors are formed there)");
+  plan->est_requested = true;
+  for (int i = 0; i < 3; ++i) plan->est_fcn[i] = ids[i];
+  plan->est_prefactor = penalty_prefactor;
+}
+
+void d4est_hip_estimator_bi(d4est_hip_plan_t* plan, const double* u_dev, const double* ghost_trace_dev, const double* residual_dev,
+                            const double* diam_dev, const double* g_lobatto_dev, double* eta2_dev, double* terms_dev) {
+  check_plan(plan, "estimator_bi");
+  if (!plan->has_faces) D4EST_HIP_ABORT("estimator_bi: the plan has no faces (plan_set_faces)");
+  d4est_hip::estimator_compute(plan, u_dev, ghost_trace_dev, residual_dev, diam_dev, g_lobatto_dev, eta2_dev, terms_dev);
+}
+
+int d4est_hip_plan_estimator_info(const d4est_hip_plan_t* plan, int* ids, double* penalty_prefactor) {
+  check_plan(plan, "plan_estimator_info");
+  if (!plan->est_requested) return 0;
+  if (ids) for (int i = 0; i < 3; ++i) ids[i] = plan->est_fcn[i];
+  if (penalty_prefactor) *penalty_prefactor = plan->est_prefactor;
+  return 1;
+}
+
+int d4est_hip_plan_bndry_nodes(const d4est_hip_plan_t* plan) { check_plan(plan, "plan_bndry_nodes"); return plan->total_bndry_nodes; }
+
+void d4est_hip_plan_boundary_gather(d4est_hip_plan_t* plan, const double* vol_dev, double* bndry_dev) {
+  check_plan(plan, "plan_boundary_gather");
+  if (!plan->has_faces) D4EST_HIP_ABORT("plan_boundary_gather: the plan has no faces (plan_set_faces)");
+  d4est_hip::launch_boundary_gather(plan, vol_dev, bndry_dev);
+}
+
 void d4est_hip_plan_set_mortar_geometry(d4est_hip_plan_t* plan, const double* sj, const double* n, const double* drst_dxyz_m,
                                         const double* drst_dxyz_p_porder, const double* hm, const double* hp, int on_device) {
   check_plan(plan, "plan_set_mortar_geometry");

@@ -3,8 +3,11 @@
 //
 // Element-level shims: a cached one-element plan per (deg, deg_quad, quadrature type) with persistent pinned staging and device
 // buffers (allocated on first use, never per call); operator-level shims: the whole-mesh plan bound to the p4est pointer.
+#include <dlfcn.h>
+
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,6 +45,7 @@ struct FluxReg { double prefactor; int bc_type; };
 std::map<const void*, FluxReg> g_flux;
 struct CoordReg { const double* lob[3]; const double* quad[3]; };
 std::map<const void*, CoordReg> g_coord;
+std::map<const void*, const double*> g_diam;   // d4est_hip_compat_bind_element_diameters
 struct SchwarzReg { d4est_hip_schwarz_t* sz; int iter; double atol, rtol; };
 std::map<const void*, SchwarzReg> g_schwarz;
 double* g_tr_h = nullptr;   // pinned staging of the transfer shims
@@ -637,8 +641,115 @@ void cg_eigs(p4est_t* p4est, d4est_elliptic_data_t* vecs, d4est_elliptic_eqns_t*
 
 void d4est_hip_compat_bind_mesh(const void* p4est, d4est_hip_plan_t* plan) {
   if (plan) g_bound[p4est] = plan;
-  else { g_bound.erase(p4est); g_bound_lhs.erase(p4est); g_flux.erase(p4est); g_coord.erase(p4est); g_schwarz.erase(p4est); }
+  else { g_bound.erase(p4est); g_bound_lhs.erase(p4est); g_flux.erase(p4est); g_coord.erase(p4est); g_schwarz.erase(p4est); g_diam.erase(p4est); }
 }
+void d4est_hip_compat_bind_element_diameters(const void* p4est, const double* diam_volume) {
+  if (diam_volume) g_diam[p4est] = diam_volume;
+  else g_diam.erase(p4est);
+}
+
+// ---- d4est_estimator_bi_compute (src/Estimators/d4est_estimator_bi.c:343-560) on the bound plan
+// the ten closed forms of include/d4est_hip.h (D4EST_HIP_EST_*), as d4est_estimator_bi.h writes them
+static double est_closed_form(int id, int dm, double hm, int dp, double hp, double c) {
+  const double max_p = (double)std::max(dm, dp), min_h = std::min(hm, hp);
+  const double max_h_over_p = std::max(hm / (double)dm, hp / (double)dp);
+  const double max_p2_over_h = std::max((double)(dm * dm) / hm, (double)(dp * dp) / hp);
+  switch (id) {
+    case 0: return std::sqrt(min_h / max_p);
+    case 1: return std::sqrt(c * max_p * max_p / min_h);
+    case 2: return std::sqrt(max_h_over_p);
+    case 3: return std::sqrt(c * max_p2_over_h);
+    case 4: return std::sqrt(.5 * max_h_over_p);
+    case 5: return std::sqrt(.5 * c * max_p2_over_h);
+    case 6: return std::sqrt(c * max_p2_over_h);
+    case 7: return std::sqrt(.5 * min_h / max_p);
+    case 8: return std::sqrt(.5 * c * max_p * max_p / min_h);
+    default: return std::sqrt(c * max_p * max_p / min_h);
+  }
+}
+// the reference's penalty functions are static inline (their addresses identify nothing): evaluate at fixed probe arguments, with a probe
+// prefactor of our own, and take the closed form that agrees everywhere; none -> abort (nothing is substituted silently)
+static int identify_penalty(penalty_calc_t fcn, const char* role) {
+  if (!fcn) COMPAT_ABORT("d4est_estimator_bi_compute: %s penalty function is NULL", role);
+  static const int dm[4] = {3, 7, 2, 9}, dp[4] = {5, 4, 2, 6};
+  static const double hm[4] = {0.25, 0.031, 0.7, 0.12}, hp[4] = {0.4, 0.05, 0.7, 0.09}, c = 1.7;
+  for (int id = 0; id < 10; ++id) {
+    bool ok = true;
+    for (int k = 0; k < 4 && ok; ++k) {
+      const double want = est_closed_form(id, dm[k], hm[k], dp[k], hp[k], c), got = fcn(dm[k], hm[k], dp[k], hp[k], c);
+      ok = std::fabs(got - want) <= 1e-13 * std::fabs(want);
+    }
+    if (ok) return id;
+  }
+  COMPAT_ABORT("d4est_estimator_bi_compute: the %s penalty function matches none of the ten penalty functions of d4est_estimator_bi.h", role);
+}
+static bool same_penalty(int a, int b) {
+  auto canon = [](int i) { return i == 9 ? 1 : (i == 6 ? 3 : i); };   // the same formula under two names
+  return canon(a) == canon(b);
+}
+
+double* d4est_estimator_bi_compute(p4est_t* p4est, d4est_elliptic_data_t* d, d4est_elliptic_eqns_t* fcns, d4est_estimator_bi_penalty_data_t pd,
+                                   d4est_xyz_fcn_t u_bndry_fcn, void* bndry_ctx, d4est_ghost_t* ghost, d4est_ghost_data_t* ghost_data,
+                                   d4est_operators_t* ops, d4est_geometry_t* geom_res, d4est_mesh_data_t* factors_res, d4est_geometry_t*,
+                                   d4est_mesh_data_t*, d4est_quadrature_t* quad, int which_field, double* estimator_vtk,
+                                   double* estimator_vtk_per_face) {
+  const char* who = "d4est_estimator_bi_compute";
+  d4est_hip_plan_t* plan = bound(p4est, who);
+  if (estimator_vtk_per_face) COMPAT_ABORT("%s: estimator_vtk_per_face is not supported (pass NULL)", who);
+  if (!d || !fcns || !fcns->build_residual) COMPAT_ABORT("%s: NULL elliptic data or build_residual", who);
+  const int ln = d4est_hip_plan_local_nodes(plan), ne = d4est_hip_plan_n_elements(plan);
+  if (d->local_nodes != ln) COMPAT_ABORT("%s: elliptic data does not match the bound plan", who);
+  int plan_ids[3];
+  double plan_c = 0.0;
+  if (!d4est_hip_plan_estimator_info(plan, plan_ids, &plan_c)) COMPAT_ABORT("%s: the bound plan has no estimator (d4est_hip_plan_set_estimator)", who);
+  const int ids[3] = {identify_penalty(pd.gradu_penalty_fcn, "gradu"), identify_penalty(pd.u_penalty_fcn, "u"),
+                      identify_penalty(pd.u_dirichlet_penalty_fcn, "u_dirichlet")};
+  for (int i = 0; i < 3; ++i)
+    if (!same_penalty(ids[i], plan_ids[i])) COMPAT_ABORT("%s: penalty function %d is id %d, the bound plan has id %d", who, i, ids[i], plan_ids[i]);
+  if (pd.penalty_prefactor != plan_c) COMPAT_ABORT("%s: penalty_prefactor %g, the bound plan has %g", who, pd.penalty_prefactor, plan_c);
+  auto dg = g_diam.find(p4est);
+  if (dg == g_diam.end()) COMPAT_ABORT("%s: no element diameters registered (d4est_hip_compat_bind_element_diameters)", who);
+  auto cr = g_coord.find(p4est);
+  if (!u_bndry_fcn) COMPAT_ABORT("%s: u_bndry_fcn == NULL", who);
+  if (cr == g_coord.end() || !cr->second.lob[0]) COMPAT_ABORT("%s: no Lobatto node coordinates registered (d4est_hip_compat_bind_coordinates)", who);
+  // the residual, as the reference: d4est_elliptic_eqns_build_residual (src/EllipticSystem/d4est_elliptic_eqns.c:33-57)
+  fcns->build_residual(p4est, ghost, ghost_data, d, ops, geom_res, quad, factors_res, fcns->user);
+  const int nb = d4est_hip_plan_bndry_nodes(plan);
+  const size_t vb = sizeof(double) * (size_t)ln;
+  double* d_u = (double*)d4est_hip_malloc(vb);
+  double* d_r = (double*)d4est_hip_malloc(vb);
+  double* d_x = (double*)d4est_hip_malloc(vb);
+  double* d_g = (double*)d4est_hip_malloc(sizeof(double) * (size_t)std::max(nb, 1));
+  double* d_diam = (double*)d4est_hip_malloc(sizeof(double) * (size_t)std::max(ne, 1));
+  double* d_out = (double*)d4est_hip_malloc(sizeof(double) * 5 * (size_t)std::max(ne, 1));   // eta2 | 4 terms
+  // Dirichlet data: u_bndry_fcn at the boundary Lobatto face nodes, whose coordinates are gathered from the registered node coordinates
+  std::vector<double> bx[3], g((size_t)std::max(nb, 1));
+  for (int c = 0; c < 3; ++c) {
+    bx[c].resize((size_t)std::max(nb, 1));
+    d4est_hip_memcpy_h2d(d_x, cr->second.lob[c], vb);
+    d4est_hip_plan_boundary_gather(plan, d_x, d_g);
+    d4est_hip_plan_synchronize(plan);
+    d4est_hip_memcpy_d2h(bx[c].data(), d_g, sizeof(double) * (size_t)nb);
+  }
+  for (int i = 0; i < nb; ++i) g[i] = u_bndry_fcn(bx[0][i], bx[1][i], bx[2][i], bndry_ctx);
+  d4est_hip_memcpy_h2d(d_g, g.data(), sizeof(double) * (size_t)nb);
+  d4est_hip_memcpy_h2d(d_u, d->u + (size_t)which_field * ln, vb);
+  d4est_hip_memcpy_h2d(d_r, d->Au, vb);
+  d4est_hip_memcpy_h2d(d_diam, dg->second, sizeof(double) * (size_t)ne);
+  d4est_hip_estimator_bi(plan, d_u, nullptr, d_r, d_diam, nb > 0 ? d_g : nullptr, d_out, d_out + ne);
+  d4est_hip_plan_synchronize(plan);
+  // the returned array: the caller frees it with P4EST_FREE = sc_free(p4est_package_id, .) -- allocate it with libsc where the process has it
+  typedef void* (*sc_malloc_t)(int, size_t);
+  sc_malloc_t scm = (sc_malloc_t)dlsym(RTLD_DEFAULT, "sc_malloc");
+  const int* pkg = (const int*)dlsym(RTLD_DEFAULT, "p4est_package_id");
+  double* est = (double*)((scm && pkg) ? scm(*pkg, sizeof(double) * (size_t)std::max(ne, 1)) : std::malloc(sizeof(double) * (size_t)std::max(ne, 1)));
+  if (!est) COMPAT_ABORT("%s: out of host memory", who);
+  d4est_hip_memcpy_d2h(est, d_out, sizeof(double) * (size_t)ne);
+  if (estimator_vtk) d4est_hip_memcpy_d2h(estimator_vtk, d_out + ne, sizeof(double) * 4 * (size_t)ne);
+  d4est_hip_free(d_u); d4est_hip_free(d_r); d4est_hip_free(d_x); d4est_hip_free(d_g); d4est_hip_free(d_diam); d4est_hip_free(d_out);
+  return est;
+}
+
 void d4est_hip_compat_bind_operator(const void* p4est, d4est_apply_operator_fcn_t apply_lhs) {
   if (apply_lhs) g_bound_lhs[p4est] = apply_lhs;
   else g_bound_lhs.erase(p4est);

@@ -1991,6 +1991,9 @@ struct FaceHost {
   int* d_unit_first = nullptr;   // per listed element: its first unit (n_hang_elems + 1 entries)
   int n_units = 0;
   std::vector<HpMortar> rec_host;   // host copy of the records (set-up of the split)
+  std::vector<HpGeomSrc> gsrc_host;  // host copy of the records' factor sources (set-up of the estimator)
+  int* d_is_bndry = nullptr;         // 1 per boundary side (launch_boundary_gather; uploaded on first use)
+  std::vector<SideDesc> sd_host;     // host copy of the side descriptors as faces_setup built them, before the hp split (the same)
   double* d_hp_ops = nullptr;
   int hp_fld_stride = 0;
   size_t hp_lds_doubles = 0;
@@ -2294,6 +2297,7 @@ static void faces_setup_hp(d4est_hip_plan* plan, FaceHost& fh) {
   fh.d_rec = upload_vec(rec);
   fh.rec_host = rec;
   fh.d_gsrc = upload_vec(gsrc);
+  fh.gsrc_host = gsrc;
   fh.d_elem_first = upload_vec(elem_first);
   {
     std::vector<int> sf(side_first.begin(), side_first.end());
@@ -2528,6 +2532,7 @@ void faces_setup(d4est_hip_plan* plan) {
   fh.d_elem_desc_generic = upload_vec(edg);
   HIP_CHECK(hipMalloc(&plan->d_side_desc, std::max<size_t>(sd.size(), 1) * sizeof(SideDesc)));
   if (!sd.empty()) HIP_CHECK(hipMemcpy(plan->d_side_desc, sd.data(), sd.size() * sizeof(SideDesc), hipMemcpyHostToDevice));
+  fh.sd_host = sd;
   plan->d_face_ops = upload_vec(ops);
   fh.d_side_deg_m = upload_vec(fh.side_deg_m);
   fh.d_side_deg_p = upload_vec(fh.side_deg_p);
@@ -2846,6 +2851,8 @@ void faces_set_geometry(d4est_hip_plan* plan, const double* sj, const double* n,
   // raw sj is kept for Robin boundary data (faces_set_robin)
   if (!fh.d_sj) HIP_CHECK(hipMalloc(&fh.d_sj, std::max<size_t>(T, 1) * sizeof(double)));
   if (T > 0) HIP_CHECK(hipMemcpyAsync(fh.d_sj, dev[0], T * sizeof(double), hipMemcpyDeviceToDevice, plan->stream));
+  // the estimator's factors (d4est_hip_plan_set_estimator): only on plans that asked for them
+  if (plan->est_requested) estimator_setup(plan, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5]);
   HIP_CHECK(hipStreamSynchronize(plan->stream));
   for (int i = 0; i < 6; ++i)
     if (tmp[i]) HIP_CHECK(hipFree(tmp[i]));
@@ -3507,7 +3514,93 @@ bool faces_have_units(d4est_hip_plan* plan) {
   return fh.hp && fh.hp_split && (fh.n_hang_elems == 0 || fh.n_units > 0);
 }
 
+void faces_estimator_mortars(d4est_hip_plan* plan, std::vector<EstMortar>& out, std::vector<int>& elem_first, const double** face_ops,
+                             const double** hp_ops) {
+  FaceHost& fh = g_face_host[plan];
+  const int ne = plan->n_elements;
+  out.clear();
+  elem_first.assign(ne + 1, 0);
+  *face_ops = plan->d_face_ops;
+  *hp_ops = fh.d_hp_ops;
+  if (fh.hp) {
+    // the records as faces_setup_hp built them (before the hp split re-labelled the small sides it hands to the conforming kernels)
+    for (int e = 0; e < ne; ++e) {
+      elem_first[e] = (int)out.size();
+      for (int r = plan->side_first_rec[6 * (size_t)e]; r < plan->side_first_rec[6 * (size_t)e + 6]; ++r) {
+        const HpMortar& m = fh.rec_host[r];
+        const HpGeomSrc& g = fh.gsrc_host[r];
+        const size_t s = 6 * (size_t)e + m.face;
+        EstMortar x{};
+        x.elem = e; x.kind = m.kind; x.code = m.code; x.NQ = m.NQ; x.gidx = m.gidx;
+        x.S = g.S; x.off = g.off; x.off_p = g.off_p; x.Ttot = g.Ttot; x.deg_m = g.deg_m; x.deg_p = g.deg_p;
+        x.N = m.N; x.offC = m.offCa; x.ops_hp = 1; x.bstride = plan->side_bndry_stride[s]; x.u_shift = m.u_shift;
+        x.fm = m.fm; x.fp = m.fp; x.qoff = m.qoff; x.nbr_qoff = m.nbr_qoff;
+        out.push_back(x);
+      }
+    }
+  } else {
+    for (int e = 0; e < ne; ++e) {
+      elem_first[e] = (int)out.size();
+      for (int f = 0; f < 6; ++f) {
+        const size_t s = 6 * (size_t)e + f;
+        const SideDesc& d = fh.sd_host[s];
+        EstMortar x{};
+        x.elem = e; x.kind = d.kind; x.code = d.code; x.NQ = d.NQ; x.gidx = d.geom;
+        x.S = d.geom; x.off = 0; x.off_p = 0; x.Ttot = d.NQ * d.NQ; x.deg_m = fh.side_deg_m[s]; x.deg_p = fh.side_deg_p[s];
+        x.N = plan->deg[e] + 1; x.offC = d.offC; x.ops_hp = 0; x.bstride = plan->side_bndry_stride[s]; x.u_shift = 0;
+        x.fm = 1.0; x.fp = 1.0; x.qoff = d.qoff; x.nbr_qoff = d.nbr_qoff;
+        out.push_back(x);
+      }
+    }
+  }
+  elem_first[ne] = (int)out.size();
+}
+
+// a volume vector's values at the Lobatto face nodes of every boundary side, in the layout of the Dirichlet data (side_bndry_stride)
+__global__ __launch_bounds__(64) void bndry_gather_kernel(const double* __restrict__ vol, double* __restrict__ out, const int* __restrict__ is_bndry,
+                                                          const int* __restrict__ side_bndry_stride, const ElemDesc* __restrict__ ed, int n_sides) {
+  for (int s = blockIdx.x; s < n_sides; s += gridDim.x) {
+    if (!is_bndry[s]) continue;
+    const ElemDesc el = ed[s / 6];
+    const int N = el.N, f = s % 6;
+    for (int k = threadIdx.x; k < N * N; k += blockDim.x) out[side_bndry_stride[s] + k] = vol[el.ns + face_vol_index(f, N, k % N, k / N)];
+  }
+}
+
+void launch_boundary_gather(d4est_hip_plan* plan, const double* vol, double* out) {
+  FaceHost& fh = g_face_host[plan];
+  const int n_sides = 6 * plan->n_elements;
+  if (n_sides == 0 || plan->total_bndry_nodes == 0) return;
+  if (!fh.d_is_bndry) {
+    std::vector<int> b(n_sides);
+    for (int s_ = 0; s_ < n_sides; ++s_) b[s_] = fh.sd_host[s_].kind == 0;   // (boundary sides; hanging sides are kind 3)
+    fh.d_is_bndry = upload_vec(b);
+  }
+  hipLaunchKernelGGL(bndry_gather_kernel, dim3(std::min(n_sides, 8192)), dim3(64), 0, plan->stream, vol, out, fh.d_is_bndry,
+                     fh.d_side_bndry_stride, (const ElemDesc*)fh.d_elem_desc_generic, n_sides);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_traces_all(d4est_hip_plan* plan, const double* u, double* trace) {
+  FaceHost& fh = g_face_host[plan];
+  const int n = plan->n_elements;
+  if (n == 0) return;
+  if (fh.hp) {
+    const size_t lds = fh.hp_lds_doubles * sizeof(double);
+    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trace_hp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(trace_hp_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, u, trace, fh.d_rec, fh.d_elem_first,
+                       (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, n, fh.hp_fld_stride);
+  } else {
+    const size_t lds = generic_lds_bytes(plan);
+    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trace_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(trace_generic_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, u, trace,
+                       (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, n, fh.fld_stride);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
 void faces_destroy(d4est_hip_plan* plan) {
+  estimator_destroy(plan);
   direct_destroy(plan);
   hybrid_destroy(plan);
   auto it = g_face_host.find(plan);
@@ -3518,7 +3611,7 @@ void faces_destroy(d4est_hip_plan* plan) {
     (void)hipFree(fh.d_sj); (void)hipFree(fh.d_robin_c); (void)hipFree(fh.d_robin_r);
     (void)hipFree(fh.d_fam_small); (void)hipFree(fh.d_fam_big);
     (void)hipFree(fh.d_rec); (void)hipFree(fh.d_gsrc); (void)hipFree(fh.d_elem_first); (void)hipFree(fh.d_side_first); (void)hipFree(fh.d_hp_ops); (void)hipFree(fh.d_hang_elems);
-    (void)hipFree(fh.d_units); (void)hipFree(fh.d_unit_first);
+    (void)hipFree(fh.d_units); (void)hipFree(fh.d_unit_first); (void)hipFree(fh.d_is_bndry);
     (void)hipFree(fh.d_ring_small); (void)hipFree(fh.d_ring_big); (void)hipFree(fh.d_dirty_small); (void)hipFree(fh.d_dirty_big);
     g_face_host.erase(it);
   }

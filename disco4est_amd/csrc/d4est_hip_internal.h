@@ -148,6 +148,13 @@ struct d4est_hip_plan {
   double* d_scratch = nullptr;
   size_t scratch_doubles = 0;
 
+  // a-posteriori error estimator (d4est_hip_estimator.hip): requested by d4est_hip_plan_set_estimator before the mortar factors, whose
+  // set-up then also forms the estimator's per-node factors (EstHost); plans without the request allocate nothing for it
+  bool est_requested = false;
+  int est_fcn[3] = {-1, -1, -1};   // gradu, u, u_dirichlet penalty ids (D4EST_HIP_EST_*)
+  double est_prefactor = 0.0;
+  void* est = nullptr;             // d4est_hip::EstHost
+
   // host-pointer entry points (d4est_hip_*_host): persistent pinned staging (3 vectors) and device mirrors u, rhs, Au, r,
   // allocated once on first use -- no per-call hipMalloc behind d4est's host double* API
   double* h_stage = nullptr;
@@ -255,6 +262,35 @@ bool faces_hp_split(d4est_hip_plan* plan);   // the plan has record kernels besi
 void launch_hybrid_dirty_stiffness(d4est_hip_plan* plan, const double* u, double* Au);
 void launch_flux_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, int phase, const DirectFuse* cf = nullptr);   // (faces.hip: supplies the Robin arrays; phase 0 fork + launches, 1 join)
 void faces_destroy(d4est_hip_plan* plan);
+// the estimator's view of the plan's mortars (d4est_hip_faces.hip builds it from its side descriptors / mortar records): one entry per
+// conforming or boundary side, per sub-mortar of a big hanging side, per small hanging side; the entries of an element consecutive
+struct EstMortar {
+  int elem;
+  int kind;          // 0 boundary, 1 interface with a local (+) element, 2 with a ghost (+) element
+  int code;          // reorder code applied when reading the (+) block
+  int NQ;            // mortar quadrature nodes per direction
+  int gidx;          // scalar index of the mortar's first node (S + off): the estimator factors sit at 8 gidx
+  int S, off, off_p, Ttot;   // where the reference-layout mortar factors of this mortar sit (set-up only)
+  int deg_m, deg_p;  // prefactor degrees (d4est_estimator_bi.c:212-228)
+  int N;             // boundary: nodes per direction of the element's face (Dirichlet data)
+  int offC, ops_hp;  // boundary: (NQ x N) Lobatto face nodes -> mortar quadrature nodes, in face_ops (ops_hp = 0) or hp_ops (1)
+  int bstride;       // boundary: side_bndry_stride of the side
+  int u_shift;       // see HpMortar::u_shift
+  double fm, fp;     // hanging-face factors on the (-) / (+) gradient (d4est_laplacian_flux.c:905-915)
+  long long qoff, nbr_qoff;
+};
+void faces_estimator_mortars(d4est_hip_plan* plan, std::vector<EstMortar>& out, std::vector<int>& elem_first, const double** face_ops,
+                             const double** hp_ops);
+// every local side's (every mortar record's) trace block, whatever kernels the operator path uses
+void launch_traces_all(d4est_hip_plan* plan, const double* u, double* trace);
+// out[side_bndry_stride[s] + a + N b] = vol at face node (a, b) of every boundary side s (d4est_hip_plan_boundary_gather)
+void launch_boundary_gather(d4est_hip_plan* plan, const double* vol, double* out);
+// d4est_hip_estimator.hip
+void estimator_setup(d4est_hip_plan* plan, const double* sj, const double* n, const double* drst_m, const double* drst_p, const double* hm,
+                     const double* hp);
+void estimator_destroy(d4est_hip_plan* plan);
+void estimator_compute(d4est_hip_plan* plan, const double* u, const double* ghost_trace, const double* residual, const double* diam,
+                       const double* g_lobatto, double* eta2, double* terms);
 
 // d4est_hip_solver.hip
 // traces, volume term, (exchange), flux; lhs_term: also the optional zeroth-order term of plan_set_lhs_coefficient

@@ -254,6 +254,54 @@ void d4est_hip_plan_set_sipg(d4est_hip_plan_t* plan, double penalty_prefactor, i
  * sj[S+k], n[3S + d*T + k], drst_dxyz_m / drst_dxyz_p_porder[9S + (i+3j)*T + k] = d r_i/d x_j, hm[S+k], hp[S+k]. */
 void d4est_hip_plan_set_mortar_geometry(d4est_hip_plan_t* plan, const double* sj, const double* n, const double* drst_dxyz_m,
                                         const double* drst_dxyz_p_porder, const double* hm, const double* hp, int on_device);
+/* ---- a-posteriori error estimator (csrc/d4est_hip_estimator.hip) -----------------------------------------------------------------
+ * d4est_estimator_bi_compute (src/Estimators/d4est_estimator_bi.c:343-560), which the hp-adaptive drivers call once per AMR level after
+ * the solve (e.g. src/Problems/ConstantDensityStar/constant_density_star_mgpc_newton_petsc.c:306-324).  Per local element e,
+ * eta2[e] = term0 + term1 + term2 + term3, summed in that order:
+ *   term0  (h_e^2 / p_e^2) r_e^T M_e r_e, M_e = V^T W J V at deg_quad (:395-441; d4est_mesh_compute_l2_norm_sqr, src/Mesh/d4est_mesh.c:2299-2370)
+ *   term1  sum over the interior mortars of e of sum_k w_k sj_k (pi_grad n.(grad u_m - grad u_p))^2   (d4est_estimator_bi_interface, :150-340)
+ *   term2  sum over the interior mortars of e of sum_d sum_k w_k sj_k (pi_u n_d (u_m - u_p))^2
+ *   term3  sum over the boundary sides of e of sum_d sum_k w_k sj_k (pi_D n_d (u_m - g))^2              (d4est_estimator_bi_dirichlet, :15-148)
+ * Every local side adds to its own element only; a big hanging side adds its four sub-mortars, a small side its own; the prefactor
+ * degrees are those of the mortar's two elements (:212-228); pi_D is evaluated as pi_D(p, h_m, p, h_m).  The boundary term is always
+ * the Dirichlet one, with g given here, whatever Dirichlet / Robin data the plan's operator holds (the reference forces BC_DIRICHLET,
+ * :491-496).  The penalty functions of d4est_estimator_bi.h, by id (any id in any role; c = penalty_prefactor): */
+#define D4EST_HIP_EST_BI_GRADU_MAXP_MINH 0              /* sqrt(min_h / max_p)                      bi_gradu_prefactor_maxp_minh */
+#define D4EST_HIP_EST_BI_U_MAXP_MINH 1                  /* sqrt(c max_p^2 / min_h)                  bi_u_prefactor_conforming_maxp_minh */
+#define D4EST_HIP_EST_BI_GRADU_MAX_H_OVER_P 2           /* sqrt(max(h_m/p_m, h_p/p_p))              bi_gradu_prefactor_max_h_over_p */
+#define D4EST_HIP_EST_BI_U_MAX_P2_OVER_H 3              /* sqrt(c max(p_m^2/h_m, p_p^2/h_p))        bi_u_prefactor_conforming_max_p2_over_h */
+#define D4EST_HIP_EST_HOUSTON_GRADU_MAX_H_OVER_P 4      /* sqrt(.5 max(h_m/p_m, h_p/p_p))           houston_gradu_prefactor_max_h_over_p */
+#define D4EST_HIP_EST_HOUSTON_U_MAX_P2_OVER_H 5         /* sqrt(.5 c max(p_m^2/h_m, p_p^2/h_p))     houston_u_prefactor_max_p2_over_h */
+#define D4EST_HIP_EST_HOUSTON_U_DIRICHLET_MAX_P2_OVER_H 6 /* sqrt(c max(p_m^2/h_m, p_p^2/h_p))      houston_u_dirichlet_prefactor_max_p2_over_h */
+#define D4EST_HIP_EST_HOUSTON_GRADU_MAXP_MINH 7         /* sqrt(.5 min_h / max_p)                   houston_gradu_prefactor_maxp_minh */
+#define D4EST_HIP_EST_HOUSTON_U_MAXP_MINH 8             /* sqrt(.5 c max_p^2 / min_h)               houston_u_prefactor_maxp_minh */
+#define D4EST_HIP_EST_HOUSTON_U_DIRICHLET_MAXP_MINH 9   /* sqrt(c max_p^2 / min_h)                  houston_u_dirichlet_prefactor_maxp_minh */
+/* Config 4 uses (7, 8, 9) with c = sipg_penalty_prefactor (constant_density_star_mgpc_newton_petsc.c:195-199).  Call BEFORE
+ * d4est_hip_plan_set_mortar_geometry or its brick / analytic forms (the estimator's per-node factors are formed there from the mortar
+ * factors, as the SIPG penalty is: the same rule as d4est_hip_plan_set_sipg).  Plans without this call allocate nothing for the
+ * estimator and run as before.  Aborts ([D4EST_HIP_ABORT]) on a NULL plan or an id outside 0..9. */
+void d4est_hip_plan_set_estimator(d4est_hip_plan_t* plan, int gradu_fcn, int u_fcn, int u_dirichlet_fcn, double penalty_prefactor);
+/* eta2_dev[n_elements] (and terms_dev[4 n_elements], term-major: term t of element e at t n_elements + e, the reference's estimator_vtk
+ * layout; NULL = not wanted) from device vectors u_dev and residual_dev (local_nodes: the residual d4est_elliptic_eqns_build_residual
+ * leaves in Au) and diam_dev[n_elements] (d4est_mesh_data_t::diam_volume).  ghost_trace_dev: the ghost trace buffer of plans with ghost
+ * sides (d4est_hip_plan_ghost_trace_size doubles, filled by the caller's exchange of u's traces), or NULL -- then the traces are
+ * exchanged through the plan_set_comm hooks, as apply_lhs does (on plans with hanging faces the *_sub blocks included).
+ * g_lobatto_dev: Dirichlet data on the boundary sides' Lobatto face nodes in the layout of d4est_hip_plan_set_dirichlet_values, NULL =
+ * g = 0.  Needs plan_set_geometry (or a form of it), plan_set_faces, the mortar factors and d4est_hip_plan_set_estimator before them;
+ * aborts otherwise.  Everything runs on the plan's stream, without host synchronisation; no atomics: bit-identical from call to call,
+ * the same on every face path of the operator (the estimator forms every side's trace itself).  Limit: the residual term holds one
+ * element's interpolated residual in LDS, (max(N^3, NQ^2 N) + NQ N^2) doubles, N = deg + 1, NQ = deg_quad + 1 -- up to deg_quad = deg + 2
+ * at p = 19 (160 KB); a plan beyond it aborts here. */
+void d4est_hip_estimator_bi(d4est_hip_plan_t* plan, const double* u_dev, const double* ghost_trace_dev, const double* residual_dev,
+                            const double* diam_dev, const double* g_lobatto_dev, double* eta2_dev, double* terms_dev);
+/* 1 and the three ids and the prefactor of d4est_hip_plan_set_estimator (either output may be NULL) when the plan has the estimator,
+ * else 0 -- for hosts that check a caller's penalty functions against the plan (the compat library's d4est_estimator_bi_compute) */
+int d4est_hip_plan_estimator_info(const d4est_hip_plan_t* plan, int* ids, double* penalty_prefactor);
+/* total_bndry_nodes of plan_set_faces, and a device volume vector's values at the Lobatto face nodes of every boundary side in the layout
+ * of d4est_hip_plan_set_dirichlet_values (side_bndry_stride; d4est_operators_apply_slicer order): where a host evaluates Dirichlet data
+ * from the node coordinates (the three coordinate vectors gathered one by one) */
+int d4est_hip_plan_bndry_nodes(const d4est_hip_plan_t* plan);
+void d4est_hip_plan_boundary_gather(d4est_hip_plan_t* plan, const double* vol_dev, double* bndry_dev);
 /* Dirichlet values on the Lobatto face nodes of every boundary side (EVAL_BNDRY_FCN_ON_LOBATTO,
  * d4est_laplacian_flux_sipg.c:80-112); NULL resets to zero (the homogeneous operator used by apply_lhs). */
 void d4est_hip_plan_set_dirichlet_values(d4est_hip_plan_t* plan, const double* g_lobatto, int on_device);

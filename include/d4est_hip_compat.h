@@ -135,6 +135,23 @@ typedef struct {
   void* user;
 } d4est_elliptic_eqns_t;
 
+/* src/dGMath/d4est_laplacian_flux_sipg.h:8-16 and src/Estimators/d4est_estimator_bi.h:8-23, member for member (passed BY VALUE to
+ * d4est_estimator_bi_compute, so the layout must be the reference's) */
+typedef double (*penalty_calc_t)(int, double, int, double, double);
+typedef struct d4est_mesh_size_parameters_opaque d4est_mesh_size_parameters_t;
+typedef struct {
+  double* estimator;
+  int output_vtk;
+  double* estimator_vtk;            /* residual term, je1 term, je2 term, je2 boundary term */
+  double* estimator_vtk_per_face;
+  penalty_calc_t u_penalty_fcn;
+  penalty_calc_t u_dirichlet_penalty_fcn;
+  penalty_calc_t gradu_penalty_fcn;
+  d4est_mesh_size_parameters_t* size_params;
+  double penalty_prefactor;
+  void* user;
+} d4est_estimator_bi_penalty_data_t;
+
 /* ---- element level: src/Quadrature/d4est_quadrature.h:132-141 ------------------------------------------------------------ */
 void d4est_quadrature_apply_stiffness_matrix(d4est_operators_t *d4est_ops,d4est_quadrature_t *d4est_quadrature,d4est_geometry_t *d4est_geometry,void *object,d4est_quadrature_object_type_t object_type,d4est_quadrature_integrand_type_t integrand_type,double *in,int deg_lobatto,double *jac_quad,double *rst_xyz[3][3],int deg_quad,double *out);
 void d4est_quadrature_apply_mass_matrix(d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geometry,d4est_quadrature_t *d4est_quadrature,void *object,d4est_quadrature_object_type_t object_type,d4est_quadrature_integrand_type_t integrand_type,double *in,int deg_lobatto,double *jac_quad,int deg_quad,double *out);
@@ -208,6 +225,19 @@ void d4est_laplacian_with_opt_apply_stiffness_matrix(p4est_t *p4est,d4est_operat
 void d4est_laplacian_with_opt_apply_aij(p4est_t *p4est,d4est_ghost_t *d4est_ghost,d4est_ghost_data_t *d4est_ghost_data,d4est_elliptic_data_t *d4est_elliptic_data,d4est_laplacian_with_opt_flux_data_t *flux_fcn_data,d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geom,d4est_quadrature_t *d4est_quad,d4est_mesh_data_t *d4est_factors,int which_field);
 void d4est_solver_multigrid_smoother_cheby_iterate_aux(p4est_t *p4est,d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geom,d4est_quadrature_t *d4est_quad,d4est_mesh_data_t *d4est_factors,d4est_ghost_t *d4est_ghost,d4est_ghost_data_t *d4est_ghost_data,d4est_elliptic_data_t *vecs,d4est_elliptic_eqns_t *fcns,double *r,int iter,double lmin,double lmax,int print_residual_norm,int mg_level,int compute_residual_at_end);
 void cg_eigs(p4est_t *p4est,d4est_elliptic_data_t *vecs,d4est_elliptic_eqns_t *fcns,d4est_ghost_t *ghost,d4est_ghost_data_t *ghost_data,d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geom,d4est_quadrature_t *d4est_quad,d4est_mesh_data_t *d4est_factors,int imax,int print_spectral_bound_iterations,int use_new,double *spectral_bound);
+/* src/Estimators/d4est_estimator_bi.h:201 (d4est_estimator_bi.c:343-560) on the bound plan, which must carry the estimator
+ * (d4est_hip_plan_set_estimator).  As the reference: fcns->build_residual(p4est, ghost, ghost_data, prob_vecs, d4est_ops,
+ * d4est_geom_for_residual, d4est_quad, d4est_factors_for_residual, fcns->user) leaves the residual in prob_vecs->Au (with the bound mesh
+ * its apply_lhs already runs on the device); then u (field which_field) and Au go up and d4est_hip_estimator_bi runs.
+ * Penalty functions: the reference's are static inline, so their addresses identify nothing -- each of the three is EVALUATED at fixed
+ * probe arguments and matched against the ten closed forms of D4EST_HIP_EST_* (ids 1 / 9 and 3 / 6 are the same formula); no match,
+ * or ids / prefactor other than the plan's, aborts.  Dirichlet data: u_bndry_fcn(x, y, z, bndry_ctx) at the boundary Lobatto face
+ * nodes, taken from the Lobatto coordinates of d4est_hip_compat_bind_coordinates (required) through d4est_hip_plan_boundary_gather;
+ * element diameters from d4est_hip_compat_bind_element_diameters (required).  estimator_vtk (4 n, or NULL) receives the four terms;
+ * estimator_vtk_per_face must be NULL (not supported: aborts).  The returned array of n doubles is allocated with sc_malloc(p4est_package_id,
+ * .) when the process has libsc (found with dlsym(RTLD_DEFAULT, .)), so that the caller's P4EST_FREE releases it, else with malloc (plain-C
+ * hosts without libsc: free it with free). */
+double* d4est_estimator_bi_compute(p4est_t *p4est,d4est_elliptic_data_t *d4est_elliptic_data,d4est_elliptic_eqns_t *fcns,d4est_estimator_bi_penalty_data_t penalty_data,d4est_xyz_fcn_t u_bndry_fcn,void *bndry_ctx,d4est_ghost_t *d4est_ghost,d4est_ghost_data_t *d4est_ghost_data,d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geom_for_residual,d4est_mesh_data_t *d4est_factors_for_residual,d4est_geometry_t *d4est_geom_for_integrals,d4est_mesh_data_t *d4est_factors_for_integrals,d4est_quadrature_t *d4est_quad,int which_field,double *estimator_vtk,double *estimator_vtk_per_face);
 #endif /* D4EST_HIP_COMPAT_NO_TYPES */
 
 /* ---- binding (not in the reference) ------------------------------------------------------------------------------------------ */
@@ -226,6 +256,8 @@ void d4est_hip_compat_bind_flux(const void* p4est, double sipg_penalty_prefactor
 /* the node coordinates of the mesh (d4est_factors->xyz[d] at the Lobatto nodes, ->xyz_quad[d] at the quadrature nodes; host arrays that
  * stay the caller's; either may be NULL): where d4est_laplacian_build_rhs_with_strong_bc evaluates the source callback */
 void d4est_hip_compat_bind_coordinates(const void* p4est, double* xyz_lobatto[3], double* xyz_quad[3]);
+/* d4est_factors->diam_volume (host array of the local elements, stays the caller's): the h of the estimator's residual term */
+void d4est_hip_compat_bind_element_diameters(const void* p4est, const double* diam_volume);
 /* the Schwarz smoother of this mesh and its three [d4est_solver_schwarz] CG options, for d4est_solver_schwarz_iterate; NULL unbinds */
 void d4est_hip_compat_bind_schwarz(const void* p4est, d4est_hip_schwarz_t* sz, int subdomain_iter, double subdomain_atol, double subdomain_rtol);
 /* the reference's Schwarz metadata as the flat arrays d4est_hip_schwarz_create takes; outputs caller-allocated:
