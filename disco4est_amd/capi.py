@@ -111,6 +111,9 @@ SIGNATURES = {
     "d4est_hip_cheby_iterate": (None, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int]),
     "d4est_hip_cheby_update": (None, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp]),
     "d4est_hip_cg_eigs": (ctypes.c_double, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _c_double_p]),
+    "d4est_hip_cg_solve": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_double_p]),
+    "d4est_hip_cg_solve_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_double_p]),
+    "d4est_hip_fcg_solve": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp, _vp, _c_double_p]),
     "d4est_hip_copy_blocks": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "d4est_hip_plan_trace_offset": (ctypes.c_longlong, [_vp, ctypes.c_int]),
     "d4est_hip_plan_side_blocks": (ctypes.c_int, [_vp, ctypes.c_int]),
@@ -509,6 +512,57 @@ class Plan:
         hist = np.zeros(2 * imax)
         b = self.lib.d4est_hip_cg_eigs(self.handle, _ptr(u), _ptr(rhs), _ptr(Au), int(imax), int(use_new), hist.ctypes.data_as(_c_double_p))
         return b, hist
+
+    # ---- Krylov solves (d4est_solver_cg_solve, d4est_solver_fcg_solve)
+    PC_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p)
+
+    def cg_solve(self, u, rhs, Au, imax, atol, rtol):
+        """CG on apply_lhs from u (advanced in place); returns (iterations, history delta_0 .. delta_iterations)"""
+        for t in (u, rhs, Au):
+            assert t.numel() == self.local_nodes
+        hist = np.zeros(int(imax) + 1)
+        it = self.lib.d4est_hip_cg_solve(self.handle, _ptr(u), _ptr(rhs), _ptr(Au), int(imax), float(atol), float(rtol),
+                                         hist.ctypes.data_as(_c_double_p))
+        return it, hist[:it + 1]
+
+    def cg_solve_host(self, u_host, rhs_host, imax, atol, rtol):
+        """the host-vector form: returns (u, Au, iterations, history)"""
+        u = np.ascontiguousarray(u_host, dtype=np.float64).copy()
+        rhs = np.ascontiguousarray(rhs_host, dtype=np.float64)
+        assert u.size == self.local_nodes and rhs.size == self.local_nodes
+        Au = np.empty_like(u)
+        hist = np.zeros(int(imax) + 1)
+        it = self.lib.d4est_hip_cg_solve_host(self.handle, u.ctypes.data_as(_vp), rhs.ctypes.data_as(_vp), Au.ctypes.data_as(_vp),
+                                              int(imax), float(atol), float(rtol), hist.ctypes.data_as(_c_double_p))
+        return u, Au, it, hist[:it + 1]
+
+    def fcg_solve(self, u, rhs, Au, imax, atol, rtol, pc=None):
+        """FCG on apply_lhs from u (advanced in place); returns (iterations, history |r_k|).  pc: None (the identity), an object
+        with `pc_fn` / `pc_ctx` (a C d4est_hip_pc_fn and its context, passed straight through: no Python in the loop), or a
+        Python callable pc(r_ptr, z_ptr) that enqueues z = B r on the plan's stream"""
+        for t in (u, rhs, Au):
+            assert t.numel() == self.local_nodes
+        hist = np.zeros(max(int(imax), 1))
+        fn, ctx = None, None
+        if pc is not None and hasattr(pc, "pc_fn"):
+            fn, ctx = ctypes.c_void_p(pc.pc_fn), ctypes.c_void_p(pc.pc_ctx)
+        elif pc is not None:
+            def call(_ctx, r, z):
+                try:
+                    pc(r, z)
+                except BaseException:   # (as set_comm: a dropped exception would leave z unwritten)
+                    import sys
+                    import traceback
+                    sys.stderr.write("[D4EST_HIP_ABORT] exception in a preconditioner callback:\n")
+                    traceback.print_exc()
+                    sys.stderr.flush()
+                    os.abort()
+            cb = self.PC_FN(call)
+            self._cb_pc = cb
+            fn = ctypes.cast(cb, ctypes.c_void_p)
+        it = self.lib.d4est_hip_fcg_solve(self.handle, _ptr(u), _ptr(rhs), _ptr(Au), int(imax), float(atol), float(rtol), fn, ctx,
+                                          hist.ctypes.data_as(_c_double_p))
+        return it, hist[:it]
 
     def copy_blocks(self, n_blocks, src, src_off, dst, dst_off, length):
         """src/dst: float64 CUDA tensors; src_off/dst_off: int64 CUDA tensors; length: int32 CUDA tensor"""

@@ -247,6 +247,7 @@ void d4est_hip_plan_destroy(d4est_hip_plan_t* plan) {
   (void)hipFree(plan->d_work_p); (void)hipFree(plan->d_work_d); (void)hipFree(plan->d_work_r); (void)hipFree(plan->d_work_m); (void)hipFree(plan->d_lhs_c); (void)hipFree(plan->d_lhs_wjc);
   (void)hipFree(plan->d_lhs_block_off);
   d4est_hip::lhs_chain_destroy(plan);
+  d4est_hip::krylov_destroy(plan);
   (void)hipFree(plan->d_reduce); (void)hipFree(plan->d_ghost_trace);
   if (plan->h_stage) (void)hipHostFree(plan->h_stage);
   for (int i = 0; i < 4; ++i) (void)hipFree(plan->d_host[i]);
@@ -684,6 +685,18 @@ double d4est_hip_cg_eigs(d4est_hip_plan_t* plan, double* u_dev, const double* rh
   return d4est_hip::cg_eigs(plan, u_dev, rhs_dev, Au_dev, imax, use_new, history_host);
 }
 
+int d4est_hip_cg_solve(d4est_hip_plan_t* plan, double* u_dev, const double* rhs_dev, double* Au_dev, int imax, double atol, double rtol,
+                       double* history_host) {
+  check_plan(plan, "cg_solve");
+  return d4est_hip::cg_solve(plan, u_dev, rhs_dev, Au_dev, imax, atol, rtol, history_host);
+}
+
+int d4est_hip_fcg_solve(d4est_hip_plan_t* plan, double* u_dev, const double* rhs_dev, double* Au_dev, int imax, double atol, double rtol,
+                        d4est_hip_pc_fn pc, void* pc_ctx, double* history_host) {
+  check_plan(plan, "fcg_solve");
+  return d4est_hip::fcg_solve(plan, u_dev, rhs_dev, Au_dev, imax, atol, rtol, pc, pc_ctx, history_host);
+}
+
 void d4est_hip_copy_blocks(d4est_hip_plan_t* plan, int n_blocks, const double* src_dev, const long long* src_off_dev,
                            double* dst_dev, const long long* dst_off_dev, const int* len_dev) {
   check_plan(plan, "copy_blocks");
@@ -870,6 +883,22 @@ double d4est_hip_cg_eigs_host(d4est_hip_plan_t* plan, double* u_host, const doub
   stage_out_end(plan, 0, u_host);
   if (Au_host) stage_out_end(plan, 2, Au_host);
   return bound;
+}
+
+int d4est_hip_cg_solve_host(d4est_hip_plan_t* plan, double* u_host, const double* rhs_host, double* Au_host, int imax, double atol,
+                            double rtol, double* history_host) {
+  check_plan(plan, "cg_solve_host");
+  if (!u_host || !rhs_host) D4EST_HIP_ABORT("cg_solve_host: NULL vector");
+  ensure_host_mirrors(plan);
+  stage_in(plan, 0, u_host, plan->d_host[0]);
+  stage_in(plan, 1, rhs_host, plan->d_host[1]);
+  const int count = d4est_hip::cg_solve(plan, plan->d_host[0], plan->d_host[1], plan->d_host[2], imax, atol, rtol, history_host);
+  stage_out_begin(plan, 0, plan->d_host[0]);
+  if (Au_host) stage_out_begin(plan, 2, plan->d_host[2]);
+  HIP_CHECK(hipStreamSynchronize(plan->stream));
+  stage_out_end(plan, 0, u_host);
+  if (Au_host) stage_out_end(plan, 2, Au_host);
+  return count;
 }
 
 void d4est_hip_plan_set_jacobian(d4est_hip_plan_t* plan, const double* J_quad, int on_device) {

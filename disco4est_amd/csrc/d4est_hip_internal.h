@@ -142,7 +142,10 @@ struct d4est_hip_plan {
   int stream_mode = 0;            // 1: non-temporal metric / factor loads and A u stores (capi: update_stream_mode; kernels: with_ld)
   bool bc_inhomogeneous = false;   // non-zero Dirichlet data or Robin data is set (an affine, not linear, operator)
 
-  int tuning[D4EST_HIP_TUNE_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};  // -1 = auto  // see d4est_hip_plan_set_tuning
+  int tuning[D4EST_HIP_TUNE_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};  // -1 = auto  // see d4est_hip_plan_set_tuning
+
+  // Krylov solvers (d4est_hip_krylov.hip): vectors, reduction partials, device scalars and the pinned stop flag, allocated on first use
+  void* krylov = nullptr;   // d4est_hip::KrylovWork
 
   // generic-path scratch (allocated lazily)
   double* d_scratch = nullptr;
@@ -316,6 +319,12 @@ void launch_cheby_update(d4est_hip_plan* plan, int n, const double* rhs, const d
 void cheby_iterate(d4est_hip_plan* plan, double* u, const double* rhs, double* Au, double* r, int iter, double lmin, double lmax,
                    int compute_residual_at_end);
 double cg_eigs(d4est_hip_plan* plan, double* u, const double* rhs, double* Au, int imax, int use_new, double* hist_out);
+
+// d4est_hip_krylov.hip
+int cg_solve(d4est_hip_plan* plan, double* u, const double* rhs, double* Au, int imax, double atol, double rtol, double* hist_out);
+int fcg_solve(d4est_hip_plan* plan, double* u, const double* rhs, double* Au, int imax, double atol, double rtol, d4est_hip_pc_fn pc,
+              void* pc_ctx, double* hist_out);
+void krylov_destroy(d4est_hip_plan* plan);
 
 
 }  // namespace d4est_hip

@@ -91,7 +91,8 @@ enum d4est_hip_tuning_key {
   D4EST_HIP_TUNE_STREAM = 12,            /* stream mode of the volume kernels with more than 8192 elements or deg >= 8, and of the p = 8 ... 15 whole-operator kernel: the data an apply reads or writes exactly once (metric, mortar factors, A u) moves with the non-temporal hint. default (-1): on when metric + u + A u of one apply exceed 320 MB (they then do not fit the 256 MB Infinity Cache, and keeping them out of the caches leaves those to u: level 5, p = 7 stiffness 191 -> 156 us); 0 / 1 force it off / on.  Same numbers either way */
   D4EST_HIP_TUNE_HP_SPLIT = 13,          /* set before plan_set_faces.  Plans with hanging faces, every deg and deg_quad <= 7 (any number of ranks): 0 every side through the tiled mortar-record kernels; 1 the conforming sides of the whole mesh AND the small sides of the hanging faces (one mortar each, the hanging factor folded into the geometric factors) through the fast conforming face kernels, only the big sides (four mortars) through the record kernels; default (-1): that split unless more than half of the elements would stay with the record kernels (level-4 brick, p = 7, every 64th ... every 3rd octant refined: apply_aij 203 -> 139 ... 661 -> 448 us).  Round 4: plans with degrees up to 15 take the split too (their conforming sides through the tiled conforming kernels, on the two family lists where the plan has them), and the record kernels run in their unit form (a side's sub-mortar records on four wavefronts); environment D4EST_HIP_HP_SPLIT_FAST_ONLY=1 / D4EST_HIP_NO_HANG_UNITS=1 restore round 3's forms */
   D4EST_HIP_TUNE_HYBRID = 14,            /* set before plan_set_faces.  Mixed-degree and locally refined plans (one rank): 0 every element through the two-phase kernels; CLEAN elements -- deg_quad = deg <= 15 and all six sides conforming against a local element of the same degree or the domain boundary -- get the whole operator from the trace-free one-kernel path of their degree (faces_direct_kernel / operator_mw_kernel over an element list), only the rest runs traces + volume + flux, on lists.  default (-1): where that was measured to pay -- the clean elements are one degree bucket and at least half of the mesh (locally refined meshes of one degree: level 4, p = 7, every 64th octant refined, apply_aij 144 -> 125 us); with several clean buckets the largest one is kept where it holds at least half of the mesh (one dominant degree; the others' elements stay two-phase) -- or, at size (at least 2048 clean elements per clean bucket), every bucket --, else every bucket would be its own latency-structured launch and the two-phase kernels win at these sizes; 1: whenever there is a clean element.  Same operator either way (tests/test_hybrid_gpu.py).  Hanging-aware form (plans under the hp split, elements with deg <= 7; environment D4EST_HIP_HYBRID_NO_HANGING=1 switches it off; mixed-aware form likewise for a conforming side against a lower-degree neighbour, D4EST_HIP_HYBRID_NO_MIXED=1): a hanging side does not make an element dirty -- big sides stay with the record kernels, small sides read the big element's sub-mortar block from the trace array and export their own; on a locally refined mesh of one degree EVERY element then takes the one-kernel path (level 4, p = 7, every 64th octant refined: 125 -> 81 us) and cheby_iterate carries its update in the operator kernel and the record flux kernel */
-  D4EST_HIP_TUNE_COUNT = 15
+  D4EST_HIP_TUNE_KRYLOV_CHECK = 15,      /* d4est_hip_cg_solve: iterations enqueued between two host reads of the device stop flag (default -1 = 8); every value gives the same iterates, bit for bit, and the same count (iterations after the stop are no-ops on the device) */
+  D4EST_HIP_TUNE_COUNT = 16
 };
 void d4est_hip_plan_set_tuning(d4est_hip_plan_t* plan, int key, int value);
 /* name of the stiffness kernel the last d4est_hip_apply_stiffness_matrix selected (for reports / profiles) */
@@ -405,6 +406,36 @@ void d4est_hip_cheby_update(d4est_hip_plan_t* plan, int n, const double* rhs_dev
  * history_host (optional, 2*imax doubles) receives alpha_0..alpha_{imax-1}, beta_0..beta_{imax-1}. */
 double d4est_hip_cg_eigs(d4est_hip_plan_t* plan, double* u_dev, const double* rhs_dev, double* Au_dev, int imax, int use_new,
                          double* history_host);
+/* ---- Krylov solves on one plan (csrc/d4est_hip_krylov.hip) ---------------------------------------------------------------------
+ * The operator is the plan's apply_lhs (zeroth-order term and communication hooks included).  u_dev is the start and receives the
+ * solution; Au_dev is work that is left as the reference leaves vecs->Au.  The arithmetic is the reference's, statement for statement;
+ * the scalars never leave the device (one-thread kernels form them from device memory), the dot products are two-stage reductions in a
+ * fixed order without atomics (bit-identical from run to run), and each reduction point calls the plan's allreduce hook once, with the
+ * scalar count of the reference's sc_allreduce.  Vectors and scalars live on the plan (allocated on the first call).
+ *
+ * d4est_solver_cg_solve (src/Solver/d4est_solver_cg.c:76-197): r = rhs - A u, d = r, delta_0 = r.r; while i < imax and
+ * delta > atol^2 + delta_0 rtol^2: alpha = delta / d.Ad, u += alpha d, r -= alpha Ad, beta = r.r / delta, d = r + beta d.  Returns the
+ * iteration count; history_host (optional, imax + 1 doubles) receives delta_0, delta_1, ... (count + 1 values); Au_dev ends as A d of the
+ * last iteration (A u of the start when no iteration ran).  Iterations are enqueued in batches of D4EST_HIP_TUNE_KRYLOV_CHECK: the
+ * scalar kernel raises a device flag when the stop test holds, every vector update after it is a no-op, and the host reads the flag
+ * and the count from pinned memory once per batch -- the only host synchronisations.  The allreduce hook is called for every
+ * enqueued iteration (1 + 2 per iteration; exactly the reference's count with D4EST_HIP_TUNE_KRYLOV_CHECK = 1).
+ * The _host form takes host vectors (u_host in / out, Au_host optional) through the plan's pinned staging, as the other *_host entries. */
+int d4est_hip_cg_solve(d4est_hip_plan_t* plan, double* u_dev, const double* rhs_dev, double* Au_dev, int imax, double atol, double rtol,
+                       double* history_host);
+int d4est_hip_cg_solve_host(d4est_hip_plan_t* plan, double* u_host, const double* rhs_host, double* Au_host, int imax, double atol,
+                            double rtol, double* history_host);
+/* preconditioner z = B r: device vectors of local_nodes doubles, work ordered on the plan's stream (the reference's pc_apply,
+ * src/LinearAlgebra/d4est_krylov_pc.h) */
+typedef void (*d4est_hip_pc_fn)(void* ctx, const double* r_dev, double* z_dev);
+/* d4est_solver_fcg_solve as the reference builds it (src/Solver/d4est_solver_fcg_improved.c:97-346; CMakeLists.txt:127): r = rhs - A u,
+ * tol = atol + rtol |r_0|; for k < imax: v = B r (pc == NULL: the identity, do_not_use_preconditioner = 1), w = A v, one pass for
+ * v.r, v.w (and from k = 1 on v.q, r.r; one allreduce of 2 or 4 scalars), the improved-FCG recurrences of rho, gamma, d, q in one
+ * scalar kernel and one pass for d, q, u, r; stop when k > 0 and |r_k| <= tol AFTER the update (r_k: the residual before it).  Returns
+ * the iteration count (updates made); history_host (optional, imax doubles) receives |r_k| of every iteration (|r_0| at k = 0).  One
+ * host synchronisation per iteration (the preconditioner dominates).  Au_dev ends as A u of the start, as in the reference. */
+int d4est_hip_fcg_solve(d4est_hip_plan_t* plan, double* u_dev, const double* rhs_dev, double* Au_dev, int imax, double atol, double rtol,
+                        d4est_hip_pc_fn pc, void* pc_ctx, double* history_host);
 /* pack / unpack of face-trace blocks for the ghost exchange: dst[dst_off[b]+i] = src[src_off[b]+i], i < len[b];
  * the three index arrays are DEVICE arrays of n_blocks entries; runs on the plan's stream.  Replaces the per-mirror
  * memcpy loop of d4est_ghost_data_exchange (src/Mesh/d4est_ghost_data.c:196-236). */
