@@ -68,6 +68,7 @@ SIGNATURES = {
     "d4est_hip_transfer_coarse_nodes": (ctypes.c_longlong, [_vp]),
     "d4est_hip_transfer_fine_nodes": (ctypes.c_longlong, [_vp]),
     "d4est_hip_transfer_prolong": (None, [_vp, _vp, _vp]),
+    "d4est_hip_transfer_prolong_add": (None, [_vp, _vp, _vp]),
     "d4est_hip_transfer_restrict": (None, [_vp, _vp, _vp]),
     "d4est_hip_transfer_project": (None, [_vp, _vp, _vp]),
     "d4est_hip_schwarz_create": (_vp, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
@@ -114,6 +115,21 @@ SIGNATURES = {
     "d4est_hip_cg_solve": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_double_p]),
     "d4est_hip_cg_solve_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_double_p]),
     "d4est_hip_fcg_solve": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp, _vp, _c_double_p]),
+    "d4est_hip_multigrid_check": (ctypes.c_int, [ctypes.c_int, _vp, _vp]),
+    "d4est_hip_multigrid_create": (_vp, [ctypes.c_int, _vp, _vp]),
+    "d4est_hip_multigrid_destroy": (None, [_vp]),
+    "d4est_hip_multigrid_set_stream": (None, [_vp, _vp]),
+    "d4est_hip_multigrid_set_smoother_cheby": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                                              ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "d4est_hip_multigrid_set_bottom_solver_cg": (None, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double]),
+    "d4est_hip_multigrid_set_bottom_solver_cheby": (None, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int]),
+    "d4est_hip_multigrid_ready": (ctypes.c_int, [_vp]),
+    "d4est_hip_multigrid_vcycle": (None, [_vp, _vp, _vp, _vp, ctypes.c_int]),
+    "d4est_hip_multigrid_vcycle_r2": (ctypes.c_double, [_vp]),
+    "d4est_hip_multigrid_solve": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_double_p]),
+    "d4est_hip_multigrid_set_pc": (None, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double]),
+    "d4est_hip_multigrid_pc_apply": (None, [_vp, _vp, _vp]),
+    "d4est_hip_multigrid_get_info": (None, [_vp, _c_double_p, _c_int_p, _c_int_p]),
     "d4est_hip_copy_blocks": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "d4est_hip_plan_trace_offset": (ctypes.c_longlong, [_vp, ctypes.c_int]),
     "d4est_hip_plan_side_blocks": (ctypes.c_int, [_vp, ctypes.c_int]),
@@ -609,6 +625,11 @@ class Transfer:
         assert x_coarse.numel() == self.coarse_nodes and x_fine.numel() == self.fine_nodes
         self.lib.d4est_hip_transfer_prolong(self.handle, _ptr(x_coarse), _ptr(x_fine))
 
+    def prolong_add(self, x_coarse, u_fine):
+        """u_fine += P x_coarse in one kernel; bit-identical to prolong into a scratch vector followed by +="""
+        assert x_coarse.numel() == self.coarse_nodes and u_fine.numel() == self.fine_nodes
+        self.lib.d4est_hip_transfer_prolong_add(self.handle, _ptr(x_coarse), _ptr(u_fine))
+
     def restrict(self, x_fine, x_coarse):
         assert x_coarse.numel() == self.coarse_nodes and x_fine.numel() == self.fine_nodes
         self.lib.d4est_hip_transfer_restrict(self.handle, _ptr(x_fine), _ptr(x_coarse))
@@ -629,3 +650,108 @@ class Transfer:
         if self.handle:
             self.lib.d4est_hip_transfer_destroy(self.handle)
             self.handle = None
+
+
+def multigrid_check(plans, transfers, n_levels=None):
+    """d4est_hip_multigrid_check: 0, or 1 (fewer than two levels), 2 (a missing entry: None), 3 (a transfer's node counts do not match
+    its two plans).  plans: coarsest first; transfers[l] connects plans[l] and plans[l + 1]."""
+    lib = load_library()
+    n = len(plans) if n_levels is None else int(n_levels)
+    pa = (ctypes.c_void_p * max(len(plans), 1))(*[(p.handle if p is not None else None) for p in plans])
+    ta = (ctypes.c_void_p * max(len(transfers), 1))(*[(t.handle if t is not None else None) for t in transfers])
+    return lib.d4est_hip_multigrid_check(n, pa, ta)
+
+
+class Multigrid:
+    """The hp-multigrid V-cycle, solve and preconditioner on the device (d4est_hip_multigrid_*): plans[0] is the bottom (coarsest)
+    level, plans[-1] the top (finest); transfers[l] connects plans[l] (coarse) and plans[l + 1] (fine).  Every plan carries its own
+    operator (faces, zeroth-order term, hooks).  `pc_fn` / `pc_ctx` make the object a preconditioner of Plan.fcg_solve(pc=mg): the C
+    function pointer and its context are passed straight through, no Python in the loop."""
+
+    def __init__(self, plans, transfers):
+        self.lib = load_library()
+        self.handle = None
+        self.plans, self.transfers = list(plans), list(transfers)   # kept alive: the object only borrows them
+        code = multigrid_check(self.plans, self.transfers)
+        if code != 0:            # (d4est_hip_multigrid_create would abort the process)
+            raise ValueError("d4est_hip_multigrid_check returned %d" % code)
+        pa = (ctypes.c_void_p * len(self.plans))(*[p.handle for p in self.plans])
+        ta = (ctypes.c_void_p * len(self.transfers))(*[t.handle for t in self.transfers])
+        self.handle = self.lib.d4est_hip_multigrid_create(len(self.plans), pa, ta)
+        self.n_levels = len(self.plans)
+        self.local_nodes = self.plans[-1].local_nodes
+        self.pc_fn = ctypes.cast(self.lib.d4est_hip_multigrid_pc_apply, ctypes.c_void_p).value
+        self.pc_ctx = self.handle
+
+    def set_stream(self, stream):
+        h = getattr(stream, "cuda_stream", stream)
+        self.lib.d4est_hip_multigrid_set_stream(self.handle, ctypes.c_void_p(int(h)))
+
+    def set_smoother_cheby(self, cheby_imax, cheby_eigs_cg_imax, cheby_eigs_lmax_lmin_ratio, cheby_eigs_max_multiplier=1.0,
+                           cheby_eigs_reuse_fromdownvcycle=0, cheby_eigs_reuse_fromlastvcycle=0, cheby_use_new_cg_eigs=0,
+                           cheby_use_zero_guess_for_eigs=0):
+        """the [mg_smoother_cheby] keys; returns the C code (0 = accepted; 1 = zero guess without reuse_fromdownvcycle; 2 = bad counts)"""
+        return self.lib.d4est_hip_multigrid_set_smoother_cheby(
+            self.handle, int(cheby_imax), int(cheby_eigs_cg_imax), float(cheby_eigs_lmax_lmin_ratio), float(cheby_eigs_max_multiplier),
+            int(cheby_eigs_reuse_fromdownvcycle), int(cheby_eigs_reuse_fromlastvcycle), int(cheby_use_new_cg_eigs),
+            int(cheby_use_zero_guess_for_eigs))
+
+    def set_bottom_solver_cg(self, bottom_imax, bottom_atol, bottom_rtol):
+        self.lib.d4est_hip_multigrid_set_bottom_solver_cg(self.handle, int(bottom_imax), float(bottom_atol), float(bottom_rtol))
+
+    def set_bottom_solver_cheby(self, cheby_imax, cheby_eigs_cg_imax, lmax_lmin_ratio, max_multiplier=1.0, use_new_cg_eigs=0):
+        self.lib.d4est_hip_multigrid_set_bottom_solver_cheby(self.handle, int(cheby_imax), int(cheby_eigs_cg_imax), float(lmax_lmin_ratio),
+                                                             float(max_multiplier), int(use_new_cg_eigs))
+
+    def set_pc(self, vcycle_imax=1, vcycle_atol=0.0, vcycle_rtol=0.0):
+        self.lib.d4est_hip_multigrid_set_pc(self.handle, int(vcycle_imax), float(vcycle_atol), float(vcycle_rtol))
+
+    def ready(self):
+        return self.lib.d4est_hip_multigrid_ready(self.handle)
+
+    def _require_ready(self):
+        if not self.ready():     # (the C entry would abort the process)
+            raise RuntimeError("Multigrid: set a smoother and a bottom solver first")
+
+    def vcycle(self, u, rhs, Au, vcycle_index=0):
+        """one V-cycle on A u = rhs; returns vcycle_r2_local = |rhs - A u|^2 of the last smoother call"""
+        self._require_ready()
+        for t in (u, rhs, Au):
+            assert t.numel() == self.local_nodes
+        self.lib.d4est_hip_multigrid_vcycle(self.handle, _ptr(u), _ptr(rhs), _ptr(Au), int(vcycle_index))
+        return self.lib.d4est_hip_multigrid_vcycle_r2(self.handle)
+
+    def solve(self, u, rhs, Au, vcycle_imax, vcycle_atol, vcycle_rtol):
+        """d4est_solver_multigrid_solve from u (advanced in place); returns (cycles, history r2_0 .. r2_cycles)"""
+        self._require_ready()
+        for t in (u, rhs, Au):
+            assert t.numel() == self.local_nodes
+        hist = np.zeros(int(vcycle_imax) + 1)
+        n = self.lib.d4est_hip_multigrid_solve(self.handle, _ptr(u), _ptr(rhs), _ptr(Au), int(vcycle_imax), float(vcycle_atol),
+                                               float(vcycle_rtol), hist.ctypes.data_as(_c_double_p))
+        return n, hist[:n + 1]
+
+    def pc_apply(self, r, z):
+        """z = B r: the preconditioner as Plan.fcg_solve calls it through the C pointer"""
+        self._require_ready()
+        assert r.numel() == self.local_nodes and z.numel() == self.local_nodes
+        self.lib.d4est_hip_multigrid_pc_apply(self.handle, _ptr(r), _ptr(z))
+
+    def info(self):
+        """(eigs per level after the multiplier, V-cycles of the last solve, bottom iterations of the last cycle)"""
+        eigs = np.zeros(self.n_levels)
+        vc, bi = ctypes.c_int(0), ctypes.c_int(0)
+        self.lib.d4est_hip_multigrid_get_info(self.handle, eigs.ctypes.data_as(_c_double_p), ctypes.byref(vc), ctypes.byref(bi))
+        return eigs, vc.value, bi.value
+
+    def destroy(self):
+        if self.handle:
+            self.lib.d4est_hip_multigrid_destroy(self.handle)
+            self.handle = None
+            self.pc_ctx = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass

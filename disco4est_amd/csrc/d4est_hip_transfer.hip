@@ -20,7 +20,9 @@
 
 namespace d4est_hip {
 
-// one workgroup per fine element
+// one workgroup per fine element; ADD: xf += P xc (each entry of P xc rounded to a double first, then added: the same number as the
+// prolongation into a vector followed by an axpy with 1.0, d4est_solver_multigrid.c:1182-1250)
+template <bool ADD>
 __global__ __launch_bounds__(256) void prolong_kernel(const double* __restrict__ xc, double* __restrict__ xf,
                                                       const int* __restrict__ child, const long long* __restrict__ off,
                                                       const double* __restrict__ ops, const int* __restrict__ list, int n_children, int max_n3) {
@@ -35,7 +37,7 @@ __global__ __launch_bounds__(256) void prolong_kernel(const double* __restrict__
     for (int i = threadIdx.x; i < NH * NH * NH; i += blockDim.x) a[i] = xc[co + i];
     __syncthreads();
     tensor3<false>(ops + d[3], ops + d[4], ops + d[5], NH, Nh, a, b);
-    for (int i = threadIdx.x; i < Nh * Nh * Nh; i += blockDim.x) xf[fo + i] = b[i];
+    for (int i = threadIdx.x; i < Nh * Nh * Nh; i += blockDim.x) xf[fo + i] = ADD ? __dadd_rn(xf[fo + i], b[i]) : b[i];
     __syncthreads();
   }
 }
@@ -103,8 +105,9 @@ struct TransferCfg {
   static constexpr int CGMAX = cg_max();
 };
 
-// t: the thread's index in its group of TransferCfg::THREADS threads (the whole workgroup for the prolongation)
-template <int NH, int Nh>
+// t: the thread's index in its group of TransferCfg::THREADS threads (the whole workgroup for the prolongation); ADD: xf_e += P xc_e
+// (the z-line's entries are complete doubles when they meet the fine vector: bit-identical to prolong followed by +=)
+template <int NH, int Nh, bool ADD>
 __device__ __forceinline__ void prolong_body(const double* __restrict__ xc_e, double* __restrict__ xf_e, const double* PxT,
                                              const double* PyT, const double* PzT, double* lds, int t) {
   constexpr int RSB = Nh | 1;
@@ -135,11 +138,11 @@ __device__ __forceinline__ void prolong_body(const double* __restrict__ xc_e, do
     for (int k = 0; k < NH; ++k) x[k] = C[k * Nh * Nh + t];
     contract_n<NH, Nh>(PzT, x, y);
 #pragma unroll
-    for (int k = 0; k < Nh; ++k) xf_e[k * Nh * Nh + t] = y[k];
+    for (int k = 0; k < Nh; ++k) xf_e[k * Nh * Nh + t] = ADD ? __dadd_rn(xf_e[k * Nh * Nh + t], y[k]) : y[k];
   }
 }
 
-template <int NH, int DMAX>
+template <int NH, int DMAX, bool ADD>
 __global__ __launch_bounds__((TransferCfg<NH, DMAX>::THREADS)) void prolong_fast_kernel(const double* __restrict__ xc, double* __restrict__ xf,
                                                                                       const int* __restrict__ child,
                                                                                       const long long* __restrict__ off,
@@ -153,10 +156,10 @@ __global__ __launch_bounds__((TransferCfg<NH, DMAX>::THREADS)) void prolong_fast
   double* xf_e = xf + off[2 * c + 1];
   const double *px = opsT + d[3], *py = opsT + d[4], *pz = opsT + d[5];
   const int t = threadIdx.x;
-  if (dN == 0) prolong_body<NH, NH>(xc_e, xf_e, px, py, pz, smem, t);
-  if constexpr (DMAX >= 1) { if (dN == 1) prolong_body<NH, NH + 1>(xc_e, xf_e, px, py, pz, smem, t); }
-  if constexpr (DMAX >= 2) { if (dN == 2) prolong_body<NH, NH + 2>(xc_e, xf_e, px, py, pz, smem, t); }
-  if constexpr (DMAX >= 3) { if (dN == 3) prolong_body<NH, NH + 3>(xc_e, xf_e, px, py, pz, smem, t); }
+  if (dN == 0) prolong_body<NH, NH, ADD>(xc_e, xf_e, px, py, pz, smem, t);
+  if constexpr (DMAX >= 1) { if (dN == 1) prolong_body<NH, NH + 1, ADD>(xc_e, xf_e, px, py, pz, smem, t); }
+  if constexpr (DMAX >= 2) { if (dN == 2) prolong_body<NH, NH + 2, ADD>(xc_e, xf_e, px, py, pz, smem, t); }
+  if constexpr (DMAX >= 3) { if (dN == 3) prolong_body<NH, NH + 3, ADD>(xc_e, xf_e, px, py, pz, smem, t); }
 }
 
 // acc (the thread's z-line of the coarse element) += its part of  op_z (x) op_y (x) op_x  applied to one fine element; op* are Nh x NH
@@ -391,12 +394,12 @@ static void fast_lds_limit(K kernel, size_t bytes) {
 }
 
 // launches of one (NH, DMAX) list
-template <int NH, int DMAX>
+template <int NH, int DMAX, bool ADD>
 static void go_prolong(d4est_hip_transfer* t, const double* xc, double* xf, const int* list, int n) {
   using C = TransferCfg<NH, DMAX>;
   const size_t lds = (size_t)C::LDS_PROLONG * sizeof(double);
-  fast_lds_limit(prolong_fast_kernel<NH, DMAX>, lds);
-  hipLaunchKernelGGL((prolong_fast_kernel<NH, DMAX>), dim3(n), dim3(C::THREADS), lds, t->stream, xc, xf, t->d_child, t->d_off, t->d_opsT, list);
+  fast_lds_limit(prolong_fast_kernel<NH, DMAX, ADD>, lds);
+  hipLaunchKernelGGL((prolong_fast_kernel<NH, DMAX, ADD>), dim3(n), dim3(C::THREADS), lds, t->stream, xc, xf, t->d_child, t->d_off, t->d_opsT, list);
 }
 template <int NH, int DMAX>
 static void go_restrict(d4est_hip_transfer* t, const double* xf, double* xc, const double* ops, const int* list, int n, int n_children) {
@@ -413,12 +416,13 @@ static void go_restrict(d4est_hip_transfer* t, const double* xf, double* xc, con
 
 #define D4EST_HIP_TRANSFER_NH(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
 
+template <bool ADD>
 static void launch_fast_prolong(d4est_hip_transfer* t, const double* xc, double* xf, int NH, int dmax, const int* list, int n) {
 #define X(N_)                                                         \
   if (NH == N_) {                                                     \
-    if (dmax == 0) go_prolong<N_, 0>(t, xc, xf, list, n);             \
-    else if (dmax == 1) go_prolong<N_, 1>(t, xc, xf, list, n);        \
-    else go_prolong<N_, 3>(t, xc, xf, list, n);                       \
+    if (dmax == 0) go_prolong<N_, 0, ADD>(t, xc, xf, list, n);        \
+    else if (dmax == 1) go_prolong<N_, 1, ADD>(t, xc, xf, list, n);   \
+    else go_prolong<N_, 3, ADD>(t, xc, xf, list, n);                  \
     return;                                                           \
   }
   D4EST_HIP_TRANSFER_NH(X)
@@ -707,18 +711,29 @@ void d4est_hip_transfer_set_stream(d4est_hip_transfer_t* t, void* hip_stream) {
 long long d4est_hip_transfer_coarse_nodes(const d4est_hip_transfer_t* t) { return t ? t->coarse_nodes : -1; }
 long long d4est_hip_transfer_fine_nodes(const d4est_hip_transfer_t* t) { return t ? t->fine_nodes : -1; }
 
-void d4est_hip_transfer_prolong(d4est_hip_transfer_t* t, const double* x_coarse_dev, double* x_fine_dev) {
-  if (!t) D4EST_HIP_ABORT("transfer_prolong: NULL transfer");
+extern "C++" {
+template <bool ADD>
+static void launch_prolong(d4est_hip_transfer_t* t, const double* x_coarse_dev, double* x_fine_dev, const char* who) {
+  if (!t) D4EST_HIP_ABORT("%s: NULL transfer", who);
   if (t->n_children == 0) return;
   for (const d4est_hip_transfer::List& L : t->prolong_lists) {
-    if (L.NH > 0) { d4est_hip::launch_fast_prolong(t, x_coarse_dev, x_fine_dev, L.NH, L.dmax, t->d_lists + L.first, L.n); continue; }
+    if (L.NH > 0) { d4est_hip::launch_fast_prolong<ADD>(t, x_coarse_dev, x_fine_dev, L.NH, L.dmax, t->d_lists + L.first, L.n); continue; }
     const int n3 = t->max_n * t->max_n * t->max_n;
     const size_t lds = (size_t)2 * n3 * sizeof(double);
-    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(d4est_hip::prolong_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(d4est_hip::prolong_kernel, dim3(std::min(L.n, 65536)), dim3(256), lds, t->stream, x_coarse_dev, x_fine_dev,
+    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(d4est_hip::prolong_kernel<ADD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(d4est_hip::prolong_kernel<ADD>, dim3(std::min(L.n, 65536)), dim3(256), lds, t->stream, x_coarse_dev, x_fine_dev,
                        t->d_child, t->d_off, t->d_ops, t->d_lists + L.first, L.n, n3);
   }
   HIP_CHECK(hipGetLastError());
+}
+}   // extern "C++"
+
+void d4est_hip_transfer_prolong(d4est_hip_transfer_t* t, const double* x_coarse_dev, double* x_fine_dev) {
+  launch_prolong<false>(t, x_coarse_dev, x_fine_dev, "transfer_prolong");
+}
+
+void d4est_hip_transfer_prolong_add(d4est_hip_transfer_t* t, const double* x_coarse_dev, double* u_fine_dev) {
+  launch_prolong<true>(t, x_coarse_dev, u_fine_dev, "transfer_prolong_add");
 }
 
 static void launch_restrict(d4est_hip_transfer_t* t, const double* x_fine_dev, double* x_coarse_dev, bool project, const char* who) {

@@ -549,6 +549,10 @@ long long d4est_hip_transfer_coarse_nodes(const d4est_hip_transfer_t* t);
 long long d4est_hip_transfer_fine_nodes(const d4est_hip_transfer_t* t);
 /* x_fine = P x_coarse (d4est_operators_apply_p_prolong / _hp_prolong per item) */
 void d4est_hip_transfer_prolong(d4est_hip_transfer_t* t, const double* x_coarse_dev, double* x_fine_dev);
+/* u_fine += P x_coarse in ONE kernel: the coarse-grid correction of the V-cycle (d4est_solver_multigrid.c:1182-1250: copy err -> rres,
+ * prolong into the fine rres, axpy 1.0 into u) without the fine-level intermediate.  Every entry of P x_coarse is rounded to a double
+ * before it is added, so the result is bit-identical to d4est_hip_transfer_prolong into a scratch vector followed by u_fine += scratch. */
+void d4est_hip_transfer_prolong_add(d4est_hip_transfer_t* t, const double* x_coarse_dev, double* u_fine_dev);
 /* x_coarse = P^T x_fine (d4est_operators_apply_p_prolong_transpose / _hp_prolong_transpose per item; overwrites x_coarse) */
 void d4est_hip_transfer_restrict(d4est_hip_transfer_t* t, const double* x_fine_dev, double* x_coarse_dev);
 /* x_coarse = L2 projection of x_fine (d4est_operators_apply_p_restrict / _hp_restrict per item, src/dGMath/d4est_operators.c:1205-1230,
@@ -566,6 +570,74 @@ void d4est_hip_transfer_project(d4est_hip_transfer_t* t, const double* x_fine_de
 long long d4est_hip_transfer_fine_matrix_nodes(const d4est_hip_transfer_t* t);
 long long d4est_hip_transfer_coarse_matrix_nodes(const d4est_hip_transfer_t* t);
 void d4est_hip_transfer_galerkin_blocks(d4est_hip_transfer_t* t, const double* fine_blocks_dev, double* coarse_blocks_dev, int literal_window);
+
+/* ---- the hp-multigrid V-cycle, solve and preconditioner (csrc/d4est_hip_multigrid.hip) ---------------------------------------------
+ * d4est_solver_multigrid_vcycle / d4est_solver_multigrid_solve (src/Solver/d4est_solver_multigrid.c:751-1348, :1420-1506) with the
+ * Chebyshev smoother driver (d4est_solver_multigrid_smoother_cheby.c:222-376), the CG and Chebyshev bottom solvers
+ * (d4est_solver_multigrid_bottom_solver_cg.c:48-198, _cheby.c:59-113) and d4est_krylov_pc_multigrid_apply
+ * (src/Solver/d4est_krylov_pc_multigrid.c:40-77) on a device-resident hierarchy.  Levels as in the reference: 0 = bottom (coarsest) ...
+ * n_levels - 1 = top (finest).  plans[l] is level l's operator -- geometry, faces, the zeroth-order term in whichever form
+ * (coefficient on the top, element blocks or Galerkin chain below), communication hooks: all the caller's, with homogeneous boundary
+ * data on every level (build_rhs_with_strong_bc moved g into rhs) -- and transfers[l] connects level l (coarse) and l + 1 (fine).  A d4est
+ * host builds transfers[l] from coarse_grid_refinement[] of the reference's V-cycle (hrefine, degH, degh per coarse element; hrefine = 2,
+ * an element that is not coarsened, is a copied item: hrefine 0 with degh = degH).  The objects stay the caller's and must outlive this
+ * one.  create propagates the finest plan's stream to every plan and transfer (ordering between levels is stream order and nothing else)
+ * and allocates the workspace once: one arena per vector kind (Ae, err, res below the top; rres on every level) laid out like the
+ * reference's *_at0 arrays with stride_to_fine_data.  It aborts, with the message of the code, unless d4est_hip_multigrid_check
+ * returns 0: 1 n_levels < 2 (the reference's abort at :1435-1438), 2 a NULL entry, 3 a transfer whose coarse / fine node counts are not
+ * those of its two plans.
+ * Not part of the object: the Schwarz smoother slot (d4est_hip_schwarz_smooth has the per-level smoother's contract, r = rhs - A u on
+ * exit, and can go behind the same internal interface), the reuse_smoother and PETSc bottom solvers, the reference-named compat entry
+ * points, hierarchies coarsened across ranks (every level's hooks are simply used).  The object never changes a plan's tuning: a
+ * caller may set D4EST_HIP_TUNE_GRAPH (key 9) on launch-bound coarse plans itself. */
+typedef struct d4est_hip_multigrid d4est_hip_multigrid_t;
+int d4est_hip_multigrid_check(int n_levels, d4est_hip_plan_t* const* plans, d4est_hip_transfer_t* const* transfers);
+d4est_hip_multigrid_t* d4est_hip_multigrid_create(int n_levels, d4est_hip_plan_t* const* plans, d4est_hip_transfer_t* const* transfers);
+void d4est_hip_multigrid_destroy(d4est_hip_multigrid_t* mg);
+/* every plan and transfer of the hierarchy onto this stream (hipStream_t as void*) */
+void d4est_hip_multigrid_set_stream(d4est_hip_multigrid_t* mg, void* hip_stream);
+/* The [mg_smoother_cheby] keys of the reference's input file, same meaning.  Per smoother call: when eigs_compute is set -- at PRE_V it
+ * is 0 only if reuse_fromlastvcycle and vcycle_index != 0, at UPV_PRE_SMOOTH it is 0 if reuse_fromdownvcycle or (reuse_fromlastvcycle
+ * and vcycle_index != 0) -- cg_eigs runs cheby_eigs_cg_imax iterations FROM THE CURRENT ITERATE, WHICH IT ADVANCES (as in the reference;
+ * with cheby_use_zero_guess_for_eigs from a zero scratch vector instead) and eigs[level] = bound * cheby_eigs_max_multiplier; then
+ * cheby_imax iterations on the window [eigs[level] / ratio, eigs[level]], the residual rhs - A u left for the restriction.
+ * Returns 0, or -- leaving the object without a smoother -- 1 for cheby_use_zero_guess_for_eigs = 1 without
+ * cheby_eigs_reuse_fromdownvcycle = 1 (the reference's abort at smoother_cheby.c:313-318), 2 for a negative cheby_imax,
+ * cheby_eigs_cg_imax < 1 or a ratio that is not positive. */
+int d4est_hip_multigrid_set_smoother_cheby(d4est_hip_multigrid_t* mg, int cheby_imax, int cheby_eigs_cg_imax, double cheby_eigs_lmax_lmin_ratio,
+                                           double cheby_eigs_max_multiplier, int cheby_eigs_reuse_fromdownvcycle,
+                                           int cheby_eigs_reuse_fromlastvcycle, int cheby_use_new_cg_eigs, int cheby_use_zero_guess_for_eigs);
+/* [mg_bottom_solver_cg]: d4est_hip_cg_solve on plans[0] from err = 0 */
+void d4est_hip_multigrid_set_bottom_solver_cg(d4est_hip_multigrid_t* mg, int bottom_imax, double bottom_atol, double bottom_rtol);
+/* [mg_bottom_solver_cheby]: cg_eigs from the current iterate on every call, the multiplier, cheby_imax iterations */
+void d4est_hip_multigrid_set_bottom_solver_cheby(d4est_hip_multigrid_t* mg, int cheby_imax, int cheby_eigs_cg_imax, double lmax_lmin_ratio,
+                                                 double max_multiplier, int use_new_cg_eigs);
+/* 1 once a smoother and a bottom solver are set, else 0; vcycle / solve / pc_apply abort while it is 0 */
+int d4est_hip_multigrid_ready(const d4est_hip_multigrid_t* mg);
+/* One V-cycle on A u = rhs (device vectors of the top level's local_nodes; Au is work, left as the last smoother call leaves it).
+ * vcycle_index is vcycle_num_finished as the eigenvalue-reuse rules see it.  Down, level = top ... 1: err = 0, smooth (u, rhs, Au) on
+ * the top / (err, res, Ae) below it, res_{level-1} = P^T (rhs - A u).  Bottom: err_0 = 0, the bottom solver.  Up, level = 0 ... top - 1:
+ * u_{level+1} += P err_level (d4est_hip_transfer_prolong_add; environment D4EST_HIP_MG_UNFUSED_CORRECTION=1, read at create: prolong
+ * and add as two kernels, same numbers), smooth.  No host synchronisation beyond those of cg_eigs / cg_solve. */
+void d4est_hip_multigrid_vcycle(d4est_hip_multigrid_t* mg, double* u_dev, const double* rhs_dev, double* Au_dev, int vcycle_index);
+/* vcycle_r2_local of the last V-cycle: |rhs - A u|^2 of the top level's final smoother call (:1330-1332), a fixed-order two-stage
+ * reduction without atomics (bit-identical from run to run); reads the device scalar (synchronises the stream) */
+double d4est_hip_multigrid_vcycle_r2(d4est_hip_multigrid_t* mg);
+/* d4est_solver_multigrid_solve: r2_0 = |rhs - A u|^2 (one apply, one call of the finest plan's allreduce hook with 1 scalar), stoptol =
+ * rtol^2 r2_0 + atol^2; while n < vcycle_imax and r2 > stoptol: one V-cycle with index n, r2 = allreduce(vcycle_r2) (one hook call),
+ * n++, break if sqrt(r2 / r2_last) >= 0.99, else r2_last = r2.  The host reads r2 once per cycle.  Returns the V-cycles done;
+ * history_host (optional, vcycle_imax + 1 doubles) receives the global r2 before the first and after each cycle. */
+int d4est_hip_multigrid_solve(d4est_hip_multigrid_t* mg, double* u_dev, const double* rhs_dev, double* Au_dev, int vcycle_imax,
+                              double vcycle_atol, double vcycle_rtol, double* history_host);
+/* d4est_krylov_pc_multigrid_apply as a d4est_hip_pc_fn (ctx = the multigrid object): z = 0, an Au of the object's own, then
+ * d4est_hip_multigrid_solve(z, rhs = r) with the parameters stored by d4est_hip_multigrid_set_pc (default: one V-cycle, atol = rtol = 0).
+ * A d4est host binds d4est_krylov_pc_t.pc_apply to it; d4est_hip_fcg_solve takes it as pc with pc_ctx = the object. */
+void d4est_hip_multigrid_set_pc(d4est_hip_multigrid_t* mg, int vcycle_imax, double vcycle_atol, double vcycle_rtol);
+void d4est_hip_multigrid_pc_apply(void* mg, const double* r_dev, double* z_dev);
+/* eigs_host[n_levels]: the spectral bound last used per level, after the multiplier (-1: none yet; level 0 is never smoothed and holds
+ * the bottom Chebyshev solver's bound when that solver is set); the V-cycles of the last solve; the bottom solver's iterations in the
+ * last cycle (CG: iterations made; Chebyshev: cheby_imax).  Any output may be NULL. */
+void d4est_hip_multigrid_get_info(const d4est_hip_multigrid_t* mg, double* eigs_host, int* vcycles, int* bottom_iterations);
 
 /* ---- additive Schwarz smoother ------------------------------------------------------------
  * Replaces d4est_solver_schwarz_iterate (src/Solver/d4est_solver_schwarz.c:172-285) with its CG subdomain solver
