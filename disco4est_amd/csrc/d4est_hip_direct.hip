@@ -110,6 +110,12 @@ constexpr int kDirectWPB = 4;
 #ifndef D4EST_HIP_DIRECT_NT_MASK
 #define D4EST_HIP_DIRECT_NT_MASK 7   /* stream mode (VOL & 8) of the one-wavefront kernel: which streams carry the non-temporal hint -- 1 the mortar factors, 2 the volume metric, 4 the A u stores (kernel experiments: tools/build_variant.sh) */
 #endif
+// the volume stage in the collocated-gradient form (stiffness_wave_eo_element_cg; deg_quad = deg, the tables DirectVol::EDq / EDqT)
+#ifndef D4EST_HIP_DIRECT_COLLOCATED
+#define D4EST_HIP_DIRECT_COLLOCATED 1
+#endif
+template <int N, int NQ>
+inline constexpr bool kDirectCollocated = D4EST_HIP_DIRECT_COLLOCATED && kWaveCollocated<N, NQ>;
 #ifndef D4EST_HIP_DIRECT_GEOM_EARLY
 #define D4EST_HIP_DIRECT_GEOM_EARLY 1   /* both faces' geometric factors requested: 0 at their use, 1 before the SIPG loop, 2 with the neighbour lines */
 #endif
@@ -509,7 +515,11 @@ __global__ __launch_bounds__(64 * kDirectWPB, 4) void faces_direct_kernel(const 
     {
       const DirectVol vl = direct_load_vol(direct_kargs());
       const int qs = __builtin_amdgcn_readfirstlane(vl.qs_stride >= 0 ? vl.qs0 + e * vl.qs_stride : vl.qs_list[e]);
-      stiffness_wave_eo_element<N, NQ, (VOL & 3) == 2, false, (VOL & 4) != 0, (VOL & 8) != 0 && (D4EST_HIP_DIRECT_NT_MASK & 2) != 0>(s_U, s_S, vl.metric, qs, e, on_q, a, b, vl.EBf, vl.EGf, vl.EBb,
+      if constexpr (kDirectCollocated<N, NQ>)
+        stiffness_wave_eo_element_cg<N, (VOL & 3) == 2, false, (VOL & 4) != 0, (VOL & 8) != 0 && (D4EST_HIP_DIRECT_NT_MASK & 2) != 0>(s_U, s_S, vl.metric, qs, e, on_q, a, b, vl.EBf, vl.EDq, vl.EBb,
+                                                                              vl.EDqT, vl.affine, vl.wq, vl.cq);
+      else
+        stiffness_wave_eo_element<N, NQ, (VOL & 3) == 2, false, (VOL & 4) != 0, (VOL & 8) != 0 && (D4EST_HIP_DIRECT_NT_MASK & 2) != 0>(s_U, s_S, vl.metric, qs, e, on_q, a, b, vl.EBf, vl.EGf, vl.EBb,
                                                                               vl.EGb, vl.affine, vl.wq, vl.cq);
     }
     if (on_m) {
@@ -710,7 +720,7 @@ bool direct_fused_ok(const d4est_hip_plan* plan) {
     return true;
   }
   const int tw = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_WAVE];
-  if (!(tw < 0 || tw == 11)) return no("tuning key 1");   // the volume kernel whose body rides along must be the selected one
+  if (!(tw < 0 || tw == 11)) return no("tuning key 1");   // (12, the 16-product body for A/B runs: volume and faces in their own kernels)   // the volume kernel whose body rides along must be the selected one
   return true;
 }
 
@@ -763,7 +773,7 @@ static void launch_direct_core(d4est_hip_plan* plan, DirectHost* dh, const Bucke
     }
     const char* sm = (!aff && vol_term != 2 && (vol.stream & 1)) ? ",stream" : "";
     if (dh->mw) std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::operator_mw_kernel<%d,vol%s%s> (stiffness_wave_kernel body + faces)", dh->N, aff ? ",affine" : "", sm);
-    else std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::faces_direct_kernel<%d,%d,vol%s%s> (faces + stiffness_wave_eo body)", dh->N, dh->NQ, aff ? ",affine" : "", sm);
+    else std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::faces_direct_kernel<%d,%d,vol%s%s%s> (faces + stiffness_wave_eo body)", dh->N, dh->NQ, aff ? ",affine" : "", sm, (D4EST_HIP_DIRECT_COLLOCATED && D4EST_HIP_WAVE_COLLOCATED && dh->N == dh->NQ && bk.d_EDq) ? ",cg" : "");
   }
   if (dh->mw) {
     launch_direct_mw(plan, dh, u, ghost_trace, Au, cf, robin_c, robin_r, vmode, vol, n, chunk);

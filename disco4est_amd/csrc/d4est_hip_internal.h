@@ -165,6 +165,10 @@ struct d4est_hip_plan {
 };
 
 namespace d4est_hip {
+// D4EST_HIP_TUNE_STIFFNESS_WAVE values that select the even-odd single-wavefront kernels (and the kernels built on their body): auto, 11,
+// and 12 = the same kernels with the 16-product body where auto / 11 take the collocated-gradient body (deg_quad = deg)
+inline bool tune_wave_eo(int tw) { return tw < 0 || tw == 11 || tw == 12; }
+
 struct TreeMapParams;
 struct CellDesc;
 void launch_analytic_geometry(d4est_hip_plan* plan, const TreeMapParams& P, const CellDesc* d_cells, double root_len);

@@ -577,7 +577,9 @@ __global__ __launch_bounds__(64, 4) void stiffness_wave2_kernel(
 // N and NQ even.  Strides: affine (ns_stride >= 0) or from the lists.
 // AFF = true: affine bucket -- the metric of node (a, b, kq) is rebuilt as (w_a w_b w_kq) * c[0..5] from the element's six
 // constants (affine + 6 * element) instead of being streamed: 16 B/DoF of traffic instead of 64 (SURVEY.md section 8d "affine path")
-template <int N, int NQ, bool AFF = false>
+// CG = true (N = NQ): the collocated-gradient body (stiffness_wave_eo_element_cg, 12 one-dimensional products per thread instead of 16);
+// EGf / EGb then carry the even-odd tables of Dq / Dq^T (Bucket::d_EDq / d_EDqT)
+template <int N, int NQ, bool AFF = false, bool CG = false>
 __global__ __launch_bounds__(64, 4) void stiffness_wave_eo_kernel(
     const double* __restrict__ u, double* __restrict__ Au, const double* __restrict__ metric,
     const int* __restrict__ ns_list, const int* __restrict__ qs_list, int n_bucket, const double* __restrict__ EBf,
@@ -613,7 +615,8 @@ __global__ __launch_bounds__(64, 4) void stiffness_wave_eo_kernel(
     load_element_image<N, PL, PN>(R0, u + ns, te);
   }
   __syncthreads();
-  stiffness_wave_eo_element<N, NQ, AFF, true>(R0, R1, metric, qs, ei, active, a, b, EBf, EGf, EBb, EGb, affine, wq);
+  if constexpr (CG) stiffness_wave_eo_element_cg<N, AFF, true>(R0, R1, metric, qs, ei, active, a, b, EBf, EGf, EBb, EGb, affine, wq);
+  else stiffness_wave_eo_element<N, NQ, AFF, true>(R0, R1, metric, qs, ei, active, a, b, EBf, EGf, EBb, EGb, affine, wq);
   if (active) {
     store_element_image<N, PL, PN>(Au + ns, R0, te);
   }
@@ -639,7 +642,7 @@ struct WaveEoMulti {
   const double* wq[MAXB] = {};
 };
 
-template <int N, bool AFF>
+template <int N, bool AFF, bool CG>
 __device__ __forceinline__ void wave_eo_multi_body(double* smem, int wg, const double* __restrict__ u, double* __restrict__ Au,
                                                    const double* __restrict__ metric, const int* __restrict__ ns_list,
                                                    const int* __restrict__ qs_list, int n_bucket, const double* __restrict__ EBf,
@@ -667,13 +670,14 @@ __device__ __forceinline__ void wave_eo_multi_body(double* smem, int wg, const d
     load_element_image<N, PL, PN>(R0, u + ns, te);
   }
   __syncthreads();
-  stiffness_wave_eo_element<N, N, AFF, true>(R0, R1, metric, qs, ei, active, a, b, EBf, EGf, EBb, EGb, affine, wq);
+  if constexpr (CG) stiffness_wave_eo_element_cg<N, AFF, true>(R0, R1, metric, qs, ei, active, a, b, EBf, EGf, EBb, EGb, affine, wq);
+  else stiffness_wave_eo_element<N, N, AFF, true>(R0, R1, metric, qs, ei, active, a, b, EBf, EGf, EBb, EGb, affine, wq);
   if (active) {
     store_element_image<N, PL, PN>(Au + ns, R0, te);
   }
 }
 
-template <bool AFF>
+template <bool AFF, bool CG>
 __global__ __launch_bounds__(64, 4) void stiffness_wave_eo_multi_kernel(const double* __restrict__ u, double* __restrict__ Au,
                                                                         const double* __restrict__ metric,
                                                                         const int* __restrict__ ns_list_all,
@@ -693,7 +697,7 @@ __global__ __launch_bounds__(64, 4) void stiffness_wave_eo_multi_kernel(const do
   const double* aff = AFF ? affine_all + (size_t)6 * off : nullptr;
 #define D4EST_CASE(N_)                                                                                                            \
   case N_:                                                                                                                        \
-    wave_eo_multi_body<N_, AFF>(smem, wg, u, Au, metric, ns_list_all + off, qs_list_all + off, nb, EBf, EGf, EBb, EGb, aff, wq);   \
+    wave_eo_multi_body<N_, AFF, CG>(smem, wg, u, Au, metric, ns_list_all + off, qs_list_all + off, nb, EBf, EGf, EBb, EGb, aff, wq);   \
     break;
   switch (A.N[bi]) {
     D4EST_CASE(2) D4EST_CASE(3) D4EST_CASE(4) D4EST_CASE(5) D4EST_CASE(6) D4EST_CASE(7) D4EST_CASE(8)
@@ -760,7 +764,7 @@ __global__ __launch_bounds__(THREADS, D4EST_HIP_MW_WAVES) void stiffness_mw_mult
 // 128-thread workgroup, wave-level hand-offs) and the 128-thread multi-wave buckets (N = 9, 10, 11) -- on config 4's degree range p = 3 ... 9
 // every bucket of the plan.  Both kinds are short, latency-structured kernels at these sizes (13 - 18 us each for 585-element buckets): side by
 // side in one launch they cost the longer of the two (general path; D4EST_HIP_STIFFNESS_SPLIT_LAUNCH=1 keeps the two launches).
-template <bool NT>
+template <bool NT, bool CG>
 __global__ __launch_bounds__(128, D4EST_HIP_MW_WAVES) void stiffness_all_multi_kernel(const double* __restrict__ u, double* __restrict__ Au,
                                                                                     const double* __restrict__ metric,
                                                                                     const int* __restrict__ ns_list_all,
@@ -772,9 +776,9 @@ __global__ __launch_bounds__(128, D4EST_HIP_MW_WAVES) void stiffness_all_multi_k
   const int wgb = blk - (bi > 0 ? A.wg_end[bi - 1] : 0);
   const int off = A.elem_offset[bi], nb = A.n_elem[bi];
   const double* EBf = A.EBf[bi];
-  const double* EGf = A.EGf[bi];   // (multi-wave buckets: Dq^T)
+  const double* EGf = A.EGf[bi];   // (multi-wave buckets: Dq^T; one-wavefront buckets with CG: Dq)
   const double* EBb = A.EBb[bi];
-  const double* EGb = A.EGb[bi];   // (multi-wave buckets: Dq)
+  const double* EGb = A.EGb[bi];   // (multi-wave buckets: Dq; one-wavefront buckets with CG: Dq^T)
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #define D4EST_CASE_EO(N_)                                                                                                              \
   case N_: {                                                                                                                           \
@@ -793,7 +797,8 @@ __global__ __launch_bounds__(128, D4EST_HIP_MW_WAVES) void stiffness_all_multi_k
       load_element_image<N_, PL, PN>(R0, u + ns, te);                                                                                  \
     }                                                                                                                                  \
     wave_lds_fence();                                                                                                                  \
-    stiffness_wave_eo_element<N_, N_, false, false>(R0, R1, metric, qs, ei, active, te % N_, te / N_, EBf, EGf, EBb, EGb, nullptr, nullptr); \
+    if constexpr (CG) stiffness_wave_eo_element_cg<N_, false, false>(R0, R1, metric, qs, ei, active, te % N_, te / N_, EBf, EGf, EBb, EGb, nullptr, nullptr); \
+    else stiffness_wave_eo_element<N_, N_, false, false>(R0, R1, metric, qs, ei, active, te % N_, te / N_, EBf, EGf, EBb, EGb, nullptr, nullptr); \
     if (active) store_element_image<N_, PL, PN>(Au + ns, R0, te);                                                                      \
   } break;
 #define D4EST_CASE_MW(N_)                                                                                                              \
@@ -1468,6 +1473,13 @@ static void launch_generic(d4est_hip_plan* plan, const Bucket& bk, int mode, con
                      per_block, coeff);
 }
 
+// deg_quad = deg <= 7: the single-wavefront even-odd kernels run the collocated-gradient body (stiffness_wave_eo_element_cg) unless tuning
+// key D4EST_HIP_TUNE_STIFFNESS_WAVE = 12 asks for the 16-product body (A/B runs, tests/test_volume_cg_gpu.py)
+static bool wave_collocated(const d4est_hip_plan* plan, const Bucket& bk) {
+  return D4EST_HIP_WAVE_COLLOCATED && bk.N == bk.NQ && bk.N * bk.N <= 64 && bk.d_EDq && bk.d_EDqT &&
+         plan->tuning[D4EST_HIP_TUNE_STIFFNESS_WAVE] != 12;
+}
+
 template <int N, int NQ>
 static void launch_stiffness_wave(d4est_hip_plan* plan, const Bucket& bk, bool use_pf, const double* u, double* Au) {
   if constexpr (NQ * NQ <= 64 && NQ >= N) {
@@ -1480,19 +1492,25 @@ static void launch_stiffness_wave(d4est_hip_plan* plan, const Bucket& bk, bool u
     (void)cus_;
     const int stagger = ts < 0 ? 0 : ts;
     const int tw_ = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_WAVE];
-    const bool use_affine = bk.affine && plan->tuning[D4EST_HIP_TUNE_AFFINE] != 0 && bk.d_EBf && (tw_ == 11 || tw_ < 0);
+    const bool use_affine = bk.affine && plan->tuning[D4EST_HIP_TUNE_AFFINE] != 0 && bk.d_EBf && tune_wave_eo(tw_);
+    const bool cg = wave_collocated(plan, bk);   // deg_quad = deg: the collocated-gradient body, its tables in the places of EGf / EGb
+    const double* EGf = cg ? bk.d_EDq : bk.d_EGf;
+    const double* EGb = cg ? bk.d_EDqT : bk.d_EGb;
+    auto go = [&](auto kern, const double* affine, const double* wq) {
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(64), W::LDS_BYTES, plan->stream, u, Au, plan->d_metric, plan->d_ns_list + bk.elem_offset,
+                         plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_EBf, EGf, bk.d_EBb, EGb, bk.ns0, bk.ns_stride, bk.qs0,
+                         bk.qs_stride, affine, wq);
+    };
     if (use_affine) {
-      std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_kernel<%d,%d,affine>", N, NQ);
-      hipLaunchKernelGGL((stiffness_wave_eo_kernel<N, NQ, true>), dim3(grid), dim3(64), W::LDS_BYTES, plan->stream, u, Au, plan->d_metric,
-                           plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_EBf, bk.d_EGf,
-                           bk.d_EBb, bk.d_EGb, bk.ns0, bk.ns_stride, bk.qs0, bk.qs_stride,
-                           plan->d_metric_affine + (size_t)6 * bk.elem_offset, bk.d_w);
-    } else if ((tw_ == 11 || tw_ < 0) && bk.d_EBf) {
-      std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_kernel<%d,%d>", N, NQ);
-      hipLaunchKernelGGL((stiffness_wave_eo_kernel<N, NQ>), dim3(grid), dim3(64), W::LDS_BYTES, plan->stream, u, Au, plan->d_metric,
-                           plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_EBf, bk.d_EGf,
-                           bk.d_EBb, bk.d_EGb, bk.ns0, bk.ns_stride, bk.qs0, bk.qs_stride);
-    } else if (tw_ == 3 || tw_ < 0) {
+      std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_kernel<%d,%d,affine%s>", N, NQ, cg ? ",cg" : "");
+      const double* aff = plan->d_metric_affine + (size_t)6 * bk.elem_offset;
+      if constexpr (kWaveCollocated<N, NQ>) { if (cg) go(stiffness_wave_eo_kernel<N, NQ, true, true>, aff, bk.d_w); }
+      if (!cg) go(stiffness_wave_eo_kernel<N, NQ, true, false>, aff, bk.d_w);
+    } else if (tune_wave_eo(tw_) && bk.d_EBf) {
+      std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_kernel<%d,%d%s>", N, NQ, cg ? ",cg" : "");
+      if constexpr (kWaveCollocated<N, NQ>) { if (cg) go(stiffness_wave_eo_kernel<N, NQ, false, true>, nullptr, nullptr); }
+      if (!cg) go(stiffness_wave_eo_kernel<N, NQ, false, false>, nullptr, nullptr);
+    } else if (tw_ == 3 || tune_wave_eo(tw_)) {
       std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave2_kernel<%d,%d>", N, NQ);
       hipLaunchKernelGGL((stiffness_wave2_kernel<N, NQ>), dim3(grid), dim3(64), W::LDS_BYTES, plan->stream, u, Au, plan->d_metric,
                          plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_B, bk.d_G, bk.d_BT,
@@ -1540,13 +1558,14 @@ static void launch_stiffness_mfma16(d4est_hip_plan* plan, const Bucket& bk, cons
 // into ONE launch per metric form (streamed / affine) when there are at least two of them; returns the buckets it covered.
 static unsigned launch_stiffness_multi(d4est_hip_plan* plan, const double* u, double* Au) {
   const int tw = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_WAVE];
-  if (!(tw < 0 || tw == 11) || plan->tuning[D4EST_HIP_TUNE_STIFFNESS_PREFETCH] > 0) return 0u;
+  if (!tune_wave_eo(tw) || plan->tuning[D4EST_HIP_TUNE_STIFFNESS_PREFETCH] > 0) return 0u;
   unsigned covered = 0u;
   for (int aff = 0; aff < 2; ++aff) {
     WaveEoMulti A;
     size_t lds = 0;
     unsigned mine = 0u;
     int wgs = 0;
+    bool all_cg = true;
     for (size_t i = 0; i < plan->buckets.size() && i < 32; ++i) {
       const Bucket& bk = plan->buckets[i];
       if (bk.n_elem == 0 || bk.N != bk.NQ || bk.N < 2 || bk.N > 8 || !bk.d_EBf || A.n == WaveEoMulti::MAXB) continue;
@@ -1561,17 +1580,19 @@ static unsigned launch_stiffness_multi(d4est_hip_plan* plan, const double* u, do
       wgs += (bk.n_elem + epb - 1) / epb;
       const int j = A.n++;
       A.wg_end[j] = wgs; A.N[j] = bk.N; A.n_elem[j] = bk.n_elem; A.elem_offset[j] = bk.elem_offset;
-      A.EBf[j] = bk.d_EBf; A.EGf[j] = bk.d_EGf; A.EBb[j] = bk.d_EBb; A.EGb[j] = bk.d_EGb; A.wq[j] = bk.d_w;
+      const bool cg = wave_collocated(plan, bk);   // (the same answer for every bucket: they all have deg_quad = deg)
+      all_cg = all_cg && cg;
+      A.EBf[j] = bk.d_EBf; A.EGf[j] = cg ? bk.d_EDq : bk.d_EGf; A.EBb[j] = bk.d_EBb; A.EGb[j] = cg ? bk.d_EDqT : bk.d_EGb; A.wq[j] = bk.d_w;
       mine |= 1u << i;
     }
     if (A.n < 2) continue;
-    std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_multi_kernel<%s> (%d buckets)", aff ? "affine" : "general", A.n);
-    if (aff)
-      hipLaunchKernelGGL((stiffness_wave_eo_multi_kernel<true>), dim3(wgs), dim3(64), lds, plan->stream, u, Au, plan->d_metric, plan->d_ns_list,
-                         plan->d_qs_list, plan->d_metric_affine, A);
-    else
-      hipLaunchKernelGGL((stiffness_wave_eo_multi_kernel<false>), dim3(wgs), dim3(64), lds, plan->stream, u, Au, plan->d_metric, plan->d_ns_list,
-                         plan->d_qs_list, (const double*)nullptr, A);
+    std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_multi_kernel<%s%s> (%d buckets)", aff ? "affine" : "general", all_cg ? ",cg" : "", A.n);
+    auto go = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(wgs), dim3(64), lds, plan->stream, u, Au, plan->d_metric, plan->d_ns_list, plan->d_qs_list,
+                         aff ? plan->d_metric_affine : (const double*)nullptr, A);
+    };
+    if (aff) { if (all_cg) go(stiffness_wave_eo_multi_kernel<true, true>); else go(stiffness_wave_eo_multi_kernel<true, false>); }
+    else { if (all_cg) go(stiffness_wave_eo_multi_kernel<false, true>); else go(stiffness_wave_eo_multi_kernel<false, false>); }
     covered |= mine;
   }
   return covered;
@@ -1617,7 +1638,7 @@ static unsigned launch_stiffness_multi_mw(d4est_hip_plan* plan, const double* u,
 // ... and both kinds in one launch where a plan has p <= 7 buckets AND 128-thread multi-wave buckets (stiffness_all_multi_kernel)
 static unsigned launch_stiffness_all_multi(d4est_hip_plan* plan, const double* u, double* Au) {
   const int tw = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_WAVE];
-  if (!(tw < 0 || tw == 11) || plan->tuning[D4EST_HIP_TUNE_STIFFNESS_PREFETCH] > 0) return 0u;
+  if (!tune_wave_eo(tw) || plan->tuning[D4EST_HIP_TUNE_STIFFNESS_PREFETCH] > 0) return 0u;
   if (plan->tuning[D4EST_HIP_TUNE_STIFFNESS_BIGP] >= 0 && plan->tuning[D4EST_HIP_TUNE_STIFFNESS_BIGP] != 1) return 0u;
   if (plan->tuning[D4EST_HIP_TUNE_STIFFNESS_EO] == 0) return 0u;
   static const bool split = std::getenv("D4EST_HIP_STIFFNESS_SPLIT_LAUNCH") != nullptr;
@@ -1626,6 +1647,7 @@ static unsigned launch_stiffness_all_multi(d4est_hip_plan* plan, const double* u
   size_t lds = 0;
   unsigned mine = 0u;
   int wgs = 0, n_eo = 0, n_mw = 0;
+  bool all_cg = true;   // the one-wavefront buckets in the collocated-gradient form (the same answer for each of them)
   for (size_t i = 0; i < plan->buckets.size() && i < 32; ++i) {
     const Bucket& bk = plan->buckets[i];
     if (bk.n_elem == 0 || bk.N != bk.NQ || A.n == WaveEoMulti::MAXB) continue;
@@ -1640,7 +1662,9 @@ static unsigned launch_stiffness_all_multi(d4est_hip_plan* plan, const double* u
       lds = std::max(lds, 2 * l);
       const int units = (bk.n_elem + epb - 1) / epb;
       wgs += (units + 1) / 2;
-      A.EBf[j] = bk.d_EBf; A.EGf[j] = bk.d_EGf; A.EBb[j] = bk.d_EBb; A.EGb[j] = bk.d_EGb;
+      const bool cg = wave_collocated(plan, bk);
+      all_cg = all_cg && cg;
+      A.EBf[j] = bk.d_EBf; A.EGf[j] = cg ? bk.d_EDq : bk.d_EGf; A.EBb[j] = bk.d_EBb; A.EGb[j] = cg ? bk.d_EDqT : bk.d_EGb;
       ++n_eo;
     } else if (bk.N >= 9 && bk.N <= 11 && bk.d_EDq) {
       lds = std::max(lds, (size_t)2 * bk.N * bk.N * (bk.N | 1) * sizeof(double));
@@ -1655,12 +1679,13 @@ static unsigned launch_stiffness_all_multi(d4est_hip_plan* plan, const double* u
     mine |= 1u << i;
   }
   if (n_eo == 0 || n_mw == 0) return 0u;   // one kind only: the launches above
-  std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_all_multi_kernel (%d + %d buckets)", n_eo, n_mw);
+  std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_all_multi_kernel%s (%d + %d buckets)", all_cg ? "<cg>" : "", n_eo, n_mw);
   auto go = [&](auto kern) {
     set_lds_limit(kern, lds);
     hipLaunchKernelGGL(kern, dim3(wgs), dim3(128), lds, plan->stream, u, Au, plan->d_metric, plan->d_ns_list, plan->d_qs_list, A);
   };
-  if (plan->stream_mode) go(stiffness_all_multi_kernel<true>); else go(stiffness_all_multi_kernel<false>);
+  if (all_cg) { if (plan->stream_mode) go(stiffness_all_multi_kernel<true, true>); else go(stiffness_all_multi_kernel<false, true>); }
+  else { if (plan->stream_mode) go(stiffness_all_multi_kernel<true, false>); else go(stiffness_all_multi_kernel<false, false>); }
   return mine;
 }
 

@@ -144,6 +144,42 @@ __device__ __forceinline__ void contract_pair_eo(const double* __restrict__ opA,
   }
 }
 
+// ONE operator applied to two inputs, one EO row per step: the row is fetched once and feeds both FMA chains (half the scalar loads
+// and half the scalar registers of contract_pair_eo with opA = opB)
+template <int HC, int R>
+__device__ __forceinline__ void contract_dual_eo(const double* __restrict__ op, const double* xfA, const double* xsA, double* yA,
+                                                 const double* xfB, const double* xsB, double* yB) {
+  constexpr int HR = (R + 1) / 2;   // outputs [0, HR) take the first input combination, [HR, R) the second
+  double c0[R], n0[R];
+  unsigned long long base = reinterpret_cast<unsigned long long>(op);
+  asm volatile("" : "+s"(base));
+  {
+    sdouble_ptr r0 = (sdouble_ptr)base;
+#pragma unroll
+    for (int o = 0; o < R; ++o) c0[o] = r0[o];
+  }
+#pragma unroll
+  for (int i = 0; i < HC; ++i) {
+    if (i + 1 < HC) {
+      asm volatile("" : "+s"(base) : "s"(c0[0]));
+      sdouble_ptr r0 = (sdouble_ptr)base;
+#pragma unroll
+      for (int o = 0; o < R; ++o) n0[o] = r0[(i + 1) * R + o];
+    }
+#pragma unroll
+    for (int o = 0; o < R; ++o) {
+      const double xa = (o < HR) ? xfA[i] : xsA[i], xb = (o < HR) ? xfB[i] : xsB[i];
+      yA[o] = (i == 0) ? c0[o] * xa : fma(c0[o], xa, yA[o]);
+      yB[o] = (i == 0) ? c0[o] * xb : fma(c0[o], xb, yB[o]);
+    }
+    if (i + 1 < HC) {
+#pragma unroll
+      for (int o = 0; o < R; ++o) c0[o] = n0[o];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // one operator, two EO rows per step
 template <int HC, int R, bool ACC>
 __device__ __forceinline__ void contract_single_eo(const double* __restrict__ op, const double* xf, const double* xs, double* y) {
@@ -765,6 +801,265 @@ __device__ __forceinline__ void stiffness_wave_eo_element(double* R0, double* R1
 #pragma unroll
       for (int i = 0; i < N; ++i) R0[i + PN * (a + N * b)] = y[i];
     }
+  }
+  SYNC();
+}
+
+// ---------------------------------------------------------------------------
+// The same apply in the COLLOCATED-GRADIENT form, for deg_quad = deg (N = NQ <= 8): the one-wavefront sibling of stiffness_mw_element_cg
+// (d4est_hip_mwave.h, where the identity is written out).  With B square,  (B_t (x) B_s (x) G_r) u = (I (x) I (x) Dq)(B_t (x) B_s (x) B_r) u
+// with Dq = B D B^-1, so the forward half is B_r, B_s, B_t | Dq_t, Dq_s, Dq_r and the backward half its transpose: 12 one-dimensional
+// products per thread instead of the 16 above -- the same operator, re-associated (differences at rounding level).
+// V u is written to LDS ONCE, as [iq + P (jq + N kq)]: the r-lines are read along the padded leading dimension, the s-lines with the
+// lanes along iq (consecutive addresses); both derivative lines go back into the private slots [kq + P (iq + N jq)] of the thread that
+// owns the quadrature nodes (iq, jq, .).  LDS line traffic per thread: 7 reads + 5 writes forward (16-product body: 6 + 5), 6 + 7
+// backward (5 + 6).  V u passes through registers at the quadrature stage: the zeroth-order term (MASS) costs no contraction.
+// EDq / EDqT: even-odd tables of Dq / Dq^T (centro-antisymmetric: the layouts of EGf / EGb).  R0 / R1, entry / exit, WG_SYNC, NT: as above.
+// ---------------------------------------------------------------------------
+#ifndef D4EST_HIP_WAVE_COLLOCATED
+#define D4EST_HIP_WAVE_COLLOCATED 1   /* deg_quad = deg <= 7: the collocated-gradient form of the one-wavefront body (0: never) */
+#endif
+template <int N, int NQ>
+inline constexpr bool kWaveCollocated = D4EST_HIP_WAVE_COLLOCATED && N == NQ && (N * N <= 64);
+
+template <int N, bool AFF, bool WG_SYNC, bool MASS = false, bool NT = false>
+__device__ __forceinline__ void stiffness_wave_eo_element_cg(double* R0, double* R1, const double* __restrict__ metric, int qs, int ei,
+                                                             bool active, int a, int b, const double* __restrict__ EBf,
+                                                             const double* __restrict__ EDq, const double* __restrict__ EBb,
+                                                             const double* __restrict__ EDqT, const double* __restrict__ affine,
+                                                             const double* __restrict__ wq, const double* __restrict__ cq = nullptr) {
+  using C = WaveCfg<N, N>;
+  constexpr int P = C::PN;
+  constexpr int N3 = N * N * N;
+  constexpr int H = (N + 1) / 2;   // rows of the even-odd tables = entries of xe / xo
+  auto SYNC = [] {
+    if constexpr (WG_SYNC) __syncthreads();
+    else wave_lds_fence();
+  };
+  const int line = P * (a + N * b);   // the thread's own line [. + P (a + N b)] in either field
+
+  // ---- F1 (r): thread (j = a, k = b):  R1[j + P (iq + N k)] <- B u
+  if (active) {
+    double x[N], xe[H], xo[H], ab[N], y[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[i] = lds_ld(&R0[i + line]);
+    eo_pre<N>(x, xe, xo);
+    contract_single_eo<H, N, false>(EBf, xe, xo, ab);
+    eo_post<N>(ab, y);
+#pragma unroll
+    for (int iq = 0; iq < N; ++iq) R1[a + P * (iq + N * b)] = y[iq];
+  }
+  SYNC();
+  // ---- F2 (s): thread (iq = a, k = b):  R0[k + P (iq + N jq)] <- B (.)
+  if (active) {
+    double x[N], xe[H], xo[H], ab[N], y[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) x[j] = lds_ld(&R1[j + line]);
+    eo_pre<N>(x, xe, xo);
+    contract_single_eo<H, N, false>(EBf, xe, xo, ab);
+    eo_post<N>(ab, y);
+#pragma unroll
+    for (int jq = 0; jq < N; ++jq) R0[b + P * (a + N * jq)] = y[jq];
+  }
+  SYNC();
+  // ---- F3 (t): thread (iq = a, jq = b): w = V u along kq (registers) -> R1[iq + P (jq + N kq)];  gt = Dq w
+  double gt[N];
+  double vm[MASS ? N : 1];
+  if (active) {
+    double x[N], xe[H], xo[H], ab[N], w[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) x[k] = lds_ld(&R0[k + line]);
+    eo_pre<N>(x, xe, xo);
+    contract_single_eo<H, N, false>(EBf, xe, xo, ab);
+    eo_post<N>(ab, w);
+#pragma unroll
+    for (int kq = 0; kq < N; ++kq) R1[a + P * (b + N * kq)] = w[kq];   // (R1's readers finished before the barrier above)
+    if constexpr (MASS) {
+#pragma unroll
+      for (int kq = 0; kq < N; ++kq) vm[kq] = w[kq];
+    }
+    eo_pre<N>(w, xe, xo);
+    contract_single_eo<H, N, false>(EDq, xo, xe, ab);
+    eo_post<N>(ab, gt);
+  }
+  SYNC();
+  // ---- F4: thread (iq = a, kq = b): gs line = Dq (s-line);  thread (jq = a, kq = b): gr line = Dq (r-line); one scalar row of Dq feeds
+  // both chains.  General path of the stand-alone kernel: the metric planes are requested MD planes ahead of their use, the first ME of
+  // them before this last forward contraction (see stiffness_wave_eo_element)
+  constexpr bool kPipe = !AFF && WG_SYNC && (D4EST_HIP_WAVE_EO_DEPTH > 0);
+  constexpr int MD = (D4EST_HIP_WAVE_EO_DEPTH < N) ? D4EST_HIP_WAVE_EO_DEPTH : N;
+  constexpr int ME = (D4EST_HIP_WAVE_EO_EARLY < MD) ? D4EST_HIP_WAVE_EO_EARLY : MD;
+  double mw[kPipe ? N : 1][6];
+  {
+    double ys[N], yr[N];
+    if (active) {
+      double z[N], x[N], ze[H], zo[H], xe[H], xo[H];
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        z[j] = lds_ld(&R1[a + P * (j + N * b)]);
+        x[j] = lds_ld(&R1[j + line]);
+      }
+      if constexpr (kPipe) {
+        const double* __restrict__ m = metric + (size_t)6 * qs + (a + N * b);
+#pragma unroll
+        for (int kq = 0; kq < ME; ++kq)
+#pragma unroll
+          for (int c = 0; c < 6; ++c) mw[kq][c] = ld_sel<NT>(&m[c * N3 + N * N * kq]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      eo_pre<N>(z, ze, zo);
+      eo_pre<N>(x, xe, xo);
+      contract_dual_eo<H, N>(EDq, zo, ze, ys, xo, xe, yr);
+      double y[N];
+      eo_post<N>(ys, y);
+#pragma unroll
+      for (int j = 0; j < N; ++j) R0[b + P * (a + N * j)] = y[j];   // gs(iq = a, jq = j, kq = b) -> [kq + P (iq + N jq)]  (R0 is free since F3)
+    }
+    SYNC();   // every thread has read its lines of R1
+    if (active) {
+      double y[N];
+      eo_post<N>(yr, y);
+#pragma unroll
+      for (int j = 0; j < N; ++j) R1[b + P * (j + N * a)] = y[j];   // gr(iq = j, jq = a, kq = b) -> [kq + P (iq + N jq)]
+    }
+  }
+  SYNC();
+
+  // ---- quadrature-point stage: thread (iq = a, jq = b); gs in R0[kq + line], gr in R1[kq + line] (the thread's private slots: the fluxes
+  // go back in place, no barrier), gt in registers
+  if (active) {
+    if constexpr (MASS) {
+      const double* __restrict__ cp = cq + qs + (a + N * b);   // w J c, pre-combined
+      double cv[N];
+#pragma unroll
+      for (int kq = 0; kq < N; ++kq) cv[kq] = cp[N * N * kq];
+#pragma unroll
+      for (int kq = 0; kq < N; ++kq) vm[kq] *= cv[kq];
+    }
+    if constexpr (AFF) {
+      const double* __restrict__ c = affine + (size_t)6 * ei;
+      const double c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3], c4 = c[4], c5 = c[5];
+      const double wab = wq[b] * wq[a];
+#pragma unroll
+      for (int kq = 0; kq < N; ++kq) {
+        const double w3 = wq[kq] * wab;
+        const double r = w3 * lds_ld(&R1[kq + line]), s = w3 * lds_ld(&R0[kq + line]), t = w3 * gt[kq];
+        R1[kq + line] = c0 * r + c1 * s + c2 * t;
+        R0[kq + line] = c1 * r + c3 * s + c4 * t;
+        gt[kq] = c2 * r + c4 * s + c5 * t;
+      }
+    } else if constexpr (kPipe) {
+      const double* __restrict__ m = metric + (size_t)6 * qs + (a + N * b);
+#pragma unroll
+      for (int kq = ME; kq < MD; ++kq)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) mw[kq][c] = ld_sel<NT>(&m[c * N3 + N * N * kq]);
+      double rn = lds_ld(&R1[line]), sn = lds_ld(&R0[line]);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int kq = 0; kq < N; ++kq) {
+        if (kq + MD < N) {
+#pragma unroll
+          for (int c = 0; c < 6; ++c) mw[kq + MD][c] = ld_sel<NT>(&m[c * N3 + N * N * (kq + MD)]);
+        }
+        const double r = rn, s = sn, t = gt[kq];
+        if (kq + 1 < N) {
+          rn = lds_ld(&R1[kq + 1 + line]);
+          sn = lds_ld(&R0[kq + 1 + line]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        R1[kq + line] = mw[kq][0] * r + mw[kq][1] * s + mw[kq][2] * t;
+        R0[kq + line] = mw[kq][1] * r + mw[kq][3] * s + mw[kq][4] * t;
+        gt[kq] = mw[kq][2] * r + mw[kq][4] * s + mw[kq][5] * t;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+      const double* __restrict__ m = metric + (size_t)6 * qs + (a + N * b);
+#pragma unroll
+      for (int kq = 0; kq < N; ++kq) {
+        const int q = N * N * kq;
+        const double m0 = m[q], m1 = m[N3 + q], m2 = m[2 * N3 + q], m3 = m[3 * N3 + q], m4 = m[4 * N3 + q], m5 = m[5 * N3 + q];
+        const double r = lds_ld(&R1[kq + line]), s = lds_ld(&R0[kq + line]), t = gt[kq];
+        R1[kq + line] = m0 * r + m1 * s + m2 * t;
+        R0[kq + line] = m1 * r + m3 * s + m4 * t;
+        gt[kq] = m2 * r + m4 * s + m5 * t;
+      }
+    }
+  }
+
+  // ---- B1: the transposed derivatives.  t: registers (+ the weighted V u of the zeroth-order term).  s / r: the threads (iq, kq) /
+  // (jq, kq) take their lines out of the flux fields and put the result back IN PLACE
+  double ft[N];
+  if (active) {
+    double te_[H], to[H], ab[N];
+    eo_pre<N>(gt, te_, to);
+    contract_single_eo<H, N, false>(EDqT, to, te_, ab);
+    eo_post<N>(ab, ft);
+    if constexpr (MASS) {
+#pragma unroll
+      for (int kq = 0; kq < N; ++kq) ft[kq] += vm[kq];
+    }
+  }
+  SYNC();
+  if (active) {
+    double z[N], x[N], ze[H], zo[H], xe[H], xo[H], ys[N], yr[N], y[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      z[j] = lds_ld(&R0[b + P * (a + N * j)]);   // flux_s(iq = a, jq = j, kq = b)
+      x[j] = lds_ld(&R1[b + P * (j + N * a)]);   // flux_r(iq = j, jq = a, kq = b)
+    }
+    eo_pre<N>(z, ze, zo);
+    eo_pre<N>(x, xe, xo);
+    contract_dual_eo<H, N>(EDqT, zo, ze, ys, xo, xe, yr);
+    eo_post<N>(ys, y);
+#pragma unroll
+    for (int j = 0; j < N; ++j) R0[b + P * (a + N * j)] = y[j];
+    eo_post<N>(yr, y);
+#pragma unroll
+    for (int j = 0; j < N; ++j) R1[b + P * (j + N * a)] = y[j];
+  }
+  SYNC();
+  // ---- B2 (t^T): thread (iq = a, jq = b): F = ft + (s part) + (r part) along kq;  R0[jq + P (iq + N k)] <- B^T F
+  {
+    double c[N];
+    if (active) {
+      double F[N], fe[H], fo[H];
+#pragma unroll
+      for (int kq = 0; kq < N; ++kq) F[kq] = ft[kq] + (lds_ld(&R0[kq + line]) + lds_ld(&R1[kq + line]));
+      eo_pre<N>(F, fe, fo);
+      contract_single_eo<H, N, false>(EBb, fe, fo, c);
+    }
+    SYNC();   // every thread has read its private lines
+    if (active) {
+      double y[N];
+      eo_post<N>(c, y);
+#pragma unroll
+      for (int k = 0; k < N; ++k) R0[b + P * (a + N * k)] = y[k];
+    }
+  }
+  SYNC();
+  // ---- B3 (s^T): thread (iq = a, k = b):  R1[iq + P (j + N k)] <- B^T (.)
+  if (active) {
+    double x[N], xe[H], xo[H], ab[N], y[N];
+#pragma unroll
+    for (int jq = 0; jq < N; ++jq) x[jq] = lds_ld(&R0[jq + line]);
+    eo_pre<N>(x, xe, xo);
+    contract_single_eo<H, N, false>(EBb, xe, xo, ab);
+    eo_post<N>(ab, y);
+#pragma unroll
+    for (int j = 0; j < N; ++j) R1[a + P * (j + N * b)] = y[j];
+  }
+  SYNC();
+  // ---- B4 (r^T): thread (j = a, k = b):  R0[i + P (j + N k)] <- B^T (.)
+  if (active) {
+    double x[N], xe[H], xo[H], ab[N], y[N];
+#pragma unroll
+    for (int iq = 0; iq < N; ++iq) x[iq] = lds_ld(&R1[iq + line]);
+    eo_pre<N>(x, xe, xo);
+    contract_single_eo<H, N, false>(EBb, xe, xo, ab);
+    eo_post<N>(ab, y);
+#pragma unroll
+    for (int i = 0; i < N; ++i) R0[i + line] = y[i];
   }
   SYNC();
 }

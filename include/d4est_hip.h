@@ -77,7 +77,7 @@ void d4est_hip_plan_set_stream(d4est_hip_plan_t* plan, void* hip_stream);
 /* Performance knobs (never change results beyond fp64 re-association).  Value -1 (default) = auto. */
 enum d4est_hip_tuning_key {
   D4EST_HIP_TUNE_STIFFNESS_PREFETCH = 0, /* 1: request the metric at kernel entry (deg_quad <= 7), 0: at the point of use */
-  D4EST_HIP_TUNE_STIFFNESS_WAVE = 1,     /* where (deg_quad+1)^2 <= 64: 0 multi-buffer kernel, 1 single-wavefront kernel, 2 two-wavefront kernel with metric prefetch, 3 single-wavefront kernel with pipelined operator loads (auto default for odd N), 11 even-odd single-wavefront kernel (auto default for even N, NQ); every value computes the same stiffness apply (tests/test_volume_gpu.py) */
+  D4EST_HIP_TUNE_STIFFNESS_WAVE = 1,     /* where (deg_quad+1)^2 <= 64: 0 multi-buffer kernel, 1 single-wavefront kernel, 2 two-wavefront kernel with metric prefetch, 3 single-wavefront kernel with pipelined operator loads (auto default for odd N), 11 even-odd single-wavefront kernel (auto default for even N, NQ; with deg_quad = deg in the collocated-gradient form, 12 one-dimensional products per thread), 12 the same kernel with the 16-product body at deg_quad = deg too (A/B runs; the whole operator then runs as volume kernel + face kernel); every value computes the same stiffness apply (tests/test_volume_gpu.py, tests/test_volume_cg_gpu.py) */
   D4EST_HIP_TUNE_STIFFNESS_STAGGER = 2,  /* single-wave kernel: delay (units of 1024 cycles) of every other resident workgroup row */
   D4EST_HIP_TUNE_FLUX_FAST = 3,          /* 0: always the generic flux kernel; else the wave-per-face kernel where all degrees <= 7 */
   D4EST_HIP_TUNE_STIFFNESS_BIGP = 4,     /* p >= 8: 0 three-field kernel, 1 two-field multi-wave kernel (default except p = 15), 2 at p = 12 ... 15 (deg_quad = deg): the FP64 matrix-core kernel (v_mfma_f64_16x16x4; default at p = 15, where no padding is needed) */
