@@ -87,6 +87,13 @@ SIGNATURES = {
     "d4est_hip_plan_set_estimator": (None, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double]),
     "d4est_hip_estimator_bi": (None, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d4est_hip_plan_estimator_info": (ctypes.c_int, [_vp, _vp, _vp]),
+    "d4est_hip_plan_set_energy_norm": (None, [_vp, ctypes.c_int, ctypes.c_double]),
+    "d4est_hip_plan_energy_norm_info": (ctypes.c_int, [_vp, _vp, _vp]),
+    "d4est_hip_norms_error": (None, [_vp, _vp, _vp, _vp]),
+    "d4est_hip_norm_l2_sqr": (None, [_vp, _vp, _vp, _vp, _vp]),
+    "d4est_hip_norm_linfty": (None, [_vp, _vp, _vp, _vp]),
+    "d4est_hip_ip_energy_norm_sqr": (None, [_vp, _vp, _vp, _vp, _vp]),
+    "d4est_hip_masked_sum": (None, [_vp, _vp, _vp, _vp]),
     "d4est_hip_plan_bndry_nodes": (ctypes.c_int, [_vp]),
     "d4est_hip_plan_boundary_gather": (None, [_vp, _vp, _vp]),
     "d4est_hip_plan_set_dirichlet_values": (None, [_vp, _vp, ctypes.c_int]),
@@ -417,6 +424,71 @@ class Plan:
         if not isinstance(diam, torch.Tensor) or (g is not None and not isinstance(g, torch.Tensor)):
             torch.cuda.current_stream(dev).synchronize() if self.torch_stream is None else self.torch_stream.synchronize()
             self.lib.d4est_hip_device_synchronize()   # (the uploaded copies must outlive the launches)
+
+    # ---- error norms (d4est_norms_save's columns; csrc/d4est_hip_norms.hip) ----
+    def set_energy_norm(self, penalty_fcn, penalty_prefactor):
+        """request the IP energy norm (d4est_ip_energy_norm_compute) with u_penalty_fcn = this SIPG penalty id (0..3, as set_faces') and
+        this prefactor; before set_faces (whose mortar factors also form the norm's face factor)"""
+        self.lib.d4est_hip_plan_set_energy_norm(self.handle, int(penalty_fcn), float(penalty_prefactor))
+
+    def _skip_mask(self, skip, dev):
+        """None, or the int32 CUDA tensor of a skip mask given as numpy / torch (1 = skip the element)"""
+        import torch
+        if skip is None:
+            return None
+        if isinstance(skip, torch.Tensor):
+            d = skip.to(device=dev, dtype=torch.int32).contiguous()
+        else:
+            d = torch.from_numpy(np.ascontiguousarray(skip, dtype=np.int32)).to(dev)
+        assert d.numel() == self.n_elements
+        return d
+
+    @staticmethod
+    def _iptr(t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+    def _sync_after_upload(self, uploaded, dev):
+        import torch
+        if uploaded:   # (the uploaded copy must outlive the launches)
+            torch.cuda.current_stream(dev).synchronize() if self.torch_stream is None else self.torch_stream.synchronize()
+            self.lib.d4est_hip_device_synchronize()
+
+    def norms_error(self, u, u_compare, err):
+        """err = |u - u_compare| at the Lobatto nodes (u_compare None: |u|); CUDA tensors of local_nodes doubles"""
+        assert u.numel() == self.local_nodes and err.numel() == self.local_nodes
+        assert u_compare is None or u_compare.numel() == self.local_nodes
+        self.lib.d4est_hip_norms_error(self.handle, _ptr(u), _ptr(u_compare) if u_compare is not None else None, _ptr(err))
+
+    def norm_l2_sqr(self, v, out, skip=None, l2_array=None):
+        """out[0] = sum over the non-skipped elements of v_e^T M_e v_e; l2_array[n_elements] (optional) gets every element's value.
+        v, out, l2_array: CUDA tensors; skip: numpy or torch mask, 1 = skip"""
+        assert v.numel() == self.local_nodes and out.numel() >= 1 and (l2_array is None or l2_array.numel() == self.n_elements)
+        d_skip = self._skip_mask(skip, v.device)
+        self.lib.d4est_hip_norm_l2_sqr(self.handle, _ptr(v), self._iptr(d_skip), _ptr(l2_array) if l2_array is not None else None, _ptr(out))
+        self._sync_after_upload(d_skip is not None and d_skip is not skip, v.device)
+
+    def norm_linfty(self, v, out, skip=None):
+        """out[0] = max(0, max_i v_i) over the nodes of the non-skipped elements (d4est_norms_fcn_Linfty)"""
+        assert v.numel() == self.local_nodes and out.numel() >= 1
+        d_skip = self._skip_mask(skip, v.device)
+        self.lib.d4est_hip_norm_linfty(self.handle, _ptr(v), self._iptr(d_skip), _ptr(out))
+        self._sync_after_upload(d_skip is not None and d_skip is not skip, v.device)
+
+    def ip_energy_norm_sqr(self, v, sums, elem_terms=None, ghost_trace=None):
+        """sums[4] = volume, boundary, interface terms and their total of d4est_ip_energy_norm_compute (squared, this rank's part);
+        elem_terms[3 n_elements] (optional), term-major.  CUDA tensors; needs set_energy_norm before set_faces"""
+        assert v.numel() == self.local_nodes and sums.numel() == 4 and (elem_terms is None or elem_terms.numel() == 3 * self.n_elements)
+        if ghost_trace is not None:
+            assert ghost_trace.numel() == self.ghost_trace_size
+        self.lib.d4est_hip_ip_energy_norm_sqr(self.handle, _ptr(v), _ptr(ghost_trace) if ghost_trace is not None else None,
+                                              _ptr(elem_terms) if elem_terms is not None else None, _ptr(sums))
+
+    def masked_sum(self, elem, out, skip=None):
+        """out[0] = fixed-order sum of elem[n_elements] over the non-skipped elements (with eta2: d4est_norms_fcn_energy_estimator)"""
+        assert elem.numel() == self.n_elements and out.numel() >= 1
+        d_skip = self._skip_mask(skip, elem.device)
+        self.lib.d4est_hip_masked_sum(self.handle, _ptr(elem), self._iptr(d_skip), _ptr(out))
+        self._sync_after_upload(d_skip is not None and d_skip is not skip, elem.device)
 
     def set_dirichlet_values(self, g):
         if g is None:

@@ -586,6 +586,50 @@ int d4est_hip_plan_estimator_info(const d4est_hip_plan_t* plan, int* ids, double
   return 1;
 }
 
+void d4est_hip_plan_set_energy_norm(d4est_hip_plan_t* plan, int penalty_fcn, double penalty_prefactor) {
+  check_plan(plan, "plan_set_energy_norm");
+  if (penalty_fcn < 0 || penalty_fcn > 3) D4EST_HIP_ABORT("plan_set_energy_norm: unknown penalty function %d", penalty_fcn);
+  if (plan->has_face_geometry) D4EST_HIP_ABORT("plan_set_energy_norm: call before plan_set_mortar_geometry (the norm's face factor is formed there)");
+  plan->norm_requested = true;
+  plan->norm_fcn = penalty_fcn;
+  plan->norm_prefactor = penalty_prefactor;
+}
+
+int d4est_hip_plan_energy_norm_info(const d4est_hip_plan_t* plan, int* penalty_fcn, double* penalty_prefactor) {
+  check_plan(plan, "plan_energy_norm_info");
+  if (!plan->norm_requested) return 0;
+  if (penalty_fcn) *penalty_fcn = plan->norm_fcn;
+  if (penalty_prefactor) *penalty_prefactor = plan->norm_prefactor;
+  return 1;
+}
+
+void d4est_hip_norms_error(d4est_hip_plan_t* plan, const double* u_dev, const double* u_compare_dev, double* err_dev) {
+  check_plan(plan, "norms_error");
+  d4est_hip::norms_error(plan, u_dev, u_compare_dev, err_dev);
+}
+
+void d4est_hip_norm_l2_sqr(d4est_hip_plan_t* plan, const double* v_dev, const int* skip_dev, double* l2_array_dev, double* sum_dev) {
+  check_plan(plan, "norm_l2_sqr");
+  d4est_hip::norms_l2_sqr(plan, v_dev, skip_dev, l2_array_dev, sum_dev);
+}
+
+void d4est_hip_norm_linfty(d4est_hip_plan_t* plan, const double* v_dev, const int* skip_dev, double* max_dev) {
+  check_plan(plan, "norm_linfty");
+  d4est_hip::norms_linfty(plan, v_dev, skip_dev, max_dev);
+}
+
+void d4est_hip_ip_energy_norm_sqr(d4est_hip_plan_t* plan, const double* v_dev, const double* ghost_trace_dev, double* elem_terms_dev,
+                                  double* sums_dev) {
+  check_plan(plan, "ip_energy_norm_sqr");
+  if (!plan->has_faces) D4EST_HIP_ABORT("ip_energy_norm_sqr: the plan has no faces (plan_set_faces)");
+  d4est_hip::norms_ip_energy_sqr(plan, v_dev, ghost_trace_dev, elem_terms_dev, sums_dev);
+}
+
+void d4est_hip_masked_sum(d4est_hip_plan_t* plan, const double* elem_dev, const int* skip_dev, double* sum_dev) {
+  check_plan(plan, "masked_sum");
+  d4est_hip::norms_masked_sum(plan, elem_dev, skip_dev, sum_dev);
+}
+
 int d4est_hip_plan_bndry_nodes(const d4est_hip_plan_t* plan) { check_plan(plan, "plan_bndry_nodes"); return plan->total_bndry_nodes; }
 
 void d4est_hip_plan_boundary_gather(d4est_hip_plan_t* plan, const double* vol_dev, double* bndry_dev) {

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/d4est_hip_compat.h"
+#include "d4est_hip_compat_penalty.h"
 
 #define COMPAT_ABORT(...)                                       \
   do {                                                          \
@@ -748,6 +749,145 @@ double* d4est_estimator_bi_compute(p4est_t* p4est, d4est_elliptic_data_t* d, d4e
   if (estimator_vtk) d4est_hip_memcpy_d2h(estimator_vtk, d_out + ne, sizeof(double) * 4 * (size_t)ne);
   d4est_hip_free(d_u); d4est_hip_free(d_r); d4est_hip_free(d_x); d4est_hip_free(d_g); d4est_hip_free(d_diam); d4est_hip_free(d_out);
   return est;
+}
+
+// ---- the columns of d4est_norms_save (src/IO/d4est_norms.c) on the bound plan: the vector goes up, the norm runs on the device
+// (csrc/d4est_hip_norms.hip), the scalars come back.  Local values: the reference's sc_reduce stays with the caller.
+typedef int (*skip_element_fcn_t)(d4est_element_data_t*);
+static void need_no_skip(skip_element_fcn_t skip, const char* who) {
+  if (skip)
+    COMPAT_ABORT("%s: skip_element_fcn != NULL; d4est_element_data_t is opaque to this library, so the function cannot be evaluated: evaluate "
+                 "it per element into the skip mask of d4est_hip_norm_l2_sqr / d4est_hip_norm_linfty / d4est_hip_masked_sum", who);
+}
+// one device buffer [v: ln | out: n_out] with v uploaded
+static double* norms_upload(d4est_hip_plan_t* plan, const double* v, int ln, size_t n_out, const char* who) {
+  if (!v) COMPAT_ABORT("%s: NULL vector", who);
+  if (ln != d4est_hip_plan_local_nodes(plan)) COMPAT_ABORT("%s: %d local nodes, the bound plan has %d", who, ln, d4est_hip_plan_local_nodes(plan));
+  double* d = (double*)d4est_hip_malloc(sizeof(double) * ((size_t)std::max(ln, 1) + n_out));
+  d4est_hip_memcpy_h2d(d, v, sizeof(double) * (size_t)ln);
+  return d;
+}
+
+double d4est_mesh_compute_l2_norm_sqr(p4est_t* p4est, d4est_operators_t*, d4est_geometry_t*, d4est_quadrature_t*, d4est_mesh_data_t*,
+                                      double* nodal_vec, int local_nodes, skip_element_fcn_t skip_element_fcn, double* l2_array) {
+  const char* who = "d4est_mesh_compute_l2_norm_sqr";   // src/Mesh/d4est_mesh.c:2299-2374
+  need_no_skip(skip_element_fcn, who);   // (before anything touches the device)
+  d4est_hip_plan_t* plan = bound(p4est, who);
+  const int ne = d4est_hip_plan_n_elements(plan);
+  double* d_v = norms_upload(plan, nodal_vec, local_nodes, (size_t)ne + 1, who);
+  double* d_sum = d_v + std::max(local_nodes, 1);
+  d4est_hip_norm_l2_sqr(plan, d_v, nullptr, l2_array ? d_sum + 1 : nullptr, d_sum);
+  d4est_hip_plan_synchronize(plan);
+  double sum = 0.0;
+  d4est_hip_memcpy_d2h(&sum, d_sum, sizeof(double));
+  if (l2_array) d4est_hip_memcpy_d2h(l2_array, d_sum + 1, sizeof(double) * (size_t)ne);
+  d4est_hip_free(d_v);
+  return sum;
+}
+
+double d4est_norms_fcn_L2(p4est_t* p4est, double* field_value_errors, int num_nodes_local, void* norm_fcn_ctx, skip_element_fcn_t skip_element_fcn) {
+  // d4est_norms.c:16-56: the context's p4est and mesh objects are handed on; sqrt of the LOCAL sum
+  need_no_skip(skip_element_fcn, "d4est_norms_fcn_L2");
+  d4est_norms_fcn_L2_ctx_t* ctx = (d4est_norms_fcn_L2_ctx_t*)norm_fcn_ctx;
+  if (!ctx) COMPAT_ABORT("d4est_norms_fcn_L2: NULL context");
+  (void)p4est;
+  return std::sqrt(d4est_mesh_compute_l2_norm_sqr(ctx->p4est, ctx->d4est_ops, ctx->d4est_geom, ctx->d4est_quad, ctx->d4est_factors,
+                                                  field_value_errors, num_nodes_local, skip_element_fcn, nullptr));
+}
+
+double d4est_norms_fcn_Linfty(p4est_t* p4est, double* field_value_errors, int num_nodes_local, void*, skip_element_fcn_t skip_element_fcn) {
+  const char* who = "d4est_norms_fcn_Linfty";   // d4est_norms.c:64-117
+  need_no_skip(skip_element_fcn, who);   // (before anything touches the device)
+  d4est_hip_plan_t* plan = bound(p4est, who);
+  double* d_v = norms_upload(plan, field_value_errors, num_nodes_local, 1, who);
+  double* d_max = d_v + std::max(num_nodes_local, 1);
+  d4est_hip_norm_linfty(plan, d_v, nullptr, d_max);
+  d4est_hip_plan_synchronize(plan);
+  double mx = 0.0;
+  d4est_hip_memcpy_d2h(&mx, d_max, sizeof(double));
+  d4est_hip_free(d_v);
+  return mx;
+}
+
+double d4est_ip_energy_norm_compute(p4est_t* p4est, double* u, d4est_ip_energy_norm_data_t* energy_norm_data, d4est_ghost_t*, d4est_ghost_data_t*,
+                                    d4est_operators_t*, d4est_geometry_t*, d4est_quadrature_t*, d4est_mesh_data_t*, int which_field) {
+  const char* who = "d4est_ip_energy_norm_compute";   // src/dGMath/d4est_ip_energy_norm.c:286-448
+  d4est_hip_plan_t* plan = bound(p4est, who);
+  if (!energy_norm_data) COMPAT_ABORT("%s: NULL energy_norm_data", who);
+  // :357 reads u[ed->nodal_stride] in the volume term, without the field offset that the face data carry (:405): only field 0 is consistent
+  if (which_field != 0) COMPAT_ABORT("%s: which_field %d; the reference's volume term reads field 0 whatever which_field says (:357)", who, which_field);
+  int plan_id = -1;
+  double plan_c = 0.0;
+  if (!d4est_hip_plan_energy_norm_info(plan, &plan_id, &plan_c)) COMPAT_ABORT("%s: the bound plan has no energy-norm set-up (d4est_hip_plan_set_energy_norm)", who);
+  const int id = d4est_hip_compat_identify_sipg(energy_norm_data->u_penalty_fcn);
+  if (id < 0) COMPAT_ABORT("%s: u_penalty_fcn is NULL or matches none of the four penalty functions of d4est_laplacian_flux_sipg.c:945-1005", who);
+  if (id != plan_id) COMPAT_ABORT("%s: u_penalty_fcn is id %d, the bound plan has id %d", who, id, plan_id);
+  if (energy_norm_data->penalty_prefactor != plan_c) COMPAT_ABORT("%s: penalty_prefactor %g, the bound plan has %g", who, energy_norm_data->penalty_prefactor, plan_c);
+  const int ln = d4est_hip_plan_local_nodes(plan);
+  double* d_v = norms_upload(plan, u, ln, 4, who);
+  double* d_sums = d_v + std::max(ln, 1);
+  d4est_hip_ip_energy_norm_sqr(plan, d_v, nullptr, nullptr, d_sums);   // ghost sides: through the plan_set_comm hooks
+  d4est_hip_plan_synchronize(plan);
+  double sums[4];
+  d4est_hip_memcpy_d2h(sums, d_sums, sizeof sums);
+  d4est_hip_free(d_v);
+  energy_norm_data->ip_energy_norm_sqr_volume_term = sums[0];
+  energy_norm_data->ip_energy_norm_sqr_boundary_term = sums[1];
+  energy_norm_data->ip_energy_norm_sqr_interface_term = sums[2];
+  return sums[3];   // (volume + boundary) + interface, :440-443
+}
+
+double d4est_norms_fcn_energy(p4est_t*, double* field_value_errors, int, void* norm_fcn_ctx, skip_element_fcn_t skip_element_fcn) {
+  if (skip_element_fcn) COMPAT_ABORT("Do not use d4est_norms_fcn_energy when skip_element_fcn != NULL, (not supported)");   // d4est_norms.c:211-213
+  d4est_norms_fcn_energy_ctx_t* ctx = (d4est_norms_fcn_energy_ctx_t*)norm_fcn_ctx;
+  if (!ctx) COMPAT_ABORT("d4est_norms_fcn_energy: NULL context");
+  return std::sqrt(d4est_ip_energy_norm_compute(ctx->p4est, field_value_errors, ctx->energy_norm_data, ctx->ghost, ctx->ghost_data, ctx->d4est_ops,
+                                                ctx->d4est_geom, ctx->d4est_quad, ctx->d4est_factors, ctx->which_field));
+}
+
+double d4est_norms_fcn_energy_estimator(p4est_t*, double*, int, void* norm_fcn_ctx, skip_element_fcn_t skip_element_fcn) {
+  need_no_skip(skip_element_fcn, "d4est_norms_fcn_energy_estimator");
+  d4est_norms_fcn_energy_ctx_t* ctx = (d4est_norms_fcn_energy_ctx_t*)norm_fcn_ctx;
+  if (!ctx) COMPAT_ABORT("d4est_norms_fcn_energy_estimator: NULL context");
+  return std::sqrt(ctx->energy_estimator_sq_local);   // d4est_norms.c:263-265: without a skip function, the sum the driver formed
+}
+
+// src/Quadrature/d4est_quadrature.c:1019-1101: sum_q [jac_q] (w w [w] u [v])_q, in the reference's order of operations
+double d4est_quadrature_innerproduct(d4est_operators_t*, d4est_geometry_t*, d4est_quadrature_t* d4est_quad, void*,
+                                     d4est_quadrature_object_type_t object_type, d4est_quadrature_integrand_type_t, double* u, double* v,
+                                     double* jac_quad, int deg_quad) {
+  if (!u) COMPAT_ABORT("d4est_quadrature_innerproduct: u == NULL");
+  if (deg_quad < 1) COMPAT_ABORT("d4est_quadrature_innerproduct: deg_quad %d", deg_quad);
+  const int dim = (object_type == QUAD_OBJECT_MORTAR) ? 2 : 3, nq = deg_quad + 1;
+  std::vector<double> w((size_t)nq);
+  d4est_hip_table(quad_type_of(d4est_quad) == D4EST_HIP_QUAD_LOBATTO ? D4EST_HIP_TABLE_LOBATTO_WEIGHTS : D4EST_HIP_TABLE_GAUSS_WEIGHTS, deg_quad, 0, w.data());
+  double wdotuv = 0.0;
+  size_t s = 0;
+  for (int i = 0; i < (dim == 3 ? nq : 1); ++i)
+    for (int k = 0; k < nq; ++k)
+      for (int m = 0; m < nq; ++m, ++s) {
+        double t = (dim == 3) ? w[i] * w[k] * w[m] * u[s] : w[k] * w[m] * u[s];
+        if (v) t = t * v[s];
+        wdotuv += jac_quad ? jac_quad[s] * t : t;
+      }
+  return wdotuv;
+}
+
+// src/dGMath/d4est_laplacian.c:236-281 on the bound plan: the local elements' D_i u on the device
+void d4est_laplacian_compute_dudr(p4est_t* p4est, d4est_ghost_t*, d4est_ghost_data_t*, d4est_operators_t*, d4est_geometry_t*, d4est_quadrature_t*,
+                                  d4est_mesh_data_t*, double* dudr_local[3], double* dudr_ghost[3], double* u, int local_nodes, int which_field) {
+  const char* who = "d4est_laplacian_compute_dudr";
+  d4est_hip_plan_t* plan = bound(p4est, who);
+  if (!dudr_local || !dudr_local[0] || !dudr_local[1] || !dudr_local[2]) COMPAT_ABORT("%s: NULL dudr_local", who);
+  if (dudr_ghost && d4est_hip_plan_ghost_trace_size(plan) > 0)
+    COMPAT_ABORT("%s: the bound plan has ghost sides; the ghost elements' dudr needs the ghost layer, which is opaque here", who);
+  if (!u) COMPAT_ABORT("%s: NULL u", who);
+  const size_t n = (size_t)std::max(local_nodes, 1);
+  double* d_u = norms_upload(plan, u + (size_t)which_field * local_nodes, local_nodes, 3 * n, who);   // :265: which_field * local_nodes
+  d4est_hip_compute_dudr(plan, d_u, d_u + n, d_u + 2 * n, d_u + 3 * n);
+  d4est_hip_plan_synchronize(plan);
+  for (int i = 0; i < 3; ++i) d4est_hip_memcpy_d2h(dudr_local[i], d_u + (size_t)(1 + i) * n, sizeof(double) * (size_t)local_nodes);
+  d4est_hip_free(d_u);
 }
 
 void d4est_hip_compat_bind_operator(const void* p4est, d4est_apply_operator_fcn_t apply_lhs) {

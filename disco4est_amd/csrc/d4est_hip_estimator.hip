@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "d4est_hip_elem_l2.h"
 #include "d4est_hip_internal.h"
 #include "d4est_hip_tables.h"
 #include "d4est_hip_wave.h"
@@ -120,48 +121,13 @@ __global__ __launch_bounds__(256) void est_residual_kernel(const double* __restr
                                                            const double* __restrict__ w, int N, int NQ, int deg,
                                                            const double* __restrict__ diam, double* __restrict__ term0) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int N3 = N * N * N, xs = (N3 > NQ * NQ * N) ? N3 : NQ * NQ * N, ys = NQ * N * N;
-  double* X = smem;        // r_e, then the (a, b, k) partial
-  double* Y = X + xs;      // the (a, j, k) partial
-  double* Bs = Y + ys;     // NQ x N
-  double* ws = Bs + NQ * N;
-  double* red = ws + NQ;   // 256
-  for (int i = threadIdx.x; i < NQ * N; i += blockDim.x) Bs[i] = B[i];
-  for (int i = threadIdx.x; i < NQ; i += blockDim.x) ws[i] = w[i];
+  const ElemL2Lds lds = elem_l2_lds(smem, B, w, N, NQ);
   for (int el = blockIdx.x; el < n_elem; el += gridDim.x) {
-    const int e = elem_ids[el], ns = ns_list[el], qs = qs_list[el];
-    for (int i = threadIdx.x; i < N3; i += blockDim.x) X[i] = r[ns + i];
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < NQ * N * N; idx += blockDim.x) {   // x: Y(a, j, k) = sum_i B(a, i) X(i, j, k)
-      const int a = idx % NQ, jk = idx / NQ;
-      double s = 0.0;
-      for (int i = 0; i < N; ++i) s = fma(Bs[a * N + i], X[i + N * jk], s);
-      Y[idx] = s;
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < NQ * NQ * N; idx += blockDim.x) {  // y: X(a, b, k) = sum_j B(b, j) Y(a, j, k)
-      const int a = idx % NQ, b = (idx / NQ) % NQ, k = idx / (NQ * NQ);
-      double s = 0.0;
-      for (int j = 0; j < N; ++j) s = fma(Bs[b * N + j], Y[a + NQ * (j + N * k)], s);
-      X[idx] = s;
-    }
-    __syncthreads();
-    double acc = 0.0;
-    for (int idx = threadIdx.x; idx < NQ * NQ * NQ; idx += blockDim.x) {  // z, then w J v^2
-      const int ab = idx % (NQ * NQ), c = idx / (NQ * NQ);
-      double v = 0.0;
-      for (int k = 0; k < N; ++k) v = fma(Bs[c * N + k], X[ab + NQ * NQ * k], v);
-      acc += ws[ab % NQ] * ws[ab / NQ] * ws[c] * J[qs + idx] * v * v;
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-      __syncthreads();
-    }
+    const int e = elem_ids[el];
+    const double sum = elem_l2_sqr(lds, r + ns_list[el], J + qs_list[el], N, NQ);   // (d4est_hip_elem_l2.h: shared with the L2 norm)
     if (threadIdx.x == 0) {
       const double h = diam[e];
-      term0[e] = red[0] * (h * h / (double)(deg * deg));   // (d4est_estimator_bi.c:420-433: estimator *= h*h/(deg*deg))
+      term0[e] = sum * (h * h / (double)(deg * deg));   // (d4est_estimator_bi.c:420-433: estimator *= h*h/(deg*deg))
     }
     __syncthreads();
   }
@@ -227,10 +193,7 @@ __global__ __launch_bounds__(64) void est_face_kernel(const double* __restrict__
   }
 }
 
-// dynamic LDS of est_residual_kernel for one bucket: X, Y, the interpolation matrix, the weights, the reduction buffer
-static size_t residual_lds_bytes(int N, int NQ) {
-  return (size_t)(std::max(N * N * N, NQ * NQ * N) + NQ * N * N + NQ * N + NQ + 256) * sizeof(double);
-}
+static size_t residual_lds_bytes(int N, int NQ) { return elem_l2_lds_bytes(N, NQ); }   // dynamic LDS of est_residual_kernel for one bucket
 
 void estimator_destroy(d4est_hip_plan* plan) {
   EstHost* x = est_of(plan);
@@ -241,18 +204,14 @@ void estimator_destroy(d4est_hip_plan* plan) {
   plan->est = nullptr;
 }
 
-void estimator_setup(d4est_hip_plan* plan, const double* sj, const double* n, const double* drst_m, const double* drst_p, const double* hm,
-                     const double* hp) {
-  estimator_destroy(plan);
-  EstHost* x = new EstHost();
-  plan->est = x;
+MortarRecords mortar_records_upload(d4est_hip_plan* plan, const char* who, const double** face_ops, const double** hp_ops) {
   std::vector<EstMortar> mort;
   std::vector<int> first;
-  faces_estimator_mortars(plan, mort, first, &x->face_ops, &x->hp_ops);
+  faces_estimator_mortars(plan, mort, first, face_ops, hp_ops);
   int max_nq = 1;
   std::vector<char> used(64, 0);
   for (const EstMortar& m : mort) {
-    if (m.NQ < 2 || m.NQ > 63) D4EST_HIP_ABORT("plan_set_estimator: mortar with %d quadrature nodes per direction", m.NQ);
+    if (m.NQ < 2 || m.NQ > 63) D4EST_HIP_ABORT("%s: mortar with %d quadrature nodes per direction", who, m.NQ);
     max_nq = std::max(max_nq, m.NQ);
     used[m.NQ] = 1;
   }
@@ -269,10 +228,26 @@ void estimator_setup(d4est_hip_plan* plan, const double* sj, const double* n, co
     if (bytes) HIP_CHECK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
     return d;
   };
-  x->n_mortars = (int)mort.size();
-  x->d_mortars = (EstMortar*)up(mort.data(), mort.size() * sizeof(EstMortar));
-  x->d_elem_first = (int*)up(first.data(), first.size() * sizeof(int));
-  double* d_wt = (double*)up(wt.data(), wt.size() * sizeof(double));
+  MortarRecords r;
+  r.n_mortars = (int)mort.size();
+  r.max_nq = max_nq;
+  r.d_mortars = (EstMortar*)up(mort.data(), mort.size() * sizeof(EstMortar));
+  r.d_elem_first = (int*)up(first.data(), first.size() * sizeof(int));
+  r.d_wt = (double*)up(wt.data(), wt.size() * sizeof(double));
+  return r;
+}
+
+void estimator_setup(d4est_hip_plan* plan, const double* sj, const double* n, const double* drst_m, const double* drst_p, const double* hm,
+                     const double* hp) {
+  estimator_destroy(plan);
+  EstHost* x = new EstHost();
+  plan->est = x;
+  const MortarRecords rec = mortar_records_upload(plan, "plan_set_estimator", &x->face_ops, &x->hp_ops);
+  const int max_nq = rec.max_nq;
+  x->n_mortars = rec.n_mortars;
+  x->d_mortars = rec.d_mortars;
+  x->d_elem_first = rec.d_elem_first;
+  double* d_wt = rec.d_wt;
   const size_t tm = std::max<size_t>((size_t)plan->total_mortar_nodes, 1);
   HIP_CHECK(hipMalloc(&x->d_fac, 8 * tm * sizeof(double)));
   HIP_CHECK(hipMemsetAsync(x->d_fac, 0, 8 * tm * sizeof(double), plan->stream));

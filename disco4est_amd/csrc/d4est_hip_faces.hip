@@ -25,6 +25,7 @@
 #include "d4est_hip_internal.h"
 #include "d4est_hip_topology.h"
 #include "d4est_hip_maps.h"
+#include "d4est_hip_penalty.h"
 #include "d4est_hip_tables.h"
 #include "d4est_hip_wave.h"
 
@@ -201,21 +202,6 @@ __global__ __launch_bounds__(64) void bndry_interp_kernel(const double* __restri
 // ---------------------------------------------------------------------------
 // set-up: 7 combined geometric factors per mortar quadrature node
 // ---------------------------------------------------------------------------
-__device__ inline double sipg_penalty(int fcn, int deg_m, double h_m, int deg_p, double h_p, double prefactor) {
-  // src/dGMath/d4est_laplacian_flux_sipg.c:945-1005
-  if (fcn == 0) {
-    const double max_deg = (deg_m > deg_p) ? deg_m : deg_p, min_h = (h_m < h_p) ? h_m : h_p;
-    return (prefactor * max_deg * max_deg) / min_h;
-  } else if (fcn == 1) {
-    const double mean_p = .5 * (deg_m + deg_p), mean_h = .5 * (h_m + h_p);
-    return (prefactor * mean_p * mean_p) / mean_h;
-  } else if (fcn == 2) {
-    const double max_deg = (deg_m > deg_p) ? deg_m : deg_p, min_h = (h_m < h_p) ? h_m : h_p;
-    return (prefactor * (max_deg + 1) * (max_deg + 1)) / min_h;
-  }
-  return prefactor * .5 * (deg_m * deg_m / h_m + deg_p * deg_p / h_p);
-}
-
 __global__ __launch_bounds__(64) void face_geom_kernel(const SideDesc* __restrict__ sd, const int* __restrict__ side_deg_m,
                                                        const int* __restrict__ side_deg_p, int n_sides,
                                                        const double* __restrict__ sj, const double* __restrict__ nrm,
@@ -2853,6 +2839,8 @@ void faces_set_geometry(d4est_hip_plan* plan, const double* sj, const double* n,
   if (T > 0) HIP_CHECK(hipMemcpyAsync(fh.d_sj, dev[0], T * sizeof(double), hipMemcpyDeviceToDevice, plan->stream));
   // the estimator's factors (d4est_hip_plan_set_estimator): only on plans that asked for them
   if (plan->est_requested) estimator_setup(plan, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5]);
+  // the IP energy norm's face factor (d4est_hip_plan_set_energy_norm): likewise
+  if (plan->norm_requested) norms_setup(plan, dev[0], dev[1], dev[4], dev[5]);
   HIP_CHECK(hipStreamSynchronize(plan->stream));
   for (int i = 0; i < 6; ++i)
     if (tmp[i]) HIP_CHECK(hipFree(tmp[i]));
@@ -3601,6 +3589,7 @@ void launch_traces_all(d4est_hip_plan* plan, const double* u, double* trace) {
 
 void faces_destroy(d4est_hip_plan* plan) {
   estimator_destroy(plan);
+  norms_destroy(plan);
   direct_destroy(plan);
   hybrid_destroy(plan);
   auto it = g_face_host.find(plan);

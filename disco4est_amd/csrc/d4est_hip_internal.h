@@ -158,6 +158,13 @@ struct d4est_hip_plan {
   double est_prefactor = 0.0;
   void* est = nullptr;             // d4est_hip::EstHost
 
+  // error norms (d4est_hip_norms.hip): the IP energy norm is requested by d4est_hip_plan_set_energy_norm before the mortar factors, whose
+  // set-up then also forms its per-node face factor; the other norms allocate their scratch on first use (NormHost)
+  bool norm_requested = false;
+  int norm_fcn = -1;               // u_penalty_fcn: a SIPG penalty id (d4est_hip_plan_set_sipg)
+  double norm_prefactor = 0.0;
+  void* norms = nullptr;           // d4est_hip::NormHost
+
   // host-pointer entry points (d4est_hip_*_host): persistent pinned staging (3 vectors) and device mirrors u, rhs, Au, r,
   // allocated once on first use -- no per-call hipMalloc behind d4est's host double* API
   double* h_stage = nullptr;
@@ -293,11 +300,30 @@ void launch_traces_all(d4est_hip_plan* plan, const double* u, double* trace);
 // out[side_bndry_stride[s] + a + N b] = vol at face node (a, b) of every boundary side s (d4est_hip_plan_boundary_gather)
 void launch_boundary_gather(d4est_hip_plan* plan, const double* vol, double* out);
 // d4est_hip_estimator.hip
+// the mortar records of faces_estimator_mortars and the per-element first-record table on the device, with the tensor quadrature
+// weights of the plan's mortar degrees (row NQ - 1 of d_wt holds the NQ weights of degree NQ - 1, row length max_nq): what the set-up of
+// the estimator and of the energy norm both start from.  The caller owns the three device arrays (d_wt is freed after its geometry kernel).
+struct MortarRecords {
+  EstMortar* d_mortars;
+  int* d_elem_first;
+  double* d_wt;
+  int n_mortars, max_nq;
+};
+MortarRecords mortar_records_upload(d4est_hip_plan* plan, const char* who, const double** face_ops, const double** hp_ops);
 void estimator_setup(d4est_hip_plan* plan, const double* sj, const double* n, const double* drst_m, const double* drst_p, const double* hm,
                      const double* hp);
 void estimator_destroy(d4est_hip_plan* plan);
 void estimator_compute(d4est_hip_plan* plan, const double* u, const double* ghost_trace, const double* residual, const double* diam,
                        const double* g_lobatto, double* eta2, double* terms);
+
+// d4est_hip_norms.hip
+void norms_setup(d4est_hip_plan* plan, const double* sj, const double* n, const double* hm, const double* hp);
+void norms_destroy(d4est_hip_plan* plan);
+void norms_error(d4est_hip_plan* plan, const double* u, const double* u_compare, double* err);
+void norms_l2_sqr(d4est_hip_plan* plan, const double* v, const int* skip, double* l2_array, double* sum);
+void norms_linfty(d4est_hip_plan* plan, const double* v, const int* skip, double* max_out);
+void norms_ip_energy_sqr(d4est_hip_plan* plan, const double* v, const double* ghost_trace, double* elem_terms, double* sums);
+void norms_masked_sum(d4est_hip_plan* plan, const double* elem, const int* skip, double* sum);
 
 // d4est_hip_solver.hip
 // traces, volume term, (exchange), flux; lhs_term: also the optional zeroth-order term of plan_set_lhs_coefficient

@@ -298,6 +298,51 @@ void d4est_hip_estimator_bi(d4est_hip_plan_t* plan, const double* u_dev, const d
 /* 1 and the three ids and the prefactor of d4est_hip_plan_set_estimator (either output may be NULL) when the plan has the estimator,
  * else 0 -- for hosts that check a caller's penalty functions against the plan (the compat library's d4est_estimator_bi_compute) */
 int d4est_hip_plan_estimator_info(const d4est_hip_plan_t* plan, int* ids, double* penalty_prefactor);
+/* ---- error norms (csrc/d4est_hip_norms.hip) -----------------------------------------------------------------------------------------
+ * The columns of d4est_norms_save (src/IO/d4est_norms.c:380-560), which the drivers write once per AMR level (e.g.
+ * src/Problems/ConstantDensityStar/constant_density_star_mgpc_newton_petsc.c:266-287, :453-473): L_2, L_infty, energy_norm and
+ * energy_estimator.  Every result is this rank's LOCAL sum / maximum, left on the device: the reduction over ranks stays with the
+ * caller (the reference's sc_reduce sits outside the compute functions) and no square root is taken.  skip_dev: int[n_elements], 1 =
+ * skip the element (the reference's skip_element_fcn, evaluated by the caller), NULL = skip none.  Everything runs on the plan's
+ * stream without host synchronisation; no floating-point atomics, every reduction has a fixed order: bit-identical from call to call.
+ *
+ * The IP energy norm must be requested BEFORE d4est_hip_plan_set_mortar_geometry or its brick / analytic forms (its per-node face
+ * factor w sj pen |n|^2 is formed there, as the estimator's factors are).  penalty_fcn: u_penalty_fcn of d4est_ip_energy_norm_data_t,
+ * a penalty_calc_t by the ids of d4est_hip_plan_set_sipg (d4est_laplacian_flux_sipg.c:945-1005); penalty_prefactor: its last
+ * argument.  Plans without this call allocate nothing for it and behave as before.  Aborts on an id outside 0..3. */
+void d4est_hip_plan_set_energy_norm(d4est_hip_plan_t* plan, int penalty_fcn, double penalty_prefactor);
+/* 1 and the id and prefactor of d4est_hip_plan_set_energy_norm (either output may be NULL) when the plan has the request, else 0 */
+int d4est_hip_plan_energy_norm_info(const d4est_hip_plan_t* plan, int* penalty_fcn, double* penalty_prefactor);
+/* err = |u - u_compare| at the Lobatto nodes (d4est_norms_save, d4est_norms.c:467-468: the absolute value is taken at the nodes, before
+ * any interpolation).  u_compare_dev == NULL: err = |u|.  err_dev may alias u_dev. */
+void d4est_hip_norms_error(d4est_hip_plan_t* plan, const double* u_dev, const double* u_compare_dev, double* err_dev);
+/* d4est_mesh_compute_l2_norm_sqr (src/Mesh/d4est_mesh.c:2299-2374): l2_array_dev[e] = v_e^T M_e v_e = sum_q w J (V v_e)^2 at the
+ * element's deg_quad, written for EVERY element (NULL = not wanted); *sum_dev = the sum over the elements that are not skipped.
+ * Needs the volume geometry.  Limit: the estimator's residual term's (d4est_hip_estimator_bi). */
+void d4est_hip_norm_l2_sqr(d4est_hip_plan_t* plan, const double* v_dev, const int* skip_dev, double* l2_array_dev, double* sum_dev);
+/* d4est_norms_fcn_Linfty (d4est_norms.c:64-117): *max_dev = max(0, max_i v_i) over the nodes of the elements that are not skipped --
+ * the maximum of the values, not of their magnitudes, from a running maximum that starts at 0, as the reference has it (the drivers
+ * pass the error field, which is non-negative). */
+void d4est_hip_norm_linfty(d4est_hip_plan_t* plan, const double* v_dev, const int* skip_dev, double* max_dev);
+/* d4est_ip_energy_norm_compute (src/dGMath/d4est_ip_energy_norm.c:286-448), squared: sums_dev[4] = volume, boundary, interface and
+ * total = (volume + boundary) + interface (:440-443); elem_terms_dev[3 n_elements], term-major in the same order, each local side's
+ * part added to its own element (NULL = not wanted).
+ *   volume     sum_d sum_q w J (du/dx_d)^2, du/dx_d = sum_i rst_xyz[i][d] V(D_i u)      (d4est_gradient_l2_norm, d4est_gradient.c:71-124)
+ *   interface  per local side with an interior mortar: 3 sum_k w_k sj_k pen_k sum_d n_d^2 (u_m - u_p)^2        (:210-270)
+ *   boundary   per boundary side: sum_k w_k sj_k pen(deg, h_k, deg, h_k) sum_d n_d^2 u_m^2, no Dirichlet data  (:70-102)
+ * As in the reference: the factor 3 (the node value already sums over d and is added once more per direction, :251-268); pen is not
+ * squared; a face is visited from both of its local sides (an interior face between local elements counts twice), a ghost side from
+ * the local side only; a big hanging side adds its four sub-mortars, a small side its own; degrees as at :216-218.
+ * ghost_trace_dev: as for d4est_hip_estimator_bi (NULL = exchanged through the plan_set_comm hooks).  Needs the volume geometry,
+ * plan_set_faces, the mortar factors and d4est_hip_plan_set_energy_norm before them; aborts otherwise.  The same on every face path
+ * of the operator (the norm forms every side's trace itself, in a buffer of its own).  Limit: the volume term holds u_e and its
+ * three derivatives in LDS, (4 N^3 + 3 (N^2 + NQ N) + NQ N + N^2 + 256) doubles <= 160 KB, N = deg + 1, NQ = deg_quad + 1 --
+ * p <= 15; a plan beyond it aborts here. */
+void d4est_hip_ip_energy_norm_sqr(d4est_hip_plan_t* plan, const double* v_dev, const double* ghost_trace_dev, double* elem_terms_dev,
+                                  double* sums_dev);
+/* *sum_dev = the fixed-order sum of elem_dev[n_elements] over the elements that are not skipped: with eta2 of d4est_hip_estimator_bi,
+ * d4est_norms_fcn_energy_estimator (d4est_norms.c:249-297) */
+void d4est_hip_masked_sum(d4est_hip_plan_t* plan, const double* elem_dev, const int* skip_dev, double* sum_dev);
 /* total_bndry_nodes of plan_set_faces, and a device volume vector's values at the Lobatto face nodes of every boundary side in the layout
  * of d4est_hip_plan_set_dirichlet_values (side_bndry_stride; d4est_operators_apply_slicer order): where a host evaluates Dirichlet data
  * from the node coordinates (the three coordinate vectors gathered one by one) */

@@ -152,6 +152,40 @@ typedef struct {
   void* user;
 } d4est_estimator_bi_penalty_data_t;
 
+/* src/dGMath/d4est_ip_energy_norm.h:9-19 and src/IO/d4est_norms.h:25-62, member for member: what d4est_norms_save's norm functions
+ * are handed as their void* context.  d4est_element_data_t stays opaque: a skip_element_fcn cannot be evaluated here. */
+typedef struct d4est_element_data_opaque d4est_element_data_t;
+typedef struct {
+  penalty_calc_t u_penalty_fcn;
+  double penalty_prefactor;
+  d4est_mesh_size_parameters_t* size_params;
+  void* user;
+  double ip_energy_norm_sqr_volume_term;
+  double ip_energy_norm_sqr_boundary_term;
+  double ip_energy_norm_sqr_interface_term;
+} d4est_ip_energy_norm_data_t;
+typedef struct {
+  p4est_t* p4est;
+  d4est_operators_t* d4est_ops;
+  d4est_geometry_t* d4est_geom;
+  d4est_quadrature_t* d4est_quad;
+  d4est_mesh_data_t* d4est_factors;
+} d4est_norms_fcn_L2_ctx_t;
+typedef struct {
+  p4est_t* p4est;
+  d4est_ghost_t* ghost;
+  d4est_ghost_data_t* ghost_data;
+  d4est_operators_t* d4est_ops;
+  d4est_geometry_t* d4est_geom;
+  d4est_quadrature_t* d4est_quad;
+  d4est_mesh_data_t* d4est_factors;
+  int which_field;
+  d4est_ip_energy_norm_data_t* energy_norm_data;
+  double energy_estimator_sq_local;
+  double* energy_estimator;
+} d4est_norms_fcn_energy_ctx_t;
+typedef double (*d4est_norm_fcn_t)(p4est_t*, double*, int, void*, int (*)(d4est_element_data_t*));
+
 /* ---- element level: src/Quadrature/d4est_quadrature.h:132-141 ------------------------------------------------------------ */
 void d4est_quadrature_apply_stiffness_matrix(d4est_operators_t *d4est_ops,d4est_quadrature_t *d4est_quadrature,d4est_geometry_t *d4est_geometry,void *object,d4est_quadrature_object_type_t object_type,d4est_quadrature_integrand_type_t integrand_type,double *in,int deg_lobatto,double *jac_quad,double *rst_xyz[3][3],int deg_quad,double *out);
 void d4est_quadrature_apply_mass_matrix(d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geometry,d4est_quadrature_t *d4est_quadrature,void *object,d4est_quadrature_object_type_t object_type,d4est_quadrature_integrand_type_t integrand_type,double *in,int deg_lobatto,double *jac_quad,int deg_quad,double *out);
@@ -238,6 +272,36 @@ void cg_eigs(p4est_t *p4est,d4est_elliptic_data_t *vecs,d4est_elliptic_eqns_t *f
  * .) when the process has libsc (found with dlsym(RTLD_DEFAULT, .)), so that the caller's P4EST_FREE releases it, else with malloc (plain-C
  * hosts without libsc: free it with free). */
 double* d4est_estimator_bi_compute(p4est_t *p4est,d4est_elliptic_data_t *d4est_elliptic_data,d4est_elliptic_eqns_t *fcns,d4est_estimator_bi_penalty_data_t penalty_data,d4est_xyz_fcn_t u_bndry_fcn,void *bndry_ctx,d4est_ghost_t *d4est_ghost,d4est_ghost_data_t *d4est_ghost_data,d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geom_for_residual,d4est_mesh_data_t *d4est_factors_for_residual,d4est_geometry_t *d4est_geom_for_integrals,d4est_mesh_data_t *d4est_factors_for_integrals,d4est_quadrature_t *d4est_quad,int which_field,double *estimator_vtk,double *estimator_vtk_per_face);
+/* ---- the columns of d4est_norms_save on the bound plan (include/d4est_hip.h "error norms") ------------------------------------------
+ * The norm functions a driver lists in norm_fcns (src/IO/d4est_norms.h:68-75) and what they call.  Host vectors in; the vector goes
+ * up, the norm runs on the device, the scalars come back.  Each returns this rank's LOCAL value -- sqrt of the local sum, the local
+ * maximum -- where the reference returns the one reduced with sc_reduce: a one-rank run is unchanged, a multi-rank caller reduces the
+ * squares itself.  A non-NULL skip_element_fcn ABORTS: d4est_element_data_t is opaque here, so it cannot be evaluated; evaluate it
+ * per element into the skip mask of d4est_hip_norm_l2_sqr / d4est_hip_norm_linfty / d4est_hip_masked_sum instead.
+ *   d4est_mesh_compute_l2_norm_sqr   src/Mesh/d4est_mesh.h (d4est_mesh.c:2299-2374)  l2_array (n_elements, or NULL) is filled
+ *   d4est_norms_fcn_L2               d4est_norms.c:16-56     ctx: d4est_norms_fcn_L2_ctx_t, of which ctx->p4est is used
+ *   d4est_norms_fcn_Linfty           d4est_norms.c:64-117    max(0, max_i v_i): the maximum of the values from 0, as the reference
+ *   d4est_ip_energy_norm_compute     d4est_ip_energy_norm.c:286-448  the bound plan must carry d4est_hip_plan_set_energy_norm;
+ *                                    u_penalty_fcn is EVALUATED at probe arguments and matched against the four SIPG closed forms
+ *                                    (csrc/d4est_hip_compat_penalty.h); no match, or an id / prefactor other than the plan's, aborts.
+ *                                    The three terms are left in energy_norm_data, the return value is their sum, not its root (as the
+ *                                    reference).  which_field must be 0: the reference reads u without the field offset (:357)
+ *   d4est_norms_fcn_energy           d4est_norms.c:201-244   ctx: d4est_norms_fcn_energy_ctx_t
+ *   d4est_norms_fcn_energy_estimator d4est_norms.c:249-297   sqrt(ctx->energy_estimator_sq_local), as the reference without a skip
+ *                                    function: a host value the driver formed -- on the device with d4est_hip_masked_sum(eta2) */
+double d4est_mesh_compute_l2_norm_sqr(p4est_t *p4est,d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geom,d4est_quadrature_t *d4est_quad,d4est_mesh_data_t *d4est_factors,double *nodal_vec,int local_nodes,int(*skip_element_fcn)(d4est_element_data_t *),double *l2_array);
+double d4est_norms_fcn_L2(p4est_t *p4est,double *field_value_errors,int num_nodes_local,void *norm_fcn_ctx,int(*skip_element_fcn)(d4est_element_data_t *));
+double d4est_norms_fcn_Linfty(p4est_t *p4est,double *field_value_errors,int num_nodes_local,void *norm_fcn_ctx,int(*skip_element_fcn)(d4est_element_data_t *));
+double d4est_ip_energy_norm_compute(p4est_t *p4est,double *u,d4est_ip_energy_norm_data_t *energy_norm_data,d4est_ghost_t *d4est_ghost,d4est_ghost_data_t *d4est_ghost_data,d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geom,d4est_quadrature_t *d4est_quad,d4est_mesh_data_t *d4est_factors,int which_field);
+double d4est_norms_fcn_energy(p4est_t *p4est,double *field_value_errors,int num_nodes_local,void *norm_fcn_ctx,int(*skip_element_fcn)(d4est_element_data_t *));
+double d4est_norms_fcn_energy_estimator(p4est_t *p4est,double *field_value_errors,int num_nodes_local,void *norm_fcn_ctx,int(*skip_element_fcn)(d4est_element_data_t *));
+/* src/Quadrature/d4est_quadrature.h (d4est_quadrature.c:1019-1101): sum_q w_q [jac_q] u_q [v_q] at the quadrature nodes, v and jac_quad
+ * may be NULL; volume (dim 3) and mortar (dim 2) objects, on the host in the reference's order of operations */
+double d4est_quadrature_innerproduct(d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geom,d4est_quadrature_t *d4est_quad,void *object,d4est_quadrature_object_type_t object_type,d4est_quadrature_integrand_type_t integrand_type,double *u,double *v,double *jac_quad,int deg_quad);
+/* src/dGMath/d4est_laplacian.h:21 (d4est_laplacian.c:236-281) on the bound plan: dudr_local[i] = D_i u of the local elements, on the
+ * device (d4est_hip_compute_dudr).  The ghost elements' part needs the ghost layer, which is opaque here: dudr_ghost is not written,
+ * and a bound plan that has ghost sides aborts when dudr_ghost is asked for (the engine exchanges traces, not element data) */
+void d4est_laplacian_compute_dudr(p4est_t *p4est,d4est_ghost_t *d4est_ghost,d4est_ghost_data_t *d4est_ghost_data,d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geom,d4est_quadrature_t *d4est_quad,d4est_mesh_data_t *d4est_factors,double *dudr_local[3],double *dudr_ghost[3],double *D4EST_RESTRICT u,int local_nodes,int which_field);
 #endif /* D4EST_HIP_COMPAT_NO_TYPES */
 
 /* ---- binding (not in the reference) ------------------------------------------------------------------------------------------ */
