@@ -71,6 +71,7 @@ SIGNATURES = {
     "d4est_hip_transfer_prolong_add": (None, [_vp, _vp, _vp]),
     "d4est_hip_transfer_restrict": (None, [_vp, _vp, _vp]),
     "d4est_hip_transfer_project": (None, [_vp, _vp, _vp]),
+    "d4est_hip_transfer_describe": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     "d4est_hip_schwarz_create": (_vp, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     "d4est_hip_schwarz_destroy": (None, [_vp]),
     "d4est_hip_schwarz_nodal_size": (ctypes.c_longlong, [_vp]),
@@ -717,6 +718,17 @@ class Transfer:
         """L2 projection onto the coarse space (apply_p_restrict / apply_hp_restrict per item)"""
         assert x_fine.numel() == self.fine_nodes and x_coarse.numel() == self.coarse_nodes
         self.lib.d4est_hip_transfer_project(self.handle, _ptr(x_fine), _ptr(x_coarse))
+
+    def describe(self):
+        """the work lists behind this transfer (d4est_hip_transfer_describe): {"prolong" | "restrict" | "galerkin": [(NH, dmax, nc, n, cg)]};
+        NH = 0 is the generic list, "galerkin" is empty until a one-transfer chain with this transfer is set on a plan"""
+        out = {}
+        for which, name in enumerate(("prolong", "restrict", "galerkin")):
+            n = self.lib.d4est_hip_transfer_describe(self.handle, which, None, 0)
+            buf = ctypes.create_string_buffer(n + 1)
+            self.lib.d4est_hip_transfer_describe(self.handle, which, buf, n + 1)
+            out[name] = [tuple(int(v) for v in line.split()) for line in buf.value.decode().splitlines()]
+        return out
 
     def destroy(self):
         if self.handle:

@@ -10,7 +10,9 @@
 //   hrefine == 0: one fine element of degree degh[0] <-> the coarse element of degree degH (p-coarsening; a copy if equal)
 //   hrefine == 1: eight children (z-order, degrees degh[0..7]) <-> their parent (h- and p-coarsening at once)
 // Vectors are element-ordered and contiguous on both grids, as in the reference (fine_stride / coarse_stride advance).
+#include <cstring>
 #include <map>
+#include <string>
 #include <vector>
 
 #include "d4est_hip_internal.h"
@@ -393,6 +395,12 @@ static void fast_lds_limit(K kernel, size_t bytes) {
   if (bytes > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
 
+// child groups a restriction / Galerkin launch of one list runs with: the instance's CGMAX where the list alone does not fill the chip
+// (coarse levels); with thousands of coarse elements one group per element keeps more elements in flight (level 5, p = 3: 61 us against
+// 113 us with groups).  The ONE statement of the rule: the launches and d4est_hip_transfer_describe both call it.
+constexpr int kOneGroupFrom = 8192;
+static inline int child_groups(int cg_max, int n_children, int n) { return (n_children == 8 && n < kOneGroupFrom) ? cg_max : 1; }
+
 // launches of one (NH, DMAX) list
 template <int NH, int DMAX, bool ADD>
 static void go_prolong(d4est_hip_transfer* t, const double* xc, double* xf, const int* list, int n) {
@@ -405,9 +413,7 @@ template <int NH, int DMAX>
 static void go_restrict(d4est_hip_transfer* t, const double* xf, double* xc, const double* ops, const int* list, int n, int n_children) {
   using C = TransferCfg<NH, DMAX>;
   // child groups: as many of the item's children at once as the LDS (and 1024 threads) hold
-  // child groups where the list alone does not fill the chip (coarse levels); with thousands of coarse elements one group per element
-  // keeps more elements in flight (level 5, p = 3: 61 us against 113 us with groups)
-  const int cg = (n_children == 8 && n < 8192) ? C::CGMAX : 1;
+  const int cg = child_groups(C::CGMAX, n_children, n);
   const size_t lds = (size_t)cg * C::LDS_RESTRICT * sizeof(double);
   fast_lds_limit(restrict_fast_kernel<NH, DMAX>, lds);
   hipLaunchKernelGGL((restrict_fast_kernel<NH, DMAX>), dim3(n), dim3(C::THREADS * cg), lds, t->stream, xf, xc, t->d_child, t->d_off,
@@ -446,7 +452,7 @@ static void launch_fast_restrict(d4est_hip_transfer* t, const double* xf, double
 template <int NH, int DMAX>
 static void go_galerkin(d4est_hip_transfer* t, const double* u, double* Au, const double* wjc, const int* list, int n, int n_children, hipStream_t st) {
   using C = GalerkinCfg<NH, DMAX>;
-  const int cg = (n_children == 8 && n < 8192) ? C::CGMAX : 1;
+  const int cg = child_groups(C::CGMAX, n_children, n);
   const size_t lds = (size_t)cg * C::LDS * sizeof(double);
   fast_lds_limit(galerkin_fast_kernel<NH, DMAX>, lds);
   hipLaunchKernelGGL((galerkin_fast_kernel<NH, DMAX>), dim3(n), dim3(C::THREADS * cg), lds, st, u, Au, wjc, t->d_child, t->d_off, t->d_item_first,
@@ -535,6 +541,19 @@ void galerkin_fused_apply(d4est_hip_transfer* t, const double* wjc, const double
     if (!done) D4EST_HIP_ABORT("fused Galerkin term: no kernel for %d coarse nodes per direction", L.NH);
   }
   HIP_CHECK(hipGetLastError());
+}
+
+// CGMAX of the instance a list with this (NH, dmax) is launched with (the dispatch above: dmax 0, 1, else the DMAX = 3 instance)
+static int instance_cg_max(bool galerkin, int NH, int dmax) {
+#define X(N_)                                                                                                                       \
+  if (NH == N_) {                                                                                                                   \
+    if (dmax == 0) return galerkin ? GalerkinCfg<N_, 0>::CGMAX : TransferCfg<N_, 0>::CGMAX;                                         \
+    if (dmax == 1) return galerkin ? GalerkinCfg<N_, 1>::CGMAX : TransferCfg<N_, 1>::CGMAX;                                         \
+    return galerkin ? GalerkinCfg<N_, 3>::CGMAX : TransferCfg<N_, 3>::CGMAX;                                                        \
+  }
+  D4EST_HIP_TRANSFER_NH(X)
+#undef X
+  return 1;
 }
 
 }  // namespace d4est_hip
@@ -706,6 +725,26 @@ void d4est_hip_transfer_destroy(d4est_hip_transfer_t* t) {
 void d4est_hip_transfer_set_stream(d4est_hip_transfer_t* t, void* hip_stream) {
   if (!t) D4EST_HIP_ABORT("transfer_set_stream: NULL transfer");
   t->stream = (hipStream_t)hip_stream;
+}
+
+int d4est_hip_transfer_describe(const d4est_hip_transfer_t* t, int which, char* buf, int len) {
+  if (!t) D4EST_HIP_ABORT("transfer_describe: NULL transfer");
+  if (which < 0 || which > 2) D4EST_HIP_ABORT("transfer_describe: which = %d (0 prolongation, 1 restriction / projection, 2 fused Galerkin term)", which);
+  const std::vector<d4est_hip_transfer::List>& lists = which == 0 ? t->prolong_lists : which == 1 ? t->restrict_lists : t->gal_lists;
+  std::string s;
+  char line[96];
+  for (const d4est_hip_transfer::List& L : lists) {
+    // the prolongation works per fine element, the generic kernels per element in a loop: no child groups in either
+    const int cg = (which == 0 || L.NH == 0) ? 1 : d4est_hip::child_groups(d4est_hip::instance_cg_max(which == 2, L.NH, L.dmax), L.nc, L.n);
+    snprintf(line, sizeof line, "%d %d %d %d %d\n", L.NH, L.dmax, L.nc, L.n, cg);
+    s += line;
+  }
+  if (buf && len > 0) {
+    const size_t k = std::min(s.size(), (size_t)len - 1);
+    memcpy(buf, s.data(), k);
+    buf[k] = 0;
+  }
+  return (int)s.size();
 }
 
 long long d4est_hip_transfer_coarse_nodes(const d4est_hip_transfer_t* t) { return t ? t->coarse_nodes : -1; }

@@ -603,6 +603,13 @@ void d4est_hip_transfer_restrict(d4est_hip_transfer_t* t, const double* x_fine_d
 /* x_coarse = L2 projection of x_fine (d4est_operators_apply_p_restrict / _hp_restrict per item, src/dGMath/d4est_operators.c:1205-1230,
  * :1275-1297: M_H^-1 P^T M_h, children summed; the restriction of FIELDS, e.g. of the solution when the mesh is coarsened) */
 void d4est_hip_transfer_project(d4est_hip_transfer_t* t, const double* x_fine_dev, double* x_coarse_dev);
+/* Which kernels serve this transfer (read-only; launches nothing): the work lists of the prolongation (which = 0), of the restriction and
+ * projection (1) and of the fused Galerkin term (2: built when a one-transfer chain is set on a plan, empty before and when the chain runs
+ * unfused), one text line "NH dmax nc n cg" per list.  NH: coarse nodes per direction of the compile-time kernel, 0 for the generic
+ * runtime-size kernels; dmax: the list's largest fine-minus-coarse size (instances exist for 0, 1 and 3: a list with 2 runs the 3);
+ * nc: children per coarse element (restriction / Galerkin lists: 1 or 8); n: entries; cg: child groups per workgroup the launch uses.
+ * Writes at most len - 1 characters and a NUL into buf (may be NULL), returns the full length. */
+int d4est_hip_transfer_describe(const d4est_hip_transfer_t* t, int which, char* buf, int len);
 
 /* The restriction of the multigrid matrix operator's element blocks through this transfer's item list (the restriction callback of
  * src/Solver/d4est_solver_multigrid_matrix_operator.c:6-48 for every coarse element): coarse block k = sum_c P_c^T M_c P_c over the item's
