@@ -175,6 +175,24 @@ SIGNATURES = {
     "d4est_hip_memcpy_h2d_async": (None, [_vp, _vp, _vp, ctypes.c_size_t]),
     "d4est_hip_memcpy_d2h_async": (None, [_vp, _vp, _vp, ctypes.c_size_t]),
     "d4est_hip_plan_synchronize": (None, [_vp]),
+    "d4est_hip_amr_create": (_vp, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_double]),
+    "d4est_hip_amr_destroy": (None, [_vp]),
+    "d4est_hip_amr_set_stream": (None, [_vp, _vp]),
+    "d4est_hip_amr_n_elements": (ctypes.c_int, [_vp]),
+    "d4est_hip_amr_local_nodes": (ctypes.c_longlong, [_vp]),
+    "d4est_hip_amr_stats": (None, [_vp, _vp, ctypes.c_int, _vp]),
+    "d4est_hip_amr_mark_smooth_pred": (None, [_vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    "d4est_hip_amr_p_balance": (None, [_vp, _vp, ctypes.c_int]),
+    "d4est_hip_amr_get_refinement_log": (None, [_vp, _vp]),
+    "d4est_hip_amr_set_refinement_log": (None, [_vp, _vp]),
+    "d4est_hip_amr_get_predictor": (None, [_vp, _vp]),
+    "d4est_hip_amr_set_balance": (None, [_vp, ctypes.c_int, _vp]),
+    "d4est_hip_amr_new_n_elements": (ctypes.c_int, [_vp]),
+    "d4est_hip_amr_new_local_nodes": (ctypes.c_longlong, [_vp]),
+    "d4est_hip_amr_get_new_degrees": (None, [_vp, _vp]),
+    "d4est_hip_amr_interpolate_field": (None, [_vp, _vp, _vp]),
+    "d4est_hip_amr_describe": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int]),
+    "d4est_hip_amr_advance": (None, [_vp]),
 }
 
 TABLE = {
@@ -733,6 +751,87 @@ class Transfer:
     def destroy(self):
         if self.handle:
             self.lib.d4est_hip_transfer_destroy(self.handle)
+            self.handle = None
+
+
+class Amr:
+    """One rank's hp-AMR bookkeeping on the device (d4est_hip_amr_*): degrees, the smooth_pred predictor, the refinement log, and the
+    transfer of a field to the refined and balanced grid.  eta2 / stats / fields are float64 CUDA tensors; the logs are host int arrays."""
+
+    def __init__(self, deg, max_degree, initial_pred, stream=None):
+        self.lib = load_library()
+        d = _iarr(deg)
+        self.handle = self.lib.d4est_hip_amr_create(len(d[0]), d[1], int(max_degree), float(initial_pred))
+        if stream is not None:
+            self.lib.d4est_hip_amr_set_stream(self.handle, ctypes.c_void_p(stream.cuda_stream))
+
+    @property
+    def n_elements(self):
+        return self.lib.d4est_hip_amr_n_elements(self.handle)
+
+    @property
+    def local_nodes(self):
+        return self.lib.d4est_hip_amr_local_nodes(self.handle)
+
+    def stats(self, eta2, percentile, stats):
+        """stats (4 doubles on the device) <- total, mean, max, estimator_at_percentile"""
+        assert eta2.numel() == self.n_elements and stats.numel() == 4
+        self.lib.d4est_hip_amr_stats(self.handle, _ptr(eta2), int(percentile), _ptr(stats))
+
+    def mark_smooth_pred(self, eta2, threshold, factor, gamma_h, gamma_p, gamma_n):
+        """threshold: a one-entry device tensor, e.g. stats[1:2] (mean; factor = sigma) or stats[3:4] (percentile; factor = 1)"""
+        assert eta2.numel() == self.n_elements and threshold.numel() == 1
+        self.lib.d4est_hip_amr_mark_smooth_pred(self.handle, _ptr(eta2), _ptr(threshold), float(factor), float(gamma_h), float(gamma_p),
+                                                float(gamma_n))
+
+    def p_balance(self, p_balance, p_balance_if_diff):
+        a = _iarr(p_balance)
+        assert len(a[0]) == self.n_elements
+        self.lib.d4est_hip_amr_p_balance(self.handle, a[1], int(p_balance_if_diff))
+
+    def get_refinement_log(self):
+        out = np.empty(self.n_elements, dtype=np.int32)
+        self.lib.d4est_hip_amr_get_refinement_log(self.handle, out.ctypes.data_as(_c_int_p))
+        return out
+
+    def set_refinement_log(self, log):
+        a = _iarr(log)
+        assert len(a[0]) == self.n_elements
+        self.lib.d4est_hip_amr_set_refinement_log(self.handle, a[1])
+
+    def get_predictor(self):
+        out = np.empty(self.n_elements, dtype=np.float64)
+        self.lib.d4est_hip_amr_get_predictor(self.handle, out.ctypes.data_as(_c_double_p))
+        return out
+
+    def set_balance(self, balance_log):
+        a = _iarr(balance_log)
+        self.lib.d4est_hip_amr_set_balance(self.handle, len(a[0]), a[1])
+        self.new_n_elements = self.lib.d4est_hip_amr_new_n_elements(self.handle)
+        self.new_local_nodes = self.lib.d4est_hip_amr_new_local_nodes(self.handle)
+
+    def new_degrees(self):
+        out = np.empty(self.lib.d4est_hip_amr_new_n_elements(self.handle), dtype=np.int32)
+        self.lib.d4est_hip_amr_get_new_degrees(self.handle, out.ctypes.data_as(_c_int_p))
+        return out
+
+    def interpolate_field(self, field_old, field_new):
+        assert field_old.numel() == self.local_nodes and field_new.numel() == self.new_local_nodes
+        self.lib.d4est_hip_amr_interpolate_field(self.handle, _ptr(field_old), _ptr(field_new))
+
+    def describe(self):
+        """the work lists of the field transfer: [(NH, dmax, nout, n)]; NH = 0 is the runtime-size kernel, (-1, 0, 0, n_aux) two-stage mode"""
+        n = self.lib.d4est_hip_amr_describe(self.handle, None, 0)
+        buf = ctypes.create_string_buffer(n + 1)
+        self.lib.d4est_hip_amr_describe(self.handle, buf, n + 1)
+        return [tuple(int(v) for v in line.split()) for line in buf.value.decode().splitlines()]
+
+    def advance(self):
+        self.lib.d4est_hip_amr_advance(self.handle)
+
+    def destroy(self):
+        if self.handle:
+            self.lib.d4est_hip_amr_destroy(self.handle)
             self.handle = None
 
 

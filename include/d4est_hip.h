@@ -25,6 +25,7 @@ extern "C" {
 
 typedef struct d4est_hip_plan d4est_hip_plan_t;
 typedef struct d4est_hip_transfer d4est_hip_transfer_t;   /* hp-multigrid inter-grid transfer, see below */
+typedef struct d4est_hip_amr d4est_hip_amr_t;             /* one rank's hp-AMR bookkeeping, see below */
 
 /* quadrature types (reference: [quadrature] name = legendre | lobatto,
  * src/Quadrature/d4est_quadrature_legendre.c:6-20, d4est_quadrature_lobatto.c:6-21) */
@@ -746,6 +747,69 @@ void d4est_hip_schwarz_smooth(d4est_hip_schwarz_t* sz, d4est_hip_plan_t* mesh_pl
                               int smoother_iterations, int subdomain_iter, double subdomain_atol, double subdomain_rtol);
 /* schwarz->subdomain_solve_iterations / _residuals of the last iterate (d4est_solver_schwarz.c:259-260), host arrays of n_subdomains */
 void d4est_hip_schwarz_get_info(d4est_hip_schwarz_t* sz, int* final_iter_host, double* final_res_host);
+
+/* ---- the hp-AMR step (csrc/d4est_hip_amr.hip) ----------------------------------------------------------------------------------------
+ * What d4est_amr_step (src/hpAMR/d4est_amr.c:852-1035) does between two solves, minus p4est's own work: the estimator statistics, the
+ * smooth_pred marking with its predictor, the p-balance update, and the interpolation of a field onto the refined and balanced grid.
+ * p4est_refine_ext, p4est_balance_ext and the p-balance face walk (d4est_amr.c:923-958) stay on the host; they exchange the refinement
+ * log, the balance log and the p_balance array -- one int per element -- with this object.  Everything runs on the object's stream
+ * (default: the null stream); nothing allocates after create / set_balance; no floating-point atomics and fixed reduction orders, so
+ * results are bit-identical from call to call.  One rank: reductions over ranks stay with the caller, as for the norms.
+ *
+ * create: the per-element degrees (1 .. 20, the limit of d4est_hip_transfer_create's kernels: two (deg + 1)^3 fields in the 160 KB LDS;
+ * aborts above it), amr->max_degree, and the predictor filled with initial_pred as d4est_amr_smooth_pred_pre_refine_callback does
+ * (src/hpAMR/d4est_amr_smooth_pred.c:23-71; the checkpoint branch is not covered).  Environment D4EST_HIP_AMR_TWO_STAGE=1, read here:
+ * d4est_hip_amr_interpolate_field runs as two d4est_hip_transfer_prolong calls through an internal auxiliary vector (A/B measurement). */
+d4est_hip_amr_t* d4est_hip_amr_create(int n_elements, const int* deg, int max_degree, double initial_pred);
+void d4est_hip_amr_destroy(d4est_hip_amr_t* amr);
+void d4est_hip_amr_set_stream(d4est_hip_amr_t* amr, void* hip_stream);
+int d4est_hip_amr_n_elements(const d4est_hip_amr_t* amr);
+long long d4est_hip_amr_local_nodes(const d4est_hip_amr_t* amr);
+/* d4est_estimator_stats_compute_aux, the mpisize == 1 branch (src/Estimators/d4est_estimator_stats.c:219-251), results on the device:
+ * stats_dev[0] estimator_total (a fixed-order sum of eta2), [1] estimator_mean = total / n, [2] estimator_max, [3] estimator_at_percentile
+ * = entry (int)(((double)n)*(1.-((double)percentile/100.0))) of the ascending-sorted eta2 (:249; the index is evaluated on the host in that
+ * arithmetic; the sort is a device radix sort, eta2_dev is left as it is).  percentile 1 .. 100; with percentile = 0 the reference reads
+ * one past the end of the array: here stats_dev[3] = -1.  n = 0 writes 0, -1, -1, -1 (:234-238). */
+void d4est_hip_amr_stats(d4est_hip_amr_t* amr, const double* eta2_dev, int percentile, double* stats_dev);
+/* d4est_amr_smooth_pred_mark_elements (src/hpAMR/d4est_amr_smooth_pred.c:215-268) for every element, with the marker
+ * eta2 >= factor * (*threshold_dev): sigma * mean as in Problems/Stamm/stamm_multigrid_pc.c:35-50 (stats_dev + 1, sigma) and the
+ * percentile markers (stats_dev + 3, 1.0).  Writes the refinement log and the new predictor (:253-267); the products are rounded
+ * multiplications taken left to right, never fused: the predictor is bit-identical to a plain C evaluation. */
+void d4est_hip_amr_mark_smooth_pred(d4est_hip_amr_t* amr, const double* eta2_dev, const double* threshold_dev, double factor,
+                                    double gamma_h, double gamma_p, double gamma_n);
+/* d4est_amr.c:973-981 and d4est_amr_smooth_pred_compute_post_p_balance_predictor (d4est_amr_smooth_pred.c:132-168): where
+ * p_balance_host[e] >= p_balance_if_diff and deg < max_degree - 1 a non-negative log entry gains 1, a negative one loses 1, and the
+ * predictor is multiplied by gamma_p (of the last mark call; 1 before any).  The face walk that fills p_balance is the host's. */
+void d4est_hip_amr_p_balance(d4est_hip_amr_t* amr, const int* p_balance_host, int p_balance_if_diff);
+/* The refinement log for p4est_refine_ext, already clipped at max_degree as d4est_amr_refine_callback does (d4est_amr.c:182-184);
+ * synchronises the stream. */
+void d4est_hip_amr_get_refinement_log(d4est_hip_amr_t* amr, int* log_host);
+/* A log made elsewhere (the uniform and random schemes, another marker).  An entry whose magnitude is below the element's degree aborts
+ * with the reference's message: coarsening is not supported in d4est_amr_interpolate_field_on_element either (d4est_amr.c:386-392). */
+void d4est_hip_amr_set_refinement_log(d4est_hip_amr_t* amr, const int* log_host);
+void d4est_hip_amr_get_predictor(d4est_hip_amr_t* amr, double* pred_host);
+/* The balance log of d4est_amr_balance_elements (d4est_amr.c:219-283) over the auxiliary (refined, unbalanced) grid: 8 auxiliary elements
+ * per negative entry of the refinement log, 1 otherwise; |balance_log[i]| is auxiliary element i's degree, a negative entry splits it into
+ * 8 children of that degree.  n_aux or a degree that does not match aborts.  Builds the new grid's degree list and the transfer tables;
+ * afterwards the three queries give what the host needs for the next plan (degrees in traversal order). */
+void d4est_hip_amr_set_balance(d4est_hip_amr_t* amr, int n_aux, const int* balance_log_host);
+int d4est_hip_amr_new_n_elements(const d4est_hip_amr_t* amr);
+long long d4est_hip_amr_new_local_nodes(const d4est_hip_amr_t* amr);
+void d4est_hip_amr_get_new_degrees(const d4est_hip_amr_t* amr, int* deg_host);
+/* d4est_amr_interpolate_field (d4est_amr.c:397-482) in one kernel and without the auxiliary vector: every new element's 1-D operator per
+ * direction is the product (formed in fp64 by set_balance) of stage 1 -- identity, p_prolong(deg -> deg') or hp_prolong(deg -> deg')[bit] --
+ * and stage 2 -- identity or hp_prolong(deg' -> deg')[bit]; kept -> kept, kept / p-refined -> split, split -> kept and split -> split
+ * (64 new elements from one) are all served.  field_old_dev has local_nodes entries, field_new_dev new_local_nodes. */
+void d4est_hip_amr_interpolate_field(d4est_hip_amr_t* amr, const double* field_old_dev, double* field_new_dev);
+/* Which kernels serve the transfer (read-only, after set_balance): one text line "NH dmax nout n" per work list of auxiliary elements.  NH:
+ * source nodes per direction of the compile-time kernel (2 .. 8), 0 for the runtime-size kernel; dmax: the list's largest new-minus-old
+ * size (instances exist for 0, 1 and 3: a list with 2 runs the 3); nout: the most new elements an auxiliary element of the list becomes
+ * (1 or 8); n: entries.  In two-stage mode one line "-1 0 0 n_aux".  Same buffer convention as d4est_hip_transfer_describe. */
+int d4est_hip_amr_describe(const d4est_hip_amr_t* amr, char* buf, int len);
+/* d4est_amr_smooth_pred_compute_post_h_balance_predictor (d4est_amr_smooth_pred.c:73-129): children of a refined element inherit the
+ * predictor, children of a balance split get 0.125 * gamma_h * 0.5^(2 |balance_log|) * aux (gamma_h of the last mark call); then the new
+ * degrees become current and the object is ready for the next level (the balance state is dropped; synchronises the stream). */
+void d4est_hip_amr_advance(d4est_hip_amr_t* amr);
 
 #ifdef __cplusplus
 }
