@@ -61,6 +61,8 @@ SIGNATURES = {
     "d4est_hip_plan_set_geometry_brick": (None, [_vp, _vp, ctypes.c_double, _vp]),
     "d4est_hip_plan_set_geometry_analytic": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double]),
     "d4est_hip_plan_set_mortar_geometry_analytic": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double]),
+    "d4est_hip_plan_compute_xyz_analytic": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
+    "d4est_hip_tree_map": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp]),
     "d4est_hip_plan_set_mortar_geometry_brick": (None, [_vp, _vp, ctypes.c_double, _vp]),
     "d4est_hip_transfer_create": (_vp, [ctypes.c_int, _vp, _vp, _vp]),
     "d4est_hip_transfer_destroy": (None, [_vp]),
@@ -241,6 +243,24 @@ def table(name, deg_a, deg_b=0):
     return out
 
 
+def tree_map(geom_type, params, tree, xi):
+    """the library's analytic tree map evaluated on the HOST (d4est_hip_tree_map; no GPU needed): xi[n, 3] tree coordinates ->
+    (status, x[n, 3], dxdxi[n, 3, 3]); status is the first non-zero return code (unknown type, rejected flag, tree out of range) or 0"""
+    lib = load_library()
+    pr = np.zeros(5)
+    pv = np.asarray(params, dtype=np.float64).reshape(-1)
+    pr[:pv.size] = pv
+    xi = np.ascontiguousarray(np.asarray(xi, dtype=np.float64).reshape(-1, 3))
+    X = np.full((xi.shape[0], 3), np.nan)
+    D = np.full((xi.shape[0], 3, 3), np.nan)
+    for k in range(xi.shape[0]):
+        rc = lib.d4est_hip_tree_map(int(geom_type), pr.ctypes.data_as(_vp), int(tree), xi[k].ctypes.data_as(_vp),
+                                    X[k].ctypes.data_as(_vp), D[k].ctypes.data_as(_vp))
+        if rc:
+            return rc, X, D
+    return 0, X, D
+
+
 def _ptr(t):
     """Device pointer of a contiguous float64 torch CUDA tensor."""
     import torch
@@ -342,7 +362,8 @@ class Plan:
 
     def set_geometry_analytic(self, geom_type, params, tree, q, dq, root_len, mortars=False, ghost=None):
         """factors of an analytic tree map generated on the device (geom_type 1 = cubed_sphere_7tree, params = (R0, R1,
-        compactify_inner_shell)); tree / q[n,3] / dq: where every element sits in the forest; mortars=True: the mortar factors
+        compactify_inner_shell); 2 = cubed_sphere, 3 = cubed_sphere_with_sphere_hole, 4 = cubed_sphere_with_cube_hole, params = (R0, R1,
+        R2, compactify_outer_shell, compactify_inner_shell), e.g. forest.CubedSphere13Map(...).params); tree / q[n,3] / dq: where every element sits in the forest; mortars=True: the mortar factors
         (ghost = (tree, q, dq) of the ghost elements)"""
         pr = np.ascontiguousarray(params, dtype=np.float64)
         t, qq, d = _iarr(tree), _iarr(np.asarray(q).reshape(-1)), _iarr(dq)
@@ -353,6 +374,20 @@ class Plan:
             (_iarr(np.zeros(0)), _iarr(np.zeros(0)), _iarr(np.zeros(0)))
         self.lib.d4est_hip_plan_set_mortar_geometry_analytic(self.handle, int(geom_type), pr.ctypes.data_as(_vp), t[1], qq[1], d[1],
                                                              gt[1], gq[1], gd[1], float(root_len))
+
+    def compute_xyz_analytic(self, geom_type, params, tree, q, dq, root_len, xyz_lobatto=None, xyz_quad=None):
+        """node coordinates of an analytic tree map on the device: xyz_lobatto (3 * local_nodes, x | y | z at the Lobatto nodes) and /
+        or xyz_quad (3 * local_nodes_quad, at the quadrature nodes); float64 CUDA tensors, either may be None.  Stream-ordered."""
+        pr = np.zeros(5)
+        pv = np.asarray(params, dtype=np.float64).reshape(-1)
+        pr[:pv.size] = pv
+        t, qq, d = _iarr(tree), _iarr(np.asarray(q).reshape(-1)), _iarr(dq)
+        assert len(t[0]) == self.n_elements and len(d[0]) == self.n_elements and len(qq[0]) == 3 * self.n_elements
+        assert xyz_lobatto is None or xyz_lobatto.numel() >= 3 * self.local_nodes
+        assert xyz_quad is None or xyz_quad.numel() >= 3 * self.local_nodes_quad
+        self.lib.d4est_hip_plan_compute_xyz_analytic(self.handle, int(geom_type), pr.ctypes.data_as(_vp), t[1], qq[1], d[1], float(root_len),
+                                                     _ptr(xyz_lobatto) if xyz_lobatto is not None else None,
+                                                     _ptr(xyz_quad) if xyz_quad is not None else None)
 
     def apply_weighted_mass_matrix(self, u, coeff_quad, out):
         assert u.numel() == self.local_nodes and out.numel() == self.local_nodes
@@ -509,9 +544,18 @@ class Plan:
         self.lib.d4est_hip_masked_sum(self.handle, _ptr(elem), self._iptr(d_skip), _ptr(out))
         self._sync_after_upload(d_skip is not None and d_skip is not skip, elem.device)
 
+    def boundary_gather(self, vol, out):
+        """out[bndry_nodes] = the volume field vol (local_nodes) on the Lobatto nodes of every boundary face, in the order
+        set_dirichlet_values expects (e.g. one component of compute_xyz_analytic's xyz_lobatto at a time)"""
+        assert vol.numel() == self.local_nodes and out.numel() == self.lib.d4est_hip_plan_bndry_nodes(self.handle)
+        self.lib.d4est_hip_plan_boundary_gather(self.handle, _ptr(vol), _ptr(out))
+
     def set_dirichlet_values(self, g):
         if g is None:
             self.lib.d4est_hip_plan_set_dirichlet_values(self.handle, None, 0)
+        elif not isinstance(g, np.ndarray) and hasattr(g, "data_ptr"):      # a float64 CUDA tensor
+            assert g.numel() == self.lib.d4est_hip_plan_bndry_nodes(self.handle)
+            self.lib.d4est_hip_plan_set_dirichlet_values(self.handle, _ptr(g), 1)
         else:
             g = np.ascontiguousarray(g, dtype=np.float64)
             self.lib.d4est_hip_plan_set_dirichlet_values(self.handle, g.ctypes.data_as(_vp), 0)

@@ -243,6 +243,7 @@ void d4est_hip_plan_destroy(d4est_hip_plan_t* plan) {
   (void)hipFree(plan->d_metric_affine);
   (void)hipFree(plan->d_nonaffine);
   (void)hipFree(plan->d_scratch);
+  d4est_hip::analytic_xyz_destroy(plan);
   d4est_hip::faces_destroy(plan);
   (void)hipFree(plan->d_work_p); (void)hipFree(plan->d_work_d); (void)hipFree(plan->d_work_r); (void)hipFree(plan->d_work_m); (void)hipFree(plan->d_lhs_c); (void)hipFree(plan->d_lhs_wjc);
   (void)hipFree(plan->d_lhs_block_off);
@@ -363,16 +364,57 @@ void d4est_hip_plan_set_mortar_geometry_brick(d4est_hip_plan_t* plan, const int*
   HIP_CHECK(hipFree(d_dq));
 }
 
+// params -> TreeMapParams; 0 on success, else non-zero with *why pointing at a message
+static int analytic_params_status(int geom_type, const double* params, d4est_hip::TreeMapParams* P, const char** why) {
+  if (d4est_hip::tree_map_num_trees(geom_type) == 0) { *why = "unknown geometry type"; return 1; }
+  if (!params) { *why = "params is NULL"; return 2; }
+  P->type = geom_type;
+  P->R0 = params[0];
+  P->R1 = params[1];
+  if (geom_type == D4EST_HIP_GEOM_CUBED_SPHERE_7TREE) {
+    if (!(params[0] > 0.) || !(params[1] > params[0])) { *why = "cubed_sphere_7tree needs params = {R0, R1 > R0, compactify_inner_shell}"; return 2; }
+    P->R2 = P->R1;
+    P->compactify = params[2] != 0.;
+    P->compactify_outer = 0;
+  } else {
+    if (!(params[0] > 0.) || !(params[1] > params[0]) || !(params[2] > params[1])) {
+      *why = "the 13-tree and holed spheres need params = {R0, R1 > R0, R2 > R1, compactify_outer_shell, compactify_inner_shell}";
+      return 2;
+    }
+    P->R2 = params[2];
+    P->compactify_outer = params[3] != 0.;
+    P->compactify = params[4] != 0.;
+    if (P->compactify && geom_type != D4EST_HIP_GEOM_CUBED_SPHERE_WITH_SPHERE_HOLE) {
+      *why = "compactify_inner_shell is not supported for cubed_sphere / cubed_sphere_with_cube_hole: the reference's map ignores the flag "
+             "while its analytic Jacobian honours it, so the factors would not belong to the map";
+      return 3;
+    }
+  }
+  P->Clength = P->R0 / std::sqrt(3.0);
+  return 0;
+}
+
 static d4est_hip::TreeMapParams analytic_params(int geom_type, const double* params, const char* who) {
-  if (geom_type != D4EST_HIP_GEOM_CUBED_SPHERE_7TREE) D4EST_HIP_ABORT("%s: unknown geometry type %d", who, geom_type);
-  if (!params || !(params[0] > 0.) || !(params[1] > params[0])) D4EST_HIP_ABORT("%s: cubed_sphere_7tree needs params = {R0, R1 > R0, compactify_inner_shell}", who);
   d4est_hip::TreeMapParams P;
-  P.type = geom_type;
-  P.R0 = params[0];
-  P.R1 = params[1];
-  P.compactify = params[2] != 0.;
-  P.Clength = P.R0 / std::sqrt(3.0);
+  const char* why = "";
+  if (analytic_params_status(geom_type, params, &P, &why)) D4EST_HIP_ABORT("%s: geometry type %d: %s", who, geom_type, why);
   return P;
+}
+
+int d4est_hip_tree_map(int geom_type, const double* params, int tree, const double* xi, double* x_out, double* dxdxi_out) {
+  d4est_hip::TreeMapParams P;
+  const char* why = "";
+  if (const int rc = analytic_params_status(geom_type, params, &P, &why)) return rc;
+  if (tree < 0 || tree >= d4est_hip::tree_map_num_trees(geom_type)) return 4;
+  if (!xi) return 5;
+  double X[3], D[3][3];
+  d4est_hip::tree_map_eval(P, tree, xi, X, D);
+  for (int i = 0; i < 3; ++i) {
+    if (x_out) x_out[i] = X[i];
+    if (dxdxi_out)
+      for (int j = 0; j < 3; ++j) dxdxi_out[3 * i + j] = D[i][j];
+  }
+  return 0;
 }
 
 static std::vector<d4est_hip::CellDesc> cells_from(int n, const int* tree, const int* q, const int* dq, int max_tree, const char* who) {
@@ -394,7 +436,7 @@ void d4est_hip_plan_set_geometry_analytic(d4est_hip_plan_t* plan, int geom_type,
   const d4est_hip::TreeMapParams P = analytic_params(geom_type, params, "plan_set_geometry_analytic");
   if (plan->n_elements > 0 && (!elem_tree || !elem_q || !elem_dq)) D4EST_HIP_ABORT("plan_set_geometry_analytic: NULL element array");
   if (!(root_len > 0.)) D4EST_HIP_ABORT("plan_set_geometry_analytic: root_len");
-  std::vector<d4est_hip::CellDesc> cells = cells_from(plan->n_elements, elem_tree, elem_q, elem_dq, 6, "plan_set_geometry_analytic");
+  std::vector<d4est_hip::CellDesc> cells = cells_from(plan->n_elements, elem_tree, elem_q, elem_dq, d4est_hip::tree_map_num_trees(geom_type) - 1, "plan_set_geometry_analytic");
   d4est_hip::CellDesc* d_cells = nullptr;
   HIP_CHECK(hipMalloc(&d_cells, std::max<size_t>(cells.size(), 1) * sizeof(d4est_hip::CellDesc)));
   if (!cells.empty()) HIP_CHECK(hipMemcpy(d_cells, cells.data(), cells.size() * sizeof(d4est_hip::CellDesc), hipMemcpyHostToDevice));
@@ -418,10 +460,22 @@ void d4est_hip_plan_set_mortar_geometry_analytic(d4est_hip_plan_t* plan, int geo
   if (plan->n_elements > 0 && (!elem_tree || !elem_q || !elem_dq)) D4EST_HIP_ABORT("plan_set_mortar_geometry_analytic: NULL element array");
   if (plan->n_ghost > 0 && (!ghost_tree || !ghost_q || !ghost_dq)) D4EST_HIP_ABORT("plan_set_mortar_geometry_analytic: NULL ghost array");
   if (!(root_len > 0.)) D4EST_HIP_ABORT("plan_set_mortar_geometry_analytic: root_len");
-  std::vector<d4est_hip::CellDesc> cells = cells_from(plan->n_elements, elem_tree, elem_q, elem_dq, 6, "plan_set_mortar_geometry_analytic");
-  std::vector<d4est_hip::CellDesc> gcells = cells_from(plan->n_ghost, ghost_tree, ghost_q, ghost_dq, 6, "plan_set_mortar_geometry_analytic");
+  std::vector<d4est_hip::CellDesc> cells = cells_from(plan->n_elements, elem_tree, elem_q, elem_dq, d4est_hip::tree_map_num_trees(geom_type) - 1, "plan_set_mortar_geometry_analytic");
+  std::vector<d4est_hip::CellDesc> gcells = cells_from(plan->n_ghost, ghost_tree, ghost_q, ghost_dq, d4est_hip::tree_map_num_trees(geom_type) - 1, "plan_set_mortar_geometry_analytic");
   d4est_hip::faces_set_geometry_analytic(plan, P, cells, gcells, root_len);
   HIP_CHECK(hipStreamSynchronize(plan->stream));
+}
+
+void d4est_hip_plan_compute_xyz_analytic(d4est_hip_plan_t* plan, int geom_type, const double* params, const int* elem_tree,
+                                         const int* elem_q, const int* elem_dq, double root_len, double* xyz_lobatto_dev,
+                                         double* xyz_quad_dev) {
+  check_plan(plan, "plan_compute_xyz_analytic");
+  const d4est_hip::TreeMapParams P = analytic_params(geom_type, params, "plan_compute_xyz_analytic");
+  if (plan->n_elements > 0 && (!elem_tree || !elem_q || !elem_dq)) D4EST_HIP_ABORT("plan_compute_xyz_analytic: NULL element array");
+  if (!(root_len > 0.)) D4EST_HIP_ABORT("plan_compute_xyz_analytic: root_len");
+  const std::vector<d4est_hip::CellDesc> cells =
+      cells_from(plan->n_elements, elem_tree, elem_q, elem_dq, d4est_hip::tree_map_num_trees(geom_type) - 1, "plan_compute_xyz_analytic");
+  d4est_hip::launch_analytic_xyz(plan, P, cells, root_len, xyz_lobatto_dev, xyz_quad_dev);
 }
 
 void d4est_hip_apply_stiffness_matrix(d4est_hip_plan_t* plan, const double* u_dev, double* Au_dev) {

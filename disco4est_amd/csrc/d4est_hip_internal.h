@@ -169,6 +169,8 @@ struct d4est_hip_plan {
   // allocated once on first use -- no per-call hipMalloc behind d4est's host double* API
   double* h_stage = nullptr;
   double* d_host[4] = {nullptr, nullptr, nullptr, nullptr};
+
+  void* xyz = nullptr;   // d4est_hip::XyzHost (d4est_hip_volume.hip): what plan_compute_xyz_analytic keeps between calls
 };
 
 namespace d4est_hip {
@@ -181,6 +183,10 @@ struct CellDesc;
 void launch_analytic_geometry(d4est_hip_plan* plan, const TreeMapParams& P, const CellDesc* d_cells, double root_len);
 void faces_set_geometry_analytic(d4est_hip_plan* plan, const TreeMapParams& P, const std::vector<CellDesc>& elem,
                                  const std::vector<CellDesc>& ghost, double root_len);
+// x | y | z of the analytic map at the Lobatto nodes and / or the quadrature nodes (either output may be null), on the plan's stream
+void launch_analytic_xyz(d4est_hip_plan* plan, const TreeMapParams& P, const std::vector<CellDesc>& cells, double root_len,
+                         double* xyz_lobatto, double* xyz_quad);
+void analytic_xyz_destroy(d4est_hip_plan* plan);
 
 // d4est_hip_volume.hip
 void launch_metric_precombine(d4est_hip_plan* plan, const double* d_J, const double* d_rst);

@@ -2051,6 +2051,96 @@ void launch_analytic_geometry(d4est_hip_plan* plan, const TreeMapParams& P, cons
   }
 }
 
+// Node coordinates of an analytic tree map (d4est_factors->xyz / ->xyz_quad, src/Mesh/d4est_mesh.c:2560-2636): one thread per node
+// of one degree bucket; `nodes` are the bucket's Nn 1-D reference nodes, s_list the elements' offsets in the node numbering written
+// (nodal_stride or quad_stride), out = x[total] | y[total] | z[total].
+__global__ __launch_bounds__(256) void analytic_xyz_kernel(const int* __restrict__ elem_ids, const int* __restrict__ s_list, int n_bucket,
+                                                           int Nn, const double* __restrict__ nodes, const CellDesc* __restrict__ cells,
+                                                           TreeMapParams P, double root_len, size_t total, double* __restrict__ out) {
+  const int N3 = Nn * Nn * Nn;
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long long)n_bucket * N3) return;
+  const int ei = (int)(gid / N3), n = (int)(gid % N3);
+  const CellDesc cell = cells[elem_ids[ei]];
+  const double r[3] = {nodes[n % Nn], nodes[(n / Nn) % Nn], nodes[n / (Nn * Nn)]};
+  double x[3];
+  cell_x(P, cell, root_len, r, x);
+  const size_t at = (size_t)s_list[ei] + n;
+  out[at] = x[0];
+  out[total + at] = x[1];
+  out[2 * total + at] = x[2];
+}
+
+// what d4est_hip_plan_compute_xyz_analytic keeps between calls: the cell descriptions (pinned staging + device), the 1-D Lobatto and
+// quadrature nodes of every bucket (two rows of `stride` per bucket) and the event that says the staging buffer is free again
+struct XyzHost {
+  CellDesc* h_cells = nullptr;
+  CellDesc* d_cells = nullptr;
+  double* d_nodes = nullptr;
+  int stride = 0;
+  hipEvent_t copied = nullptr;
+};
+
+void launch_analytic_xyz(d4est_hip_plan* plan, const TreeMapParams& P, const std::vector<CellDesc>& cells, double root_len,
+                         double* xyz_lobatto, double* xyz_quad) {
+  XyzHost* xh = static_cast<XyzHost*>(plan->xyz);
+  if (!xh) {
+    xh = new XyzHost;
+    plan->xyz = xh;
+    const size_t nc = std::max<size_t>(cells.size(), 1);
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&xh->h_cells), nc * sizeof(CellDesc)));
+    HIP_CHECK(hipMalloc(&xh->d_cells, nc * sizeof(CellDesc)));
+    HIP_CHECK(hipEventCreateWithFlags(&xh->copied, hipEventDisableTiming));
+    for (const Bucket& bk : plan->buckets) xh->stride = std::max(xh->stride, std::max(bk.N, bk.NQ));
+    const size_t nb = plan->buckets.size();
+    std::vector<double> tab(std::max<size_t>(2 * nb * xh->stride, 1), 0.0);
+    for (size_t bi = 0; bi < nb; ++bi) {
+      const Bucket& bk = plan->buckets[bi];
+      std::vector<double> x, w;
+      Tables1D::lobatto(bk.deg, x, w);
+      std::copy(x.begin(), x.end(), tab.begin() + (2 * bi) * xh->stride);
+      if (plan->quad_type == QUAD_LEGENDRE) Tables1D::gauss(bk.deg_quad, x, w);
+      else Tables1D::lobatto(bk.deg_quad, x, w);
+      std::copy(x.begin(), x.end(), tab.begin() + (2 * bi + 1) * xh->stride);
+    }
+    HIP_CHECK(hipMalloc(&xh->d_nodes, tab.size() * sizeof(double)));
+    HIP_CHECK(hipMemcpy(xh->d_nodes, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+  } else {
+    HIP_CHECK(hipEventSynchronize(xh->copied));   // the previous call's copy has left the staging buffer
+  }
+  if (!cells.empty()) {
+    std::copy(cells.begin(), cells.end(), xh->h_cells);
+    HIP_CHECK(hipMemcpyAsync(xh->d_cells, xh->h_cells, cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice, plan->stream));
+  }
+  HIP_CHECK(hipEventRecord(xh->copied, plan->stream));
+  for (size_t bi = 0; bi < plan->buckets.size(); ++bi) {
+    const Bucket& bk = plan->buckets[bi];
+    if (bk.n_elem == 0) continue;
+    for (int which = 0; which < 2; ++which) {
+      double* out = which ? xyz_quad : xyz_lobatto;
+      if (!out) continue;
+      const int Nn = which ? bk.NQ : bk.N;
+      const long long threads = (long long)bk.n_elem * Nn * Nn * Nn;
+      hipLaunchKernelGGL(analytic_xyz_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, plan->stream,
+                         plan->d_elem_ids + bk.elem_offset, (which ? plan->d_qs_list : plan->d_ns_list) + bk.elem_offset, bk.n_elem, Nn,
+                         xh->d_nodes + (2 * bi + which) * xh->stride, xh->d_cells, P, root_len,
+                         (size_t)(which ? plan->local_nodes_quad : plan->local_nodes), out);
+    }
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+void analytic_xyz_destroy(d4est_hip_plan* plan) {
+  XyzHost* xh = static_cast<XyzHost*>(plan->xyz);
+  if (!xh) return;
+  (void)hipHostFree(xh->h_cells);
+  (void)hipFree(xh->d_cells);
+  (void)hipFree(xh->d_nodes);
+  (void)hipEventDestroy(xh->copied);
+  delete xh;
+  plan->xyz = nullptr;
+}
+
 // d4est_operators_apply_slicer / _apply_lift (src/dGMath/d4est_operators.c:1521-1582, :1454-1519), batched: the trace of a volume
 // field on face f of every element (N^2 values per element, face axes in increasing order, first axis fastest) and its inverse
 // scatter (zero elsewhere).  Face vectors are element-ordered with stride sum_{e' < e} N_{e'}^2.

@@ -275,6 +275,127 @@ def cubed_sphere_7tree_connectivity():
     return Connectivity(d["tree_to_tree"], d["tree_to_face"])
 
 
+def _shell_radius(Ra, Rb, compactify, c):
+    """R(c) of a shell between Ra (c = 1) and Rb (c = 2) and dR/dc; compactified: R = m / (c - t)"""
+    if compactify:
+        m = 1.0 / (1.0 / Rb - 1.0 / Ra)
+        t = (Ra - 2.0 * Rb) / (Ra - Rb)
+        return m / (c - t), -m / (c - t) ** 2
+    return Ra * (2.0 - c) + Rb * (c - 1.0), np.full_like(c, Rb - Ra)
+
+
+def _plain_wedge(Ra, Rb, compactify, xi):
+    """the equiangular wedge of a shell: x = tan(pi a/4), y = tan(pi b/4), q = R(c) / sqrt(x^2 + y^2 + 1); returns (q x, q y, q) and
+    their gradients with respect to xi, in the layout of CubedSphere7Map._wedge"""
+    a, b, c = 2 * xi[:, 0] - 1, 2 * xi[:, 1] - 1, xi[:, 2] + 1
+    R, dR = _shell_radius(Ra, Rb, compactify, c)
+    x, y = np.tan(a * np.pi / 4), np.tan(b * np.pi / 4)
+    dx, dy = (np.pi / 4) * (1 + x * x), (np.pi / 4) * (1 + y * y)
+    S = x * x + y * y + 1.0
+    q = R / np.sqrt(S)
+    h = -R * S ** -1.5
+    dq = [h * x * dx, h * y * dy, dR / np.sqrt(S)]          # with respect to (a, b, c)
+    sc = [2.0, 2.0, 1.0]
+    qx = [(dq[0] * x + q * dx) * sc[0], dq[1] * x * sc[1], dq[2] * x * sc[2]]
+    qy = [dq[0] * y * sc[0], (dq[1] * y + q * dy) * sc[1], dq[2] * y * sc[2]]
+    qq = [dq[k] * sc[k] for k in range(3)]
+    return q * x, q * y, q, qx, qy, qq
+
+
+class _ShellsMap:
+    """wedges 0..5 on the outer shell (R1, R2), 6..11 on the inner shell (R0, R1), optionally the centre cube as tree 12; the
+    wedge index modulo 6 picks the axis permutation of CubedSphere7Map"""
+    GEOM_TYPE = None
+    num_trees = 12
+
+    def _inner(self, xi):
+        raise NotImplementedError
+
+    def _wedge(self, tree, xi):
+        return _plain_wedge(self.R1, self.R2, self.compactify_outer, xi) if tree < 6 else self._inner(xi)
+
+    def x(self, tree, xi):
+        assert 0 <= tree < self.num_trees
+        if tree == 12:
+            return (2 * xi - 1) * self.Clength
+        qx, qy, q, _, _, _ = self._wedge(tree, xi)
+        comp = (qx, qy, q)
+        return np.stack([s * comp[i] for (i, s) in CubedSphere7Map._PICK[tree % 6]], axis=1)
+
+    def jacobian(self, tree, xi):
+        assert 0 <= tree < self.num_trees
+        if tree == 12:
+            return np.broadcast_to(2 * self.Clength * np.eye(3), (xi.shape[0], 3, 3)).copy()
+        _, _, _, dqx, dqy, dq = self._wedge(tree, xi)
+        comp = (dqx, dqy, dq)
+        D = np.zeros((xi.shape[0], 3, 3))
+        for row, (i, s) in enumerate(CubedSphere7Map._PICK[tree % 6]):
+            for k in range(3):
+                D[:, row, k] = s * comp[i][k]
+        return D
+
+    @property
+    def params(self):
+        """the params array of d4est_hip_plan_set_geometry_analytic for this map"""
+        return (self.R0, self.R1, self.R2, float(self.compactify_outer), float(self.compactify_inner))
+
+
+class CubedSphere13Map(_ShellsMap):
+    """The reference's 13-tree cubed sphere, [geometry] name = cubed_sphere (d4est_geometry_cubed_sphere_X,
+    src/Geometry/d4est_geometry_cubed_sphere.c:316-403): outer wedges 0..5 equiangular on (R1, R2) -- optionally compactified,
+    R = m / (c - t) --, inner wedges 6..11 the blended form of the 7-tree map on (R0, R1), tree 12 the centre cube.  There is no
+    compactify_inner: the reference's X ignores that flag on these trees while its DX honours it (include/d4est_hip.h)."""
+    GEOM_TYPE = 2
+    num_trees = 13
+
+    def __init__(self, R0, R1, R2, compactify_outer=False):
+        self.R0, self.R1, self.R2 = float(R0), float(R1), float(R2)
+        self.compactify_outer, self.compactify_inner = bool(compactify_outer), False
+        self.Clength = self.R0 / np.sqrt(3.0)
+        self._blend = CubedSphere7Map(R0, R1, False)
+
+    def _inner(self, xi):
+        return self._blend._wedge(xi)
+
+
+class SphereWithHoleMap(_ShellsMap):
+    """The reference's twelve-wedge spheres with a hole: cubed_sphere_with_sphere_hole (both shells equiangular, each with its own
+    compactification flag; d4est_geometry_cubed_sphere_with_sphere_hole_X, :407-497) or, with cube_hole=True,
+    cubed_sphere_with_cube_hole (the 13-tree map without its cube, :2243-2260; no compactify_inner)."""
+
+    def __init__(self, R0, R1, R2, compactify_outer=False, compactify_inner=False, cube_hole=False):
+        assert not (cube_hole and compactify_inner), "cubed_sphere_with_cube_hole has no compactified inner shell"
+        self.R0, self.R1, self.R2 = float(R0), float(R1), float(R2)
+        self.compactify_outer, self.compactify_inner, self.cube_hole = bool(compactify_outer), bool(compactify_inner), bool(cube_hole)
+        self.GEOM_TYPE = 4 if cube_hole else 3
+        self.Clength = self.R0 / np.sqrt(3.0)
+        self._blend = CubedSphere7Map(R0, R1, False)
+
+    def _inner(self, xi):
+        if self.cube_hole:
+            return self._blend._wedge(xi)
+        return _plain_wedge(self.R0, self.R1, self.compactify_inner, xi)
+
+
+def _golden_connectivity(name):
+    import json
+    import os
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", name)
+    with open(path) as fh:
+        d = json.load(fh)
+    return Connectivity(d["tree_to_tree"], d["tree_to_face"], d["vertices"], d["tree_to_vertex"])
+
+
+def cubed_sphere_13tree_connectivity():
+    """p8est_connectivity_new_sphere (p4est 2.8) from the committed fixture written by tests/golden/make_sphere_connectivities.py"""
+    return _golden_connectivity("cubed_sphere_13tree_connectivity.json")
+
+
+def sphere_with_hole_connectivity():
+    """d4est_connectivity_new_sphere_with_hole (src/Geometry/d4est_connectivity_cubed_sphere.c:109-181) from the committed fixture"""
+    return _golden_connectivity("sphere_with_hole_connectivity.json")
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 class ForestMesh:
     """Forest of trees at a uniform base ``level`` with optional ONE level of local refinement (``refine``: bool over the

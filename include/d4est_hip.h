@@ -141,16 +141,44 @@ void d4est_hip_plan_set_mortar_geometry_brick(d4est_hip_plan_t* plan, const int*
  * and 24 doubles per mortar node.  geom_type / params:
  *   D4EST_HIP_GEOM_CUBED_SPHERE_7TREE  [geometry] name = cubed_sphere_7tree (src/Geometry/d4est_geometry_cubed_sphere.c:498-580,
  *                                      :1884-1899): params = {R0, R1, compactify_inner_shell}; trees 0..5 wedges, 6 the centre cube
+ *   D4EST_HIP_GEOM_CUBED_SPHERE        [geometry] name = cubed_sphere (:316-403, :2070-2100): the 13 trees of
+ *                                      p8est_connectivity_new_sphere -- 0..5 outer wedges on (R1, R2), 6..11 inner wedges on
+ *                                      (R0, R1), 12 the centre cube
+ *   D4EST_HIP_GEOM_CUBED_SPHERE_WITH_SPHERE_HOLE  name = cubed_sphere_with_sphere_hole (:407-497): the 12 trees of
+ *                                      d4est_connectivity_new_sphere_with_hole, both shells equiangular
+ *   D4EST_HIP_GEOM_CUBED_SPHERE_WITH_CUBE_HOLE    name = cubed_sphere_with_cube_hole (:2243-2260): the 13-tree map on those 12 trees
+ *     params of these three = {R0, R1 > R0, R2 > R1, compactify_outer_shell, compactify_inner_shell} (flags: zero / non-zero).
+ *     compactify_inner_shell != 0 is REJECTED for cubed_sphere and cubed_sphere_with_cube_hole (abort; d4est_hip_tree_map returns
+ *     non-zero): the reference's map of those trees ignores the flag while its analytic Jacobian honours it, so the factors would
+ *     not be the Jacobian of the map.  cubed_sphere_with_sphere_hole takes both flags.
  * The mortar variant is called where d4est_hip_plan_set_mortar_geometry would be (after plan_set_hanging / plan_set_faces /
  * plan_set_sipg), needs the same three arrays for the ghost elements (order of ghost_deg), follows faces between trees through
  * side_reorder / side_orientation and hanging faces through the half-size virtual children of the big element
  * (src/Mesh/d4est_mortars.c:419-468); face_h_type FACE_H_EQ_J_DIV_SJ_QUAD. */
 #define D4EST_HIP_GEOM_CUBED_SPHERE_7TREE 1
+#define D4EST_HIP_GEOM_CUBED_SPHERE 2
+#define D4EST_HIP_GEOM_CUBED_SPHERE_WITH_SPHERE_HOLE 3
+#define D4EST_HIP_GEOM_CUBED_SPHERE_WITH_CUBE_HOLE 4
 void d4est_hip_plan_set_geometry_analytic(d4est_hip_plan_t* plan, int geom_type, const double* params, const int* elem_tree,
                                           const int* elem_q, const int* elem_dq, double root_len);
 void d4est_hip_plan_set_mortar_geometry_analytic(d4est_hip_plan_t* plan, int geom_type, const double* params, const int* elem_tree,
                                                  const int* elem_q, const int* elem_dq, const int* ghost_tree, const int* ghost_q,
                                                  const int* ghost_dq, double root_len);
+
+/* Node coordinates of the same maps on the device: xyz_lobatto_dev = x[local_nodes] | y | z at every element's Lobatto nodes
+ * (d4est_factors->xyz, what d4est_hip_plan_set_geometry_numerical takes), xyz_quad_dev = x[local_nodes_quad] | y | z at its quadrature
+ * nodes (Gauss or Lobatto by the plan's quad_type; d4est_factors->xyz_quad) -- for the right-hand side, the coefficient of a
+ * linearised term, boundary data.  Either pointer may be NULL.  One thread per node on the plan's stream, no host synchronisation;
+ * the plan allocates its small staging on the first call and nothing afterwards.  Boundary-face coordinates need no entry of their
+ * own: d4est_hip_plan_boundary_gather of each of the three Lobatto components gives them in the order
+ * d4est_hip_plan_set_dirichlet_values expects.  Aborts like plan_set_geometry_analytic on a bad type, tree or flag. */
+void d4est_hip_plan_compute_xyz_analytic(d4est_hip_plan_t* plan, int geom_type, const double* params, const int* elem_tree,
+                                         const int* elem_q, const int* elem_dq, double root_len, double* xyz_lobatto_dev,
+                                         double* xyz_quad_dev);
+/* The same map evaluated on the HOST (the host side of the inline functions the kernels call; no HIP call, works without a GPU):
+ * x_out[3] = x(tree, xi) and dxdxi_out[9] = d x_i / d xi_j (row-major) at tree coordinates xi[3] in [0,1]^3; either output may be
+ * NULL.  Returns 0, or non-zero -- without aborting -- for an unknown type, bad radii, a rejected flag or a tree out of range. */
+int d4est_hip_tree_map(int geom_type, const double* params, int tree, const double* xi, double* x_out, double* dxdxi_out);
 
 /* ---- volume kernels (device vectors of local_nodes doubles) ---------------------- */
 /* Au = K u : replaces d4est_laplacian_apply_stiffness_matrix (src/dGMath/d4est_laplacian.c:198-234)
