@@ -64,6 +64,11 @@ SIGNATURES = {
     "d4est_hip_plan_compute_xyz_analytic": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
     "d4est_hip_tree_map": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp]),
     "d4est_hip_plan_set_mortar_geometry_brick": (None, [_vp, _vp, ctypes.c_double, _vp]),
+    "d4est_hip_plan_set_h_types": (None, [_vp, ctypes.c_int, ctypes.c_int]),
+    "d4est_hip_plan_compute_size_parameters_brick": (None, [_vp, _vp, _vp, ctypes.c_double, _vp]),
+    "d4est_hip_plan_compute_size_parameters_analytic": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double]),
+    "d4est_hip_plan_compute_diameters": (None, [_vp, _vp]),
+    "d4est_hip_plan_size_parameter": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     "d4est_hip_transfer_create": (_vp, [ctypes.c_int, _vp, _vp, _vp]),
     "d4est_hip_transfer_destroy": (None, [_vp]),
     "d4est_hip_transfer_set_stream": (None, [_vp, _vp]),
@@ -196,6 +201,16 @@ SIGNATURES = {
     "d4est_hip_amr_describe": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int]),
     "d4est_hip_amr_advance": (None, [_vp]),
 }
+
+# [mesh_parameters] face_h_type / volume_h_type by the reference's names (d4est_mesh_face_h_t / d4est_mesh_volume_h_t) and the size
+# parameter arrays (D4EST_HIP_SIZE_*)
+FACE_H = {
+    "FACE_H_EQ_J_DIV_SJ_QUAD": 0, "FACE_H_EQ_J_DIV_SJ_MIN_LOBATTO": 1, "FACE_H_EQ_J_DIV_SJ_MEAN_LOBATTO": 2,
+    "FACE_H_EQ_J_DIV_SJ_MAX_LOBATTO": 3, "FACE_H_EQ_TREE_H": 4, "FACE_H_EQ_VOLUME_DIV_AREA": 5, "FACE_H_EQ_FACE_DIAM": 6,
+    "FACE_H_EQ_TOTAL_VOLUME_DIV_TOTAL_AREA": 7,
+}
+VOL_H = {"VOL_H_EQ_DIAM": 0, "VOL_H_EQ_CUBE_APPROX": 1}
+SIZE_PARAMETER = {"diam_volume": 0, "volume": 1, "area": 2, "diam_face": 3, "j_div_sj_min": 4, "j_div_sj_mean": 5, "j_div_sj_max": 6}
 
 TABLE = {
     "lobatto_nodes": 0, "lobatto_weights": 1, "gauss_nodes": 2, "gauss_weights": 3,
@@ -389,6 +404,65 @@ class Plan:
                                                      _ptr(xyz_lobatto) if xyz_lobatto is not None else None,
                                                      _ptr(xyz_quad) if xyz_quad is not None else None)
 
+    # ---- element size parameters (csrc/d4est_hip_sizes.hip) ----
+    def set_h_types(self, face_h_type=0, volume_h_type=0):
+        """[mesh_parameters] face_h_type / volume_h_type: ids or the reference's names (capi.FACE_H / capi.VOL_H); before set_faces"""
+        f = FACE_H[face_h_type] if isinstance(face_h_type, str) else int(face_h_type)
+        v = VOL_H[volume_h_type] if isinstance(volume_h_type, str) else int(volume_h_type)
+        self.lib.d4est_hip_plan_set_h_types(self.handle, f, v)
+
+    def compute_size_parameters(self, brick=None, analytic=None):
+        """d4est_mesh_init_element_size_parameters on the device, stream-ordered.  brick = (elem_dq, root_len, extents[, ghost_dq]) or
+        analytic = (geom_type, params, tree, q, dq, root_len[, ghost]) with ghost = (tree, q, dq) of the ghost elements or None, as
+        set_faces takes them; ghost elements need set_faces first.  The arrays: size_parameter(name)"""
+        assert (brick is None) != (analytic is None), "one of brick / analytic"
+        if brick is not None:
+            dq = _iarr(brick[0])
+            ex = np.ascontiguousarray(brick[2], dtype=np.float64)
+            gdq = _iarr(brick[3]) if len(brick) > 3 and brick[3] is not None else None
+            assert len(dq[0]) == self.n_elements
+            self.lib.d4est_hip_plan_compute_size_parameters_brick(self.handle, dq[1], gdq[1] if gdq else None, float(brick[1]),
+                                                                  ex.ctypes.data_as(_vp))
+            return
+        geom_type, params, tree, q, dq, root_len = analytic[:6]
+        ghost = analytic[6] if len(analytic) > 6 else None
+        pr = np.zeros(5)
+        pv = np.asarray(params, dtype=np.float64).reshape(-1)
+        pr[:pv.size] = pv
+        t, qq, d = _iarr(tree), _iarr(np.asarray(q).reshape(-1)), _iarr(dq)
+        assert len(t[0]) == self.n_elements and len(d[0]) == self.n_elements and len(qq[0]) == 3 * self.n_elements
+        g = (_iarr(ghost[0]), _iarr(np.asarray(ghost[1]).reshape(-1)), _iarr(ghost[2])) if ghost is not None else None
+        self.lib.d4est_hip_plan_compute_size_parameters_analytic(self.handle, int(geom_type), pr.ctypes.data_as(_vp), t[1], qq[1], d[1],
+                                                                 g[0][1] if g else None, g[1][1] if g else None, g[2][1] if g else None,
+                                                                 float(root_len))
+
+    def compute_diameters(self, xyz):
+        """diam_volume and diam_face of the local elements from their node coordinates alone: xyz = one float64 CUDA tensor of
+        3 * local_nodes entries, x | y | z at the Lobatto nodes (any geometry).  Stream-ordered."""
+        assert xyz.numel() == 3 * self.local_nodes
+        self.lib.d4est_hip_plan_compute_diameters(self.handle, _ptr(xyz))
+
+    def size_parameter(self, name, device=None):
+        """the plan-owned array `name` (capi.SIZE_PARAMETER: diam_volume, volume: one per element; area, diam_face, j_div_sj_min / _mean /
+        _max: six per element; ghost elements after the local ones) as a torch tensor VIEW of the plan's memory -- valid while the plan
+        lives, overwritten by the next compute_* call; None when it has not been computed"""
+        import torch
+        ptr, cnt = ctypes.c_void_p(), ctypes.c_longlong()
+        if not self.lib.d4est_hip_plan_size_parameter(self.handle, SIZE_PARAMETER[name] if isinstance(name, str) else int(name),
+                                                      ctypes.byref(ptr), ctypes.byref(cnt)):
+            return None
+        n = int(cnt.value)
+        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        if n == 0:
+            return torch.empty(0, dtype=torch.float64, device=dev)
+
+        class _View:   # the CUDA array interface: torch.as_tensor wraps the memory without copying
+            __cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (int(ptr.value), False), "version": 2, "strides": None}
+
+        t = torch.as_tensor(_View(), device=dev)
+        t._d4est_hip_plan = self   # (the view keeps the plan object alive)
+        return t
+
     def apply_weighted_mass_matrix(self, u, coeff_quad, out):
         assert u.numel() == self.local_nodes and out.numel() == self.local_nodes
         assert coeff_quad.numel() == self.local_nodes_quad
@@ -457,7 +531,8 @@ class Plan:
     def estimator_bi(self, u, residual, diam, eta2, terms=None, ghost_trace=None, g=None):
         """eta2[n_elements] (and terms[4 n_elements], term-major) of d4est_estimator_bi_compute.  u, residual: CUDA tensors of
         local_nodes doubles; eta2 / terms / ghost_trace: CUDA tensors; diam (n_elements) and g (Dirichlet data on the boundary Lobatto
-        face nodes, set_dirichlet_values' layout; None = 0): numpy arrays or CUDA tensors"""
+        face nodes, set_dirichlet_values' layout; None = 0): numpy arrays or CUDA tensors; diam None: the plan's own diam_volume
+        (compute_size_parameters / compute_diameters)"""
         import torch
         assert u.numel() == self.local_nodes and residual.numel() == self.local_nodes
         assert eta2.numel() == self.n_elements and (terms is None or terms.numel() == 4 * self.n_elements)
@@ -468,14 +543,14 @@ class Plan:
                 return a
             return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
 
-        d_diam, d_g = on_dev(diam), on_dev(g)
-        assert d_diam.numel() == self.n_elements
+        d_diam, d_g = on_dev(diam), on_dev(g)   # diam None: the plan's own diam_volume (compute_size_parameters / compute_diameters)
+        assert d_diam is None or d_diam.numel() == self.n_elements
         if ghost_trace is not None:
             assert ghost_trace.numel() == self.ghost_trace_size
         self.lib.d4est_hip_estimator_bi(self.handle, _ptr(u), _ptr(ghost_trace) if ghost_trace is not None else None, _ptr(residual),
-                                        _ptr(d_diam), _ptr(d_g) if d_g is not None else None, _ptr(eta2),
+                                        _ptr(d_diam) if d_diam is not None else None, _ptr(d_g) if d_g is not None else None, _ptr(eta2),
                                         _ptr(terms) if terms is not None else None)
-        if not isinstance(diam, torch.Tensor) or (g is not None and not isinstance(g, torch.Tensor)):
+        if (diam is not None and not isinstance(diam, torch.Tensor)) or (g is not None and not isinstance(g, torch.Tensor)):
             torch.cuda.current_stream(dev).synchronize() if self.torch_stream is None else self.torch_stream.synchronize()
             self.lib.d4est_hip_device_synchronize()   # (the uploaded copies must outlive the launches)
 

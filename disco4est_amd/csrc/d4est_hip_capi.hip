@@ -244,6 +244,7 @@ void d4est_hip_plan_destroy(d4est_hip_plan_t* plan) {
   (void)hipFree(plan->d_nonaffine);
   (void)hipFree(plan->d_scratch);
   d4est_hip::analytic_xyz_destroy(plan);
+  d4est_hip::sizes_destroy(plan);
   d4est_hip::faces_destroy(plan);
   (void)hipFree(plan->d_work_p); (void)hipFree(plan->d_work_d); (void)hipFree(plan->d_work_r); (void)hipFree(plan->d_work_m); (void)hipFree(plan->d_lhs_c); (void)hipFree(plan->d_lhs_wjc);
   (void)hipFree(plan->d_lhs_block_off);
@@ -359,7 +360,7 @@ void d4est_hip_plan_set_mortar_geometry_brick(d4est_hip_plan_t* plan, const int*
   drop_graph(plan);
   if (!plan->has_faces) D4EST_HIP_ABORT("plan_set_mortar_geometry_brick: call plan_set_faces first");
   int* d_dq = upload_elem_dq(plan, elem_dq, root_len, extents, "plan_set_mortar_geometry_brick");
-  d4est_hip::faces_set_geometry_brick(plan, d_dq, root_len, extents);
+  d4est_hip::faces_set_geometry_brick(plan, d_dq, elem_dq, root_len, extents);
   HIP_CHECK(hipStreamSynchronize(plan->stream));
   HIP_CHECK(hipFree(d_dq));
 }
@@ -476,6 +477,65 @@ void d4est_hip_plan_compute_xyz_analytic(d4est_hip_plan_t* plan, int geom_type, 
   const std::vector<d4est_hip::CellDesc> cells =
       cells_from(plan->n_elements, elem_tree, elem_q, elem_dq, d4est_hip::tree_map_num_trees(geom_type) - 1, "plan_compute_xyz_analytic");
   d4est_hip::launch_analytic_xyz(plan, P, cells, root_len, xyz_lobatto_dev, xyz_quad_dev);
+}
+
+void d4est_hip_plan_set_h_types(d4est_hip_plan_t* plan, int face_h_type, int volume_h_type) {
+  check_plan(plan, "plan_set_h_types");
+  drop_graph(plan);
+  if (face_h_type < 0 || face_h_type > D4EST_HIP_FACE_H_EQ_TOTAL_VOLUME_DIV_TOTAL_AREA) D4EST_HIP_ABORT("plan_set_h_types: unknown face_h_type %d", face_h_type);
+  if (volume_h_type < 0 || volume_h_type > D4EST_HIP_VOL_H_EQ_CUBE_APPROX) D4EST_HIP_ABORT("plan_set_h_types: unknown volume_h_type %d", volume_h_type);
+  if (plan->has_face_geometry) D4EST_HIP_ABORT("plan_set_h_types: call before plan_set_mortar_geometry (hm and hp are filled there)");
+  plan->face_h_type = face_h_type;
+  plan->volume_h_type = volume_h_type;
+}
+
+void d4est_hip_plan_compute_size_parameters_brick(d4est_hip_plan_t* plan, const int* elem_dq, const int* ghost_dq, double root_len,
+                                                  const double* extents) {
+  check_plan(plan, "plan_compute_size_parameters_brick");
+  if (plan->n_elements > 0 && !elem_dq) D4EST_HIP_ABORT("plan_compute_size_parameters_brick: elem_dq is NULL");
+  if (!extents || !(root_len > 0.) || !(extents[1] > extents[0]) || !(extents[3] > extents[2]) || !(extents[5] > extents[4]))
+    D4EST_HIP_ABORT("plan_compute_size_parameters_brick: bad brick extents / root length");
+  const int ng = ghost_dq ? plan->n_ghost : 0;
+  std::vector<d4est_hip::CellDesc> cells((size_t)plan->n_elements + ng);
+  for (size_t i = 0; i < cells.size(); ++i) {
+    const int dq = (int)i < plan->n_elements ? elem_dq[i] : ghost_dq[i - plan->n_elements];
+    if (dq <= 0) D4EST_HIP_ABORT("plan_compute_size_parameters_brick: element %zu has dq %d", i, dq);
+    cells[i] = d4est_hip::CellDesc{0, {0, 0, 0}, dq, 0};
+  }
+  d4est_hip::sizes_compute(plan, nullptr, extents, cells, ng, root_len);
+}
+
+void d4est_hip_plan_compute_size_parameters_analytic(d4est_hip_plan_t* plan, int geom_type, const double* params, const int* elem_tree,
+                                                     const int* elem_q, const int* elem_dq, const int* ghost_tree, const int* ghost_q,
+                                                     const int* ghost_dq, double root_len) {
+  const char* who = "plan_compute_size_parameters_analytic";
+  check_plan(plan, who);
+  const d4est_hip::TreeMapParams P = analytic_params(geom_type, params, who);
+  if (plan->n_elements > 0 && (!elem_tree || !elem_q || !elem_dq)) D4EST_HIP_ABORT("%s: NULL element array", who);
+  if (!(root_len > 0.)) D4EST_HIP_ABORT("%s: root_len", who);
+  const bool ghosts = ghost_tree || ghost_q || ghost_dq;
+  if (ghosts && (!ghost_tree || !ghost_q || !ghost_dq)) D4EST_HIP_ABORT("%s: all three ghost arrays or none", who);
+  const int ng = ghosts ? plan->n_ghost : 0;
+  const int max_tree = d4est_hip::tree_map_num_trees(geom_type) - 1;
+  std::vector<d4est_hip::CellDesc> cells = cells_from(plan->n_elements, elem_tree, elem_q, elem_dq, max_tree, who);
+  const std::vector<d4est_hip::CellDesc> gcells = cells_from(ng, ghost_tree, ghost_q, ghost_dq, max_tree, who);
+  cells.insert(cells.end(), gcells.begin(), gcells.end());
+  d4est_hip::sizes_compute(plan, &P, nullptr, cells, ng, root_len);
+}
+
+void d4est_hip_plan_compute_diameters(d4est_hip_plan_t* plan, const double* xyz_lobatto_dev) {
+  check_plan(plan, "plan_compute_diameters");
+  d4est_hip::sizes_compute_diameters(plan, xyz_lobatto_dev);
+}
+
+int d4est_hip_plan_size_parameter(const d4est_hip_plan_t* plan, int which, const double** array_dev, long long* count) {
+  check_plan(plan, "plan_size_parameter");
+  long long n = 0;
+  const double* a = d4est_hip::sizes_array(plan, which, &n);
+  if (!a) return 0;
+  if (array_dev) *array_dev = a;
+  if (count) *count = n;
+  return 1;
 }
 
 void d4est_hip_apply_stiffness_matrix(d4est_hip_plan_t* plan, const double* u_dev, double* Au_dev) {
@@ -629,6 +689,10 @@ void d4est_hip_estimator_bi(d4est_hip_plan_t* plan, const double* u_dev, const d
                             const double* diam_dev, const double* g_lobatto_dev, double* eta2_dev, double* terms_dev) {
   check_plan(plan, "estimator_bi");
   if (!plan->has_faces) D4EST_HIP_ABORT("estimator_bi: the plan has no faces (plan_set_faces)");
+  if (!diam_dev) {   // the plan's own diam_volume (d4est_hip_plan_compute_size_parameters_* / _compute_diameters)
+    diam_dev = d4est_hip::sizes_array(plan, D4EST_HIP_SIZE_DIAM_VOLUME, nullptr);
+    if (!diam_dev) D4EST_HIP_ABORT("estimator_bi: diam_dev is NULL and the plan's diam_volume has not been computed (plan_compute_size_parameters_* / plan_compute_diameters)");
+  }
   d4est_hip::estimator_compute(plan, u_dev, ghost_trace_dev, residual_dev, diam_dev, g_lobatto_dev, eta2_dev, terms_dev);
 }
 

@@ -709,7 +709,10 @@ double* d4est_estimator_bi_compute(p4est_t* p4est, d4est_elliptic_data_t* d, d4e
     if (!same_penalty(ids[i], plan_ids[i])) COMPAT_ABORT("%s: penalty function %d is id %d, the bound plan has id %d", who, i, ids[i], plan_ids[i]);
   if (pd.penalty_prefactor != plan_c) COMPAT_ABORT("%s: penalty_prefactor %g, the bound plan has %g", who, pd.penalty_prefactor, plan_c);
   auto dg = g_diam.find(p4est);
-  if (dg == g_diam.end()) COMPAT_ABORT("%s: no element diameters registered (d4est_hip_compat_bind_element_diameters)", who);
+  // no bound array: the plan's own diam_volume (d4est_hip_plan_compute_size_parameters_* / _compute_diameters); a bound array keeps precedence
+  if (dg == g_diam.end() && !d4est_hip_plan_size_parameter(plan, D4EST_HIP_SIZE_DIAM_VOLUME, nullptr, nullptr))
+    COMPAT_ABORT("%s: no element diameters: neither registered (d4est_hip_compat_bind_element_diameters) nor computed on the plan "
+                 "(d4est_hip_plan_compute_size_parameters_* / d4est_hip_plan_compute_diameters)", who);
   auto cr = g_coord.find(p4est);
   if (!u_bndry_fcn) COMPAT_ABORT("%s: u_bndry_fcn == NULL", who);
   if (cr == g_coord.end() || !cr->second.lob[0]) COMPAT_ABORT("%s: no Lobatto node coordinates registered (d4est_hip_compat_bind_coordinates)", who);
@@ -736,8 +739,8 @@ double* d4est_estimator_bi_compute(p4est_t* p4est, d4est_elliptic_data_t* d, d4e
   d4est_hip_memcpy_h2d(d_g, g.data(), sizeof(double) * (size_t)nb);
   d4est_hip_memcpy_h2d(d_u, d->u + (size_t)which_field * ln, vb);
   d4est_hip_memcpy_h2d(d_r, d->Au, vb);
-  d4est_hip_memcpy_h2d(d_diam, dg->second, sizeof(double) * (size_t)ne);
-  d4est_hip_estimator_bi(plan, d_u, nullptr, d_r, d_diam, nb > 0 ? d_g : nullptr, d_out, d_out + ne);
+  if (dg != g_diam.end()) d4est_hip_memcpy_h2d(d_diam, dg->second, sizeof(double) * (size_t)ne);
+  d4est_hip_estimator_bi(plan, d_u, nullptr, d_r, dg != g_diam.end() ? d_diam : nullptr, nb > 0 ? d_g : nullptr, d_out, d_out + ne);
   d4est_hip_plan_synchronize(plan);
   // the returned array: the caller frees it with P4EST_FREE = sc_free(p4est_package_id, .) -- allocate it with libsc where the process has it
   typedef void* (*sc_malloc_t)(int, size_t);

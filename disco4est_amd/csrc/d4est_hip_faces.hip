@@ -2922,7 +2922,70 @@ __global__ __launch_bounds__(64) void brick_mortar_hp_kernel(const HpMortar* __r
   }
 }
 
-void faces_set_geometry_brick(d4est_hip_plan* plan, const int* d_elem_dq, double root_len, const double* extents) {
+// The mortar faces of hm / hp with the elements whose size parameters d4est_mesh_calculate_mortar_h reads for them
+// (src/Mesh/d4est_mesh.c:689-856 as called at :629-644 and :1071-1103): (-) elements on f_m, (+) elements in (-) order on f_p; on a
+// hanging face the side of four gives each mortar face its own small element, the other side its one big element.
+// dq: p4est side length of the local elements, then of the ghost elements.
+static std::vector<MortarHUnit> mortar_h_units(d4est_hip_plan* plan, const std::vector<int>& dq, double root_len, const char* who) {
+  FaceHost& fh = g_face_host[plan];
+  const int ne = plan->n_elements, type = plan->face_h_type;
+  if ((type == D4EST_HIP_FACE_H_EQ_FACE_DIAM || type == D4EST_HIP_FACE_H_EQ_TOTAL_VOLUME_DIV_TOTAL_AREA) && plan->n_ghost > 0)
+    D4EST_HIP_ABORT("%s: face_h_type %d (%s) is not defined on a plan with ghost sides: the reference reads diam_face / area / volume without "
+                    "the ghost offset there (src/Mesh/d4est_mesh.c:801-802, :841)", who, type,
+                    type == D4EST_HIP_FACE_H_EQ_FACE_DIAM ? "FACE_H_EQ_FACE_DIAM" : "FACE_H_EQ_TOTAL_VOLUME_DIV_TOTAL_AREA");
+  auto idx = [&](int ref) {
+    if (ref == -1) D4EST_HIP_ABORT("%s: boundary reference on an interior side", who);
+    const int i = ref >= 0 ? ref : ne - (ref + 2);
+    if (i >= (int)dq.size()) D4EST_HIP_ABORT("%s: ghost element %d has no cell description", who, i - ne);
+    return i;
+  };
+  std::vector<MortarHUnit> units;
+  auto add = [&](int at, int T, int e, int f, int hang, size_t s, int i) {
+    MortarHUnit u{};
+    u.at = at; u.T = T;
+    u.one_m = e; u.f_m = f; u.n_m = 1; u.em[0] = e;
+    if (plan->side_nbr[s] == -1) {   // boundary: one h (:629-644)
+      u.one_p = e; u.f_p = f; u.n_p = 1; u.ep[0] = e;
+    } else {
+      u.f_p = plan->side_nbr_face[s];
+      if (hang == 0) {
+        u.one_p = idx(plan->side_nbr[s]); u.n_p = 1; u.ep[0] = u.one_p;
+      } else if (hang == 1) {        // (+) side: the four small elements in (-) order
+        u.n_p = 4;
+        for (int k = 0; k < 4; ++k) u.ep[k] = idx(plan->side_nbr4[4 * s + k]);
+        u.one_p = u.ep[i];
+      } else {                       // this element is one of the four (-) elements; (+) side: the big element
+        u.n_m = 4;
+        for (int k = 0; k < 4; ++k) u.em[k] = idx(plan->side_nbr4[4 * s + k]);
+        u.one_p = idx(plan->side_nbr[s]); u.n_p = 1; u.ep[0] = u.one_p;
+      }
+    }
+    u.tree_h_m = (double)dq[u.one_m] / root_len;
+    u.tree_h_p = (double)dq[u.one_p] / root_len;
+    units.push_back(u);
+  };
+  if (fh.hp) {
+    std::vector<HpMortar> rec((size_t)fh.n_rec);
+    std::vector<HpGeomSrc> gs((size_t)fh.n_rec);
+    if (fh.n_rec > 0) {
+      HIP_CHECK(hipMemcpy(rec.data(), fh.d_rec, rec.size() * sizeof(HpMortar), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(gs.data(), fh.d_gsrc, gs.size() * sizeof(HpGeomSrc), hipMemcpyDeviceToHost));
+    }
+    for (int e = 0; e < ne; ++e)
+      for (int f = 0; f < 6; ++f) {
+        const size_t s = 6 * (size_t)e + f;
+        for (int r = plan->side_first_rec[s]; r < plan->side_first_rec[s + 1]; ++r)
+          add(gs[r].S + gs[r].off, rec[r].NQ * rec[r].NQ, e, f, plan->side_hang[s], s, r - plan->side_first_rec[s]);
+      }
+  } else {
+    std::vector<SideDesc> sd(6 * (size_t)ne);
+    if (!sd.empty()) HIP_CHECK(hipMemcpy(sd.data(), plan->d_side_desc, sd.size() * sizeof(SideDesc), hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < sd.size(); ++s) add(sd[s].geom, sd[s].NQ * sd[s].NQ, (int)(s / 6), (int)(s % 6), 0, s, 0);
+  }
+  return units;
+}
+
+void faces_set_geometry_brick(d4est_hip_plan* plan, const int* d_elem_dq, const int* h_elem_dq, double root_len, const double* extents) {
   FaceHost& fh = g_face_host[plan];
   const size_t T = std::max<size_t>((size_t)plan->total_mortar_nodes, 1);
   double* a[6];
@@ -2942,6 +3005,25 @@ void faces_set_geometry_brick(d4est_hip_plan* plan, const int* d_elem_dq, double
                        n_sides, d_elem_dq, root_len, ex, ey, ez, a[0], a[1], a[2], a[3], a[4], a[5]);
   }
   HIP_CHECK(hipGetLastError());
+  if (plan->face_h_type != D4EST_HIP_FACE_H_EQ_J_DIV_SJ_QUAD) {
+    // a ghost element's size follows from the side that refers to it (2:1 balance): the same, half (the small elements of a big
+    // side) or twice (the big element of a small side) the local element's
+    const int ne = plan->n_elements, ng = plan->n_ghost;
+    std::vector<int> dq(h_elem_dq, h_elem_dq + ne);
+    dq.resize((size_t)ne + ng, ne > 0 ? h_elem_dq[0] : 1);
+    auto set = [&](int ref, int v) { if (ref <= -2 && -(ref + 2) < ng) dq[(size_t)ne - (ref + 2)] = v; };
+    for (size_t s = 0; s < 6 * (size_t)ne; ++s) {
+      const int hang = plan->side_hang.empty() ? 0 : plan->side_hang[s], own = h_elem_dq[s / 6];
+      set(plan->side_nbr[s], hang == 2 ? 2 * own : hang == 1 ? own / 2 : own);
+      if (hang != 0)
+        for (int k = 0; k < 4; ++k) set(plan->side_nbr4[4 * s + k], hang == 1 ? own / 2 : own);
+    }
+    std::vector<CellDesc> cells(dq.size());
+    for (size_t i = 0; i < dq.size(); ++i) cells[i] = CellDesc{0, {0, 0, 0}, dq[i], 0};
+    const std::vector<MortarHUnit> units = mortar_h_units(plan, dq, root_len, "plan_set_mortar_geometry_brick");
+    if (plan->face_h_type != D4EST_HIP_FACE_H_EQ_TREE_H) sizes_compute(plan, nullptr, extents, cells, ng, root_len);
+    sizes_fill_mortar_h(plan, units, a[4], a[5]);
+  }
   faces_set_geometry(plan, a[0], a[1], a[2], a[3], a[4], a[5], /*on_device=*/1);
   for (int i = 0; i < 6; ++i) HIP_CHECK(hipFree(a[i]));
 }
@@ -3111,6 +3193,15 @@ void faces_set_geometry_analytic(d4est_hip_plan* plan, const TreeMapParams& P, c
     hipLaunchKernelGGL(analytic_mortar_kernel, dim3(std::min((int)units.size(), 8192)), dim3(64), 0, plan->stream, d_units, (int)units.size(), P,
                        root_len, d_qn, a[0], a[1], a[2], a[3], a[4], a[5]);
   HIP_CHECK(hipGetLastError());
+  if (plan->face_h_type != D4EST_HIP_FACE_H_EQ_J_DIV_SJ_QUAD) {
+    std::vector<CellDesc> cells(elem);
+    cells.insert(cells.end(), ghost.begin(), ghost.end());
+    std::vector<int> dq(cells.size());
+    for (size_t i = 0; i < cells.size(); ++i) dq[i] = cells[i].dq;
+    const std::vector<MortarHUnit> hunits = mortar_h_units(plan, dq, root_len, "plan_set_mortar_geometry_analytic");
+    if (plan->face_h_type != D4EST_HIP_FACE_H_EQ_TREE_H) sizes_compute(plan, &P, nullptr, cells, (int)ghost.size(), root_len);
+    sizes_fill_mortar_h(plan, hunits, a[4], a[5]);
+  }
   faces_set_geometry(plan, a[0], a[1], a[2], a[3], a[4], a[5], /*on_device=*/1);
   for (int i = 0; i < 6; ++i) HIP_CHECK(hipFree(a[i]));
   HIP_CHECK(hipFree(d_units));

@@ -171,6 +171,12 @@ struct d4est_hip_plan {
   double* d_host[4] = {nullptr, nullptr, nullptr, nullptr};
 
   void* xyz = nullptr;   // d4est_hip::XyzHost (d4est_hip_volume.hip): what plan_compute_xyz_analytic keeps between calls
+
+  // element size parameters (d4est_hip_sizes.hip): [mesh_parameters] face_h_type / volume_h_type (d4est_hip_plan_set_h_types; the defaults
+  // are what the device mortar forms always wrote) and the plan-owned arrays of d4est_mesh_init_element_size_parameters
+  int face_h_type = D4EST_HIP_FACE_H_EQ_J_DIV_SJ_QUAD;
+  int volume_h_type = D4EST_HIP_VOL_H_EQ_DIAM;
+  void* sizes = nullptr;           // d4est_hip::SizeHost
 };
 
 namespace d4est_hip {
@@ -188,6 +194,28 @@ void launch_analytic_xyz(d4est_hip_plan* plan, const TreeMapParams& P, const std
                          double* xyz_lobatto, double* xyz_quad);
 void analytic_xyz_destroy(d4est_hip_plan* plan);
 
+// d4est_hip_sizes.hip: element size parameters (d4est_mesh_init_element_size_parameters_local / _ghost) on the plan's stream.
+// cells: the local elements followed by n_ghost ghost elements (n_ghost = 0: local elements only); brick != nullptr: the brick
+// geometry with these extents (the cells' tree and q are not used), else the analytic map P
+void sizes_compute(d4est_hip_plan* plan, const TreeMapParams* P, const double* brick_extents, const std::vector<CellDesc>& cells,
+                   int n_ghost, double root_len);
+void sizes_compute_diameters(d4est_hip_plan* plan, const double* xyz_lobatto);
+// the plan-owned device array `which` (D4EST_HIP_SIZE_*) and its length; nullptr when it has not been computed
+const double* sizes_array(const d4est_hip_plan* plan, int which, long long* count);
+void sizes_destroy(d4est_hip_plan* plan);
+// one mortar face of the reference-layout hm / hp arrays and the elements whose parameters d4est_mesh_calculate_mortar_h reads for it:
+// index e for a local element, n_elements + g for ghost g.  one_m / one_p: the element whose parameter the mortar face takes (its own
+// small element on a side of four, else the one element); em / ep: all elements of the side, which enter
+// FACE_H_EQ_TOTAL_VOLUME_DIV_TOTAL_AREA.  A boundary side has (+) = (-).
+struct MortarHUnit {
+  int at, T;                     // hm[at .. at + T), hp likewise
+  int one_m, f_m, n_m, em[4];
+  int one_p, f_p, n_p, ep[4];
+  double tree_h_m, tree_h_p;     // dq / root_len of one_m / one_p
+};
+// hm / hp of every unit by the plan's face_h_type (any but J_DIV_SJ_QUAD) from the size parameters, which must have been computed
+void sizes_fill_mortar_h(d4est_hip_plan* plan, const std::vector<MortarHUnit>& units, double* hm, double* hp);
+
 // d4est_hip_volume.hip
 void launch_metric_precombine(d4est_hip_plan* plan, const double* d_J, const double* d_rst);
 void launch_stiffness(d4est_hip_plan* plan, const double* u, double* Au);
@@ -198,7 +226,7 @@ void launch_stiffness_view(d4est_hip_plan* plan, const double* u, double* Au, in
 void launch_mass_like(d4est_hip_plan* plan, int mode, const double* in, double* out, const double* coeff = nullptr, int which = 0);
 void launch_brick_geometry(d4est_hip_plan* plan, const int* d_elem_dq, double root_len, const double* extents);
 void launch_numerical_geometry(d4est_hip_plan* plan, const double* d_xyz);
-void faces_set_geometry_brick(d4est_hip_plan* plan, const int* d_elem_dq, double root_len, const double* extents);
+void faces_set_geometry_brick(d4est_hip_plan* plan, const int* d_elem_dq, const int* h_elem_dq, double root_len, const double* extents);
 void launch_slicer_lift(d4est_hip_plan* plan, const double* in, double* out, int face, int lift);
 void launch_dij(d4est_hip_plan* plan, const double* in, double* out, int dir, int transpose);
 void launch_dudr(d4est_hip_plan* plan, const double* u, double* d0, double* d1, double* d2);

@@ -130,7 +130,7 @@ void d4est_hip_plan_set_geometry_numerical(d4est_hip_plan_t* plan, const double*
  * rst_xyz_quad / mortar arrays are formed on the host or uploaded.  elem_dq[e] = the quadrant's side length in p4est integer
  * coordinates (d4est_element_data_t::dq), root_len = P4EST_ROOT_LEN, extents = {X0, X1, Y0, Y1, Z0, Z1}.  The mortar variant is
  * called where d4est_hip_plan_set_mortar_geometry would be (after plan_set_faces / plan_set_sipg); hanging faces use the mortar-sized
- * cell (src/Mesh/d4est_mortars.c:420-470), face_h_type FACE_H_EQ_J_DIV_SJ_QUAD. */
+ * cell (src/Mesh/d4est_mortars.c:420-470); hm / hp by the plan's face_h_type (d4est_hip_plan_set_h_types; default FACE_H_EQ_J_DIV_SJ_QUAD). */
 void d4est_hip_plan_set_geometry_brick(d4est_hip_plan_t* plan, const int* elem_dq, double root_len, const double* extents);
 void d4est_hip_plan_set_mortar_geometry_brick(d4est_hip_plan_t* plan, const int* elem_dq, double root_len, const double* extents);
 
@@ -154,7 +154,7 @@ void d4est_hip_plan_set_mortar_geometry_brick(d4est_hip_plan_t* plan, const int*
  * The mortar variant is called where d4est_hip_plan_set_mortar_geometry would be (after plan_set_hanging / plan_set_faces /
  * plan_set_sipg), needs the same three arrays for the ghost elements (order of ghost_deg), follows faces between trees through
  * side_reorder / side_orientation and hanging faces through the half-size virtual children of the big element
- * (src/Mesh/d4est_mortars.c:419-468); face_h_type FACE_H_EQ_J_DIV_SJ_QUAD. */
+ * (src/Mesh/d4est_mortars.c:419-468); hm / hp by the plan's face_h_type (d4est_hip_plan_set_h_types; default FACE_H_EQ_J_DIV_SJ_QUAD). */
 #define D4EST_HIP_GEOM_CUBED_SPHERE_7TREE 1
 #define D4EST_HIP_GEOM_CUBED_SPHERE 2
 #define D4EST_HIP_GEOM_CUBED_SPHERE_WITH_SPHERE_HOLE 3
@@ -313,7 +313,8 @@ void d4est_hip_plan_set_mortar_geometry(d4est_hip_plan_t* plan, const double* sj
 void d4est_hip_plan_set_estimator(d4est_hip_plan_t* plan, int gradu_fcn, int u_fcn, int u_dirichlet_fcn, double penalty_prefactor);
 /* eta2_dev[n_elements] (and terms_dev[4 n_elements], term-major: term t of element e at t n_elements + e, the reference's estimator_vtk
  * layout; NULL = not wanted) from device vectors u_dev and residual_dev (local_nodes: the residual d4est_elliptic_eqns_build_residual
- * leaves in Au) and diam_dev[n_elements] (d4est_mesh_data_t::diam_volume).  ghost_trace_dev: the ghost trace buffer of plans with ghost
+ * leaves in Au) and diam_dev[n_elements] (d4est_mesh_data_t::diam_volume; NULL = the plan's own diam_volume,
+ * d4est_hip_plan_compute_size_parameters_* / _compute_diameters, and an abort if that has not been computed).  ghost_trace_dev: the ghost trace buffer of plans with ghost
  * sides (d4est_hip_plan_ghost_trace_size doubles, filled by the caller's exchange of u's traces), or NULL -- then the traces are
  * exchanged through the plan_set_comm hooks, as apply_lhs does (on plans with hanging faces the *_sub blocks included).
  * g_lobatto_dev: Dirichlet data on the boundary sides' Lobatto face nodes in the layout of d4est_hip_plan_set_dirichlet_values, NULL =
@@ -327,6 +328,53 @@ void d4est_hip_estimator_bi(d4est_hip_plan_t* plan, const double* u_dev, const d
 /* 1 and the three ids and the prefactor of d4est_hip_plan_set_estimator (either output may be NULL) when the plan has the estimator,
  * else 0 -- for hosts that check a caller's penalty functions against the plan (the compat library's d4est_estimator_bi_compute) */
 int d4est_hip_plan_estimator_info(const d4est_hip_plan_t* plan, int* ids, double* penalty_prefactor);
+/* ---- element size parameters and [mesh_parameters] face_h_type / volume_h_type (csrc/d4est_hip_sizes.hip) ----------------------------
+ * The ids follow the reference's enums d4est_mesh_face_h_t / d4est_mesh_volume_h_t (src/Mesh/d4est_mesh.h:33-48). */
+#define D4EST_HIP_FACE_H_EQ_J_DIV_SJ_QUAD 0                 /* J / sj at every mortar quadrature node (the default) */
+#define D4EST_HIP_FACE_H_EQ_J_DIV_SJ_MIN_LOBATTO 1          /* min of J / sj over the face's Lobatto nodes */
+#define D4EST_HIP_FACE_H_EQ_J_DIV_SJ_MEAN_LOBATTO 2
+#define D4EST_HIP_FACE_H_EQ_J_DIV_SJ_MAX_LOBATTO 3
+#define D4EST_HIP_FACE_H_EQ_TREE_H 4                        /* dq / P4EST_ROOT_LEN */
+#define D4EST_HIP_FACE_H_EQ_VOLUME_DIV_AREA 5               /* volume of the element / area of its face */
+#define D4EST_HIP_FACE_H_EQ_FACE_DIAM 6                     /* largest node distance on the face */
+#define D4EST_HIP_FACE_H_EQ_TOTAL_VOLUME_DIV_TOTAL_AREA 7   /* summed over the side's one or four elements */
+#define D4EST_HIP_VOL_H_EQ_DIAM 0
+#define D4EST_HIP_VOL_H_EQ_CUBE_APPROX 1                    /* diam_volume / sqrt(3) */
+/* Which h the device mortar forms (plan_set_mortar_geometry_brick / _analytic) write into hm / hp, and whether diam_volume is scaled:
+ * d4est_mesh_calculate_mortar_h (src/Mesh/d4est_mesh.c:689-856, called at :629-644 and :1071-1103) and
+ * d4est_mesh_data_compute_volume_diam (:3414-3468).  Call BEFORE the mortar geometry, like d4est_hip_plan_set_sipg; aborts on an id out
+ * of range.  A plan without the call behaves as before (J_DIV_SJ_QUAD, DIAM).  With any other face type the mortar forms first compute
+ * the size parameters below themselves (ghost elements included), then fill hm with the parameter of the (-) element(s) on face f_m
+ * and hp with that of the (+) element(s), in (-) order, on face f_p -- constant over a mortar face; on a hanging face each of the four
+ * mortar faces takes the parameter of its own small element on the side that has four and of the one big element (its own parameter,
+ * not a half-size child's) on the other.  FACE_H_EQ_FACE_DIAM and FACE_H_EQ_TOTAL_VOLUME_DIV_TOTAL_AREA index the reference's arrays
+ * without the ghost offset (:801-802, :841), so what the reference computes across ranks is not defined: on a plan with ghost sides
+ * the mortar forms abort for these two.  Host-array factors (d4est_hip_plan_set_mortar_geometry) carry their own hm / hp. */
+void d4est_hip_plan_set_h_types(d4est_hip_plan_t* plan, int face_h_type, int volume_h_type);
+/* d4est_mesh_init_element_size_parameters_local / _ghost (src/Mesh/d4est_mesh.c:1620-1827) on the device, everything on the Lobatto
+ * nodes of the element's own deg; index e for local element e, n_elements + g for ghost g, faces at 6 * index + f: */
+#define D4EST_HIP_SIZE_DIAM_VOLUME 0     /* n: max over all node pairs of |x_i - x_j| (:3446-3467), / sqrt(3) with VOL_H_EQ_CUBE_APPROX */
+#define D4EST_HIP_SIZE_VOLUME 1          /* n: Lobatto inner product of 1 with J (:1736-1749) */
+#define D4EST_HIP_SIZE_AREA 2            /* 6n: the same with sj on the face's Lobatto nodes (:1778-1791) */
+#define D4EST_HIP_SIZE_DIAM_FACE 3       /* 6n: max pair distance over the face's nodes (:1794-1807) */
+#define D4EST_HIP_SIZE_J_DIV_SJ_MIN 4    /* 6n: min / mean / max of J / sj over the face's Lobatto nodes (:1808-1812), J and sj as */
+#define D4EST_HIP_SIZE_J_DIV_SJ_MEAN 5   /*     d4est_mortars_compute_geometric_data_on_mortar gives them with */
+#define D4EST_HIP_SIZE_J_DIV_SJ_MAX 6    /*     COMPUTE_NORMAL_USING_JACOBIAN */
+/* Brick geometry: elem_dq / root_len / extents as d4est_hip_plan_set_geometry_brick; ghost_dq (order of ghost_deg, needs plan_set_faces)
+ * or NULL = local elements only.  Analytic tree maps: the arguments of d4est_hip_plan_set_mortar_geometry_analytic; the three ghost
+ * arrays may be NULL likewise.  One launch per degree on the plan's stream, no host synchronisation after the first call's
+ * allocations, no atomics: bit-identical from call to call.  Degrees 1 ... 23. */
+void d4est_hip_plan_compute_size_parameters_brick(d4est_hip_plan_t* plan, const int* elem_dq, const int* ghost_dq, double root_len,
+                                                  const double* extents);
+void d4est_hip_plan_compute_size_parameters_analytic(d4est_hip_plan_t* plan, int geom_type, const double* params, const int* elem_tree,
+                                                     const int* elem_q, const int* elem_dq, const int* ghost_tree, const int* ghost_q,
+                                                     const int* ghost_dq, double root_len);
+/* diam_volume and diam_face alone, of the local elements, from their node coordinates xyz_lobatto_dev = x[local_nodes] | y | z
+ * (d4est_factors->xyz, any geometry): all the estimator's h needs on a geometry the engine has no map for (:1673-1690, :1794-1807). */
+void d4est_hip_plan_compute_diameters(d4est_hip_plan_t* plan, const double* xyz_lobatto_dev);
+/* The plan-owned device array `which` (D4EST_HIP_SIZE_*) and its length in doubles; returns 1, or 0 -- leaving the outputs alone --
+ * when that array has not been computed.  The pointer stays valid until the plan is destroyed or a later call covers more elements. */
+int d4est_hip_plan_size_parameter(const d4est_hip_plan_t* plan, int which, const double** array_dev, long long* count);
 /* ---- error norms (csrc/d4est_hip_norms.hip) -----------------------------------------------------------------------------------------
  * The columns of d4est_norms_save (src/IO/d4est_norms.c:380-560), which the drivers write once per AMR level (e.g.
  * src/Problems/ConstantDensityStar/constant_density_star_mgpc_newton_petsc.c:266-287, :453-473): L_2, L_infty, energy_norm and

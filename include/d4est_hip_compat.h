@@ -267,7 +267,8 @@ void cg_eigs(p4est_t *p4est,d4est_elliptic_data_t *vecs,d4est_elliptic_eqns_t *f
  * probe arguments and matched against the ten closed forms of D4EST_HIP_EST_* (ids 1 / 9 and 3 / 6 are the same formula); no match,
  * or ids / prefactor other than the plan's, aborts.  Dirichlet data: u_bndry_fcn(x, y, z, bndry_ctx) at the boundary Lobatto face
  * nodes, taken from the Lobatto coordinates of d4est_hip_compat_bind_coordinates (required) through d4est_hip_plan_boundary_gather;
- * element diameters from d4est_hip_compat_bind_element_diameters (required).  estimator_vtk (4 n, or NULL) receives the four terms;
+ * element diameters from d4est_hip_compat_bind_element_diameters or, when none are bound, the plan's own diam_volume
+ * (d4est_hip_plan_compute_size_parameters_* / d4est_hip_plan_compute_diameters); neither aborts.  estimator_vtk (4 n, or NULL) receives the four terms;
  * estimator_vtk_per_face must be NULL (not supported: aborts).  The returned array of n doubles is allocated with sc_malloc(p4est_package_id,
  * .) when the process has libsc (found with dlsym(RTLD_DEFAULT, .)), so that the caller's P4EST_FREE releases it, else with malloc (plain-C
  * hosts without libsc: free it with free). */
@@ -320,7 +321,8 @@ void d4est_hip_compat_bind_flux(const void* p4est, double sipg_penalty_prefactor
 /* the node coordinates of the mesh (d4est_factors->xyz[d] at the Lobatto nodes, ->xyz_quad[d] at the quadrature nodes; host arrays that
  * stay the caller's; either may be NULL): where d4est_laplacian_build_rhs_with_strong_bc evaluates the source callback */
 void d4est_hip_compat_bind_coordinates(const void* p4est, double* xyz_lobatto[3], double* xyz_quad[3]);
-/* d4est_factors->diam_volume (host array of the local elements, stays the caller's): the h of the estimator's residual term */
+/* d4est_factors->diam_volume (host array of the local elements, stays the caller's): the h of the estimator's residual term; takes
+ * precedence over the diam_volume the plan computed itself */
 void d4est_hip_compat_bind_element_diameters(const void* p4est, const double* diam_volume);
 /* the Schwarz smoother of this mesh and its three [d4est_solver_schwarz] CG options, for d4est_solver_schwarz_iterate; NULL unbinds */
 void d4est_hip_compat_bind_schwarz(const void* p4est, d4est_hip_schwarz_t* sz, int subdomain_iter, double subdomain_atol, double subdomain_rtol);
