@@ -561,6 +561,35 @@ __global__ __launch_bounds__(64, 4) void stiffness_wave2_kernel(
   }
 }
 
+// The element's loads of the even-odd single-wavefront kernels.  E > 0 (collocated-gradient body, streamed metric): the entry-prefetch
+// schedule -- behind the requests for u, and before their LDS writes, the lane requests the planes kq = 0 ... E - 1 of all six metric
+// components of its quadrature line (lane te owns the nodes (a, b, .) with a + N b = te) into mwe, where they wait under the forward
+// contractions (stiffness_wave_eo_element_cg).  The memory counter retires in order: u first, so that the wait before the LDS writes
+// does not cover the 6 E metric loads; the scheduling barriers pin that order.  Called by active lanes only (an inactive lane has no
+// element: its qs is not valid and it requests nothing).
+constexpr int kWaveCgEntry = D4EST_HIP_WAVE_CG_ENTRY;
+constexpr bool kWaveCgSplit = D4EST_HIP_WAVE_CG_SPLIT_F4 != 0;
+template <int N, int PL, int PN, int E>
+__device__ __forceinline__ void wave_eo_load_element(double* R0, const double* __restrict__ src, const double* __restrict__ metric, int qs,
+                                                     int te, double (*mwe)[6]) {
+  constexpr int N3 = N * N * N;
+  static_assert(E == 0 || PL == N * N, "entry prefetch: deg_quad = deg");
+  if constexpr (E > 0) {
+    double v[(N3 + PL - 1) / PL];
+    load_element_issue<N, PL>(v, src, te);
+    __builtin_amdgcn_sched_barrier(0);
+    const double* __restrict__ m = metric + (size_t)6 * qs + te;
+#pragma unroll
+    for (int kq = 0; kq < E && kq < N; ++kq)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) mwe[kq][c] = m[c * N3 + N * N * kq];
+    __builtin_amdgcn_sched_barrier(0);
+    load_element_commit<N, PL, PN>(R0, v, te);
+  } else {
+    load_element_image<N, PL, PN>(R0, src, te);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // EVEN-ODD single-wavefront kernel.  The 1-D operators on symmetric node sets are centro-symmetric
 // (B: B[R-1-r][C-1-c] = B[r][c]) or centro-antisymmetric (G = B D).  With xe = x[c] + x[C-1-c], xo = x[c] - x[C-1-c]
@@ -579,7 +608,8 @@ __global__ __launch_bounds__(64, 4) void stiffness_wave2_kernel(
 // constants (affine + 6 * element) instead of being streamed: 16 B/DoF of traffic instead of 64 (SURVEY.md section 8d "affine path")
 // CG = true (N = NQ): the collocated-gradient body (stiffness_wave_eo_element_cg, 12 one-dimensional products per thread instead of 16);
 // EGf / EGb then carry the even-odd tables of Dq / Dq^T (Bucket::d_EDq / d_EDqT)
-template <int N, int NQ, bool AFF = false, bool CG = false>
+// ENTRY (CG, streamed metric): the entry-prefetch schedule of the metric stream, see wave_eo_load_element
+template <int N, int NQ, bool AFF = false, bool CG = false, bool ENTRY = false>
 __global__ __launch_bounds__(64, 4) void stiffness_wave_eo_kernel(
     const double* __restrict__ u, double* __restrict__ Au, const double* __restrict__ metric,
     const int* __restrict__ ns_list, const int* __restrict__ qs_list, int n_bucket, const double* __restrict__ EBf,
@@ -599,6 +629,7 @@ __global__ __launch_bounds__(64, 4) void stiffness_wave_eo_kernel(
   const bool active = (slot < C::EPB) && (ei < n_bucket);
   double* R0 = smem + (active ? slot : 0) * C::LDS_PER_ELEM;
   double* R1 = R0 + FS;
+  double mwe[kWaveCgEntry > 0 ? kWaveCgEntry : 1][6];   // (ENTRY: the metric planes requested here)
   int ns = 0, qs = 0;
   if (active) {
     if (ns_stride >= 0) {
@@ -612,10 +643,10 @@ __global__ __launch_bounds__(64, 4) void stiffness_wave_eo_kernel(
       ns = __builtin_amdgcn_readfirstlane(ns);
       qs = __builtin_amdgcn_readfirstlane(qs);
     }
-    load_element_image<N, PL, PN>(R0, u + ns, te);
+    wave_eo_load_element<N, PL, PN, (ENTRY && CG && !AFF) ? kWaveCgEntry : 0>(R0, u + ns, metric, qs, te, mwe);
   }
   __syncthreads();
-  if constexpr (CG) stiffness_wave_eo_element_cg<N, AFF, true>(R0, R1, metric, qs, ei, active, a, b, EBf, EGf, EBb, EGb, affine, wq);
+  if constexpr (CG) stiffness_wave_eo_element_cg<N, AFF, true, false, false, (ENTRY && !AFF) ? kWaveCgEntry : 0, ENTRY && !AFF && kWaveCgSplit>(R0, R1, metric, qs, ei, active, a, b, EBf, EGf, EBb, EGb, affine, wq, nullptr, mwe);
   else stiffness_wave_eo_element<N, NQ, AFF, true>(R0, R1, metric, qs, ei, active, a, b, EBf, EGf, EBb, EGb, affine, wq);
   if (active) {
     store_element_image<N, PL, PN>(Au + ns, R0, te);
@@ -642,7 +673,7 @@ struct WaveEoMulti {
   const double* wq[MAXB] = {};
 };
 
-template <int N, bool AFF, bool CG>
+template <int N, bool AFF, bool CG, bool ENTRY>
 __device__ __forceinline__ void wave_eo_multi_body(double* smem, int wg, const double* __restrict__ u, double* __restrict__ Au,
                                                    const double* __restrict__ metric, const int* __restrict__ ns_list,
                                                    const int* __restrict__ qs_list, int n_bucket, const double* __restrict__ EBf,
@@ -659,6 +690,7 @@ __device__ __forceinline__ void wave_eo_multi_body(double* smem, int wg, const d
   const bool active = (slot < C::EPB) && (ei < n_bucket);
   double* R0 = smem + (active ? slot : 0) * C::LDS_PER_ELEM;
   double* R1 = R0 + FS;
+  double mwe[kWaveCgEntry > 0 ? kWaveCgEntry : 1][6];
   int ns = 0, qs = 0;
   if (active) {
     ns = ns_list[ei];
@@ -667,17 +699,17 @@ __device__ __forceinline__ void wave_eo_multi_body(double* smem, int wg, const d
       ns = __builtin_amdgcn_readfirstlane(ns);
       qs = __builtin_amdgcn_readfirstlane(qs);
     }
-    load_element_image<N, PL, PN>(R0, u + ns, te);
+    wave_eo_load_element<N, PL, PN, (ENTRY && CG && !AFF) ? kWaveCgEntry : 0>(R0, u + ns, metric, qs, te, mwe);
   }
   __syncthreads();
-  if constexpr (CG) stiffness_wave_eo_element_cg<N, AFF, true>(R0, R1, metric, qs, ei, active, a, b, EBf, EGf, EBb, EGb, affine, wq);
+  if constexpr (CG) stiffness_wave_eo_element_cg<N, AFF, true, false, false, (ENTRY && !AFF) ? kWaveCgEntry : 0, ENTRY && !AFF && kWaveCgSplit>(R0, R1, metric, qs, ei, active, a, b, EBf, EGf, EBb, EGb, affine, wq, nullptr, mwe);
   else stiffness_wave_eo_element<N, N, AFF, true>(R0, R1, metric, qs, ei, active, a, b, EBf, EGf, EBb, EGb, affine, wq);
   if (active) {
     store_element_image<N, PL, PN>(Au + ns, R0, te);
   }
 }
 
-template <bool AFF, bool CG>
+template <bool AFF, bool CG, bool ENTRY = false>
 __global__ __launch_bounds__(64, 4) void stiffness_wave_eo_multi_kernel(const double* __restrict__ u, double* __restrict__ Au,
                                                                         const double* __restrict__ metric,
                                                                         const int* __restrict__ ns_list_all,
@@ -697,7 +729,7 @@ __global__ __launch_bounds__(64, 4) void stiffness_wave_eo_multi_kernel(const do
   const double* aff = AFF ? affine_all + (size_t)6 * off : nullptr;
 #define D4EST_CASE(N_)                                                                                                            \
   case N_:                                                                                                                        \
-    wave_eo_multi_body<N_, AFF, CG>(smem, wg, u, Au, metric, ns_list_all + off, qs_list_all + off, nb, EBf, EGf, EBb, EGb, aff, wq);   \
+    wave_eo_multi_body<N_, AFF, CG, ENTRY>(smem, wg, u, Au, metric, ns_list_all + off, qs_list_all + off, nb, EBf, EGf, EBb, EGb, aff, wq);   \
     break;
   switch (A.N[bi]) {
     D4EST_CASE(2) D4EST_CASE(3) D4EST_CASE(4) D4EST_CASE(5) D4EST_CASE(6) D4EST_CASE(7) D4EST_CASE(8)
@@ -1480,6 +1512,18 @@ static bool wave_collocated(const d4est_hip_plan* plan, const Bucket& bk) {
          plan->tuning[D4EST_HIP_TUNE_STIFFNESS_WAVE] != 12;
 }
 
+// ... and its metric stream on the entry-prefetch schedule (wave_eo_load_element) where tuning key D4EST_HIP_TUNE_STIFFNESS_ENTRY says so.
+// Automatic: the one-bucket kernel at N = 8, where the A/B at level 4 measured a gain (profiles/r06_cg_entry_bench.txt); the mixed-degree
+// launch keeps the first schedule.  Both schedules are instantiated for every N.
+static bool wave_entry(const d4est_hip_plan* plan, int N, bool multi) {
+  const int te = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_ENTRY];
+  if (kWaveCgEntry <= 0) return false;
+  return te < 0 ? (!multi && N == 8) : te != 0;
+}
+static void wave_entry_tag(char* tag, size_t n) {
+  std::snprintf(tag, n, ",entry%d%s", kWaveCgEntry, kWaveCgSplit ? ",split" : "");
+}
+
 template <int N, int NQ>
 static void launch_stiffness_wave(d4est_hip_plan* plan, const Bucket& bk, bool use_pf, const double* u, double* Au) {
   if constexpr (NQ * NQ <= 64 && NQ >= N) {
@@ -1507,8 +1551,14 @@ static void launch_stiffness_wave(d4est_hip_plan* plan, const Bucket& bk, bool u
       if constexpr (kWaveCollocated<N, NQ>) { if (cg) go(stiffness_wave_eo_kernel<N, NQ, true, true>, aff, bk.d_w); }
       if (!cg) go(stiffness_wave_eo_kernel<N, NQ, true, false>, aff, bk.d_w);
     } else if (tune_wave_eo(tw_) && bk.d_EBf) {
-      std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_kernel<%d,%d%s>", N, NQ, cg ? ",cg" : "");
-      if constexpr (kWaveCollocated<N, NQ>) { if (cg) go(stiffness_wave_eo_kernel<N, NQ, false, true>, nullptr, nullptr); }
+      const bool entry = cg && wave_entry(plan, N, false);
+      char tag[24] = "";
+      if (entry) wave_entry_tag(tag, sizeof(tag));
+      std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_kernel<%d,%d%s%s>", N, NQ, cg ? ",cg" : "", tag);
+      if constexpr (kWaveCollocated<N, NQ>) {
+        if (entry) go(stiffness_wave_eo_kernel<N, NQ, false, true, true>, nullptr, nullptr);
+        else if (cg) go(stiffness_wave_eo_kernel<N, NQ, false, true>, nullptr, nullptr);
+      }
       if (!cg) go(stiffness_wave_eo_kernel<N, NQ, false, false>, nullptr, nullptr);
     } else if (tw_ == 3 || tune_wave_eo(tw_)) {
       std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave2_kernel<%d,%d>", N, NQ);
@@ -1586,12 +1636,16 @@ static unsigned launch_stiffness_multi(d4est_hip_plan* plan, const double* u, do
       mine |= 1u << i;
     }
     if (A.n < 2) continue;
-    std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_multi_kernel<%s%s> (%d buckets)", aff ? "affine" : "general", all_cg ? ",cg" : "", A.n);
+    const bool entry = !aff && all_cg && wave_entry(plan, 0, true);
+    char tag[24] = "";
+    if (entry) wave_entry_tag(tag, sizeof(tag));
+    std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_multi_kernel<%s%s%s> (%d buckets)", aff ? "affine" : "general", all_cg ? ",cg" : "", tag, A.n);
     auto go = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3(wgs), dim3(64), lds, plan->stream, u, Au, plan->d_metric, plan->d_ns_list, plan->d_qs_list,
                          aff ? plan->d_metric_affine : (const double*)nullptr, A);
     };
     if (aff) { if (all_cg) go(stiffness_wave_eo_multi_kernel<true, true>); else go(stiffness_wave_eo_multi_kernel<true, false>); }
+    else if (entry) go(stiffness_wave_eo_multi_kernel<false, true, true>);
     else { if (all_cg) go(stiffness_wave_eo_multi_kernel<false, true>); else go(stiffness_wave_eo_multi_kernel<false, false>); }
     covered |= mine;
   }

@@ -364,15 +364,20 @@ __device__ __forceinline__ double lds_ld(const double* p) {
 // a compile-time trip count: a `for (idx = te; idx < N3; idx += PL)` loop is not unrolled (its trip count depends on te), and the
 // rolled loop waits for each global load before it requests the next -- N3 / PL serialised memory round trips per element (12 at
 // p = 11).  Here every load is in flight before the first LDS write.
-template <int N, int PL, int PN>
-__device__ __forceinline__ void load_element_image(double* R, const double* __restrict__ src, int te) {
+// (two halves: the kernels that request the first metric planes at entry put those requests between the issue of the element's loads
+// and their LDS writes, stiffness_wave_eo_kernel in d4est_hip_volume.hip)
+template <int N, int PL>
+__device__ __forceinline__ void load_element_issue(double* v, const double* __restrict__ src, int te) {
   constexpr int N3 = N * N * N, NL = (N3 + PL - 1) / PL;
-  double v[NL];
 #pragma unroll
   for (int q = 0; q < NL; ++q) {
     const int idx = te + PL * q;
     v[q] = (N3 % PL == 0 || idx < N3) ? src[idx] : 0.0;
   }
+}
+template <int N, int PL, int PN>
+__device__ __forceinline__ void load_element_commit(double* R, const double* v, int te) {
+  constexpr int N3 = N * N * N, NL = (N3 + PL - 1) / PL;
   if constexpr (PL == N * N) {   // one k-plane per pass: the lane's (i, j) is the same in every plane (no division per load)
     const int ij = (te % N) + PN * (te / N);
 #pragma unroll
@@ -385,6 +390,13 @@ __device__ __forceinline__ void load_element_image(double* R, const double* __re
     const int i = idx % N, j = (idx / N) % N, k = idx / (N * N);
     if (N3 % PL == 0 || idx < N3) R[i + PN * (j + N * k)] = v[q];
   }
+}
+template <int N, int PL, int PN>
+__device__ __forceinline__ void load_element_image(double* R, const double* __restrict__ src, int te) {
+  constexpr int N3 = N * N * N, NL = (N3 + PL - 1) / PL;
+  double v[NL];
+  load_element_issue<N, PL>(v, src, te);
+  load_element_commit<N, PL, PN>(R, v, te);
 }
 template <int N, int PL, int PN, bool NT = false>
 __device__ __forceinline__ void store_element_image(double* __restrict__ dst, const double* R, int te) {
@@ -822,12 +834,53 @@ __device__ __forceinline__ void stiffness_wave_eo_element(double* R0, double* R1
 template <int N, int NQ>
 inline constexpr bool kWaveCollocated = D4EST_HIP_WAVE_COLLOCATED && N == NQ && (N * N <= 64);
 
-template <int N, bool AFF, bool WG_SYNC, bool MASS = false, bool NT = false>
+// Entry prefetch (general path of the stand-alone kernels, E > 0): the caller has requested the metric planes kq = 0 ... E - 1 of the
+// thread's quadrature line right behind the element's own loads, into mwe[kq][0..5] -- they are in flight under the whole forward half
+// (at N = 8 the body needs 96 VGPRs of the 128 that four waves per SIMD leave: room for 6 E more).  The steady state then keeps
+// MD = max(E, D4EST_HIP_WAVE_EO_DEPTH) planes ahead.  SPLIT: F4 and its mirror in B1 as two one-line chains (gs, then gr) instead of
+// the dual chain -- 48 live doubles instead of 96 beside the waiting planes, the rows of Dq fetched twice; every chain sums in the
+// same order, so all schedules give the same bits.
+#ifndef D4EST_HIP_WAVE_CG_ENTRY
+#define D4EST_HIP_WAVE_CG_ENTRY 2
+#endif
+#ifndef D4EST_HIP_WAVE_CG_SPLIT_F4
+#define D4EST_HIP_WAVE_CG_SPLIT_F4 0
+#endif
+#ifndef D4EST_HIP_WAVE_CG_ABLATE
+#define D4EST_HIP_WAVE_CG_ABLATE 0   /* timing experiments only (wrong results): 1 no forward contractions, 2 no backward contractions */
+#endif
+// the contractions of the collocated body; OFF (ablation builds): the inputs passed through, so that every load and LDS access stays
+template <int H, int N, bool OFF>
+__device__ __forceinline__ void cg_single(const double* __restrict__ op, const double* xf, const double* xs, double* y) {
+  if constexpr (OFF) {
+#pragma unroll
+    for (int o = 0; o < N; ++o) y[o] = (o < (N + 1) / 2) ? xf[o % H] : xs[o % H];
+  } else {
+    contract_single_eo<H, N, false>(op, xf, xs, y);
+  }
+}
+template <int H, int N, bool OFF>
+__device__ __forceinline__ void cg_dual(const double* __restrict__ op, const double* xfA, const double* xsA, double* yA, const double* xfB,
+                                        const double* xsB, double* yB) {
+  if constexpr (OFF) {
+#pragma unroll
+    for (int o = 0; o < N; ++o) {
+      yA[o] = (o < (N + 1) / 2) ? xfA[o % H] : xsA[o % H];
+      yB[o] = (o < (N + 1) / 2) ? xfB[o % H] : xsB[o % H];
+    }
+  } else {
+    contract_dual_eo<H, N>(op, xfA, xsA, yA, xfB, xsB, yB);
+  }
+}
+
+template <int N, bool AFF, bool WG_SYNC, bool MASS = false, bool NT = false, int E = 0, bool SPLIT = false>
 __device__ __forceinline__ void stiffness_wave_eo_element_cg(double* R0, double* R1, const double* __restrict__ metric, int qs, int ei,
                                                              bool active, int a, int b, const double* __restrict__ EBf,
                                                              const double* __restrict__ EDq, const double* __restrict__ EBb,
                                                              const double* __restrict__ EDqT, const double* __restrict__ affine,
-                                                             const double* __restrict__ wq, const double* __restrict__ cq = nullptr) {
+                                                             const double* __restrict__ wq, const double* __restrict__ cq = nullptr,
+                                                             const double (*mwe)[6] = nullptr) {
+  constexpr bool kNoF = (D4EST_HIP_WAVE_CG_ABLATE & 1) != 0, kNoB = (D4EST_HIP_WAVE_CG_ABLATE & 2) != 0;
   using C = WaveCfg<N, N>;
   constexpr int P = C::PN;
   constexpr int N3 = N * N * N;
@@ -844,7 +897,7 @@ __device__ __forceinline__ void stiffness_wave_eo_element_cg(double* R0, double*
 #pragma unroll
     for (int i = 0; i < N; ++i) x[i] = lds_ld(&R0[i + line]);
     eo_pre<N>(x, xe, xo);
-    contract_single_eo<H, N, false>(EBf, xe, xo, ab);
+    cg_single<H, N, kNoF>(EBf, xe, xo, ab);
     eo_post<N>(ab, y);
 #pragma unroll
     for (int iq = 0; iq < N; ++iq) R1[a + P * (iq + N * b)] = y[iq];
@@ -856,7 +909,7 @@ __device__ __forceinline__ void stiffness_wave_eo_element_cg(double* R0, double*
 #pragma unroll
     for (int j = 0; j < N; ++j) x[j] = lds_ld(&R1[j + line]);
     eo_pre<N>(x, xe, xo);
-    contract_single_eo<H, N, false>(EBf, xe, xo, ab);
+    cg_single<H, N, kNoF>(EBf, xe, xo, ab);
     eo_post<N>(ab, y);
 #pragma unroll
     for (int jq = 0; jq < N; ++jq) R0[b + P * (a + N * jq)] = y[jq];
@@ -870,7 +923,7 @@ __device__ __forceinline__ void stiffness_wave_eo_element_cg(double* R0, double*
 #pragma unroll
     for (int k = 0; k < N; ++k) x[k] = lds_ld(&R0[k + line]);
     eo_pre<N>(x, xe, xo);
-    contract_single_eo<H, N, false>(EBf, xe, xo, ab);
+    cg_single<H, N, kNoF>(EBf, xe, xo, ab);
     eo_post<N>(ab, w);
 #pragma unroll
     for (int kq = 0; kq < N; ++kq) R1[a + P * (b + N * kq)] = w[kq];   // (R1's readers finished before the barrier above)
@@ -879,7 +932,7 @@ __device__ __forceinline__ void stiffness_wave_eo_element_cg(double* R0, double*
       for (int kq = 0; kq < N; ++kq) vm[kq] = w[kq];
     }
     eo_pre<N>(w, xe, xo);
-    contract_single_eo<H, N, false>(EDq, xo, xe, ab);
+    cg_single<H, N, kNoF>(EDq, xo, xe, ab);
     eo_post<N>(ab, gt);
   }
   SYNC();
@@ -887,29 +940,52 @@ __device__ __forceinline__ void stiffness_wave_eo_element_cg(double* R0, double*
   // both chains.  General path of the stand-alone kernel: the metric planes are requested MD planes ahead of their use, the first ME of
   // them before this last forward contraction (see stiffness_wave_eo_element)
   constexpr bool kPipe = !AFF && WG_SYNC && (D4EST_HIP_WAVE_EO_DEPTH > 0);
-  constexpr int MD = (D4EST_HIP_WAVE_EO_DEPTH < N) ? D4EST_HIP_WAVE_EO_DEPTH : N;
-  constexpr int ME = (D4EST_HIP_WAVE_EO_EARLY < MD) ? D4EST_HIP_WAVE_EO_EARLY : MD;
+  constexpr int ME0 = (kPipe && E > 0) ? ((E < N) ? E : N) : 0;   // planes the caller requested at kernel entry (mwe)
+  constexpr int MD0 = (D4EST_HIP_WAVE_EO_DEPTH < N) ? D4EST_HIP_WAVE_EO_DEPTH : N;
+  constexpr int MD = (ME0 > MD0) ? ME0 : MD0;
+  constexpr int ME1 = (D4EST_HIP_WAVE_EO_EARLY < MD) ? D4EST_HIP_WAVE_EO_EARLY : MD;
+  constexpr int ME = (ME0 > ME1) ? ME0 : ME1;
   double mw[kPipe ? N : 1][6];
+  if constexpr (ME0 > 0) {
+#pragma unroll
+    for (int kq = 0; kq < ME0; ++kq)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) mw[kq][c] = mwe[kq][c];
+  }
   {
     double ys[N], yr[N];
     if (active) {
       double z[N], x[N], ze[H], zo[H], xe[H], xo[H];
+      if constexpr (SPLIT) {   // two one-line chains: the second line is read when the first chain is done
 #pragma unroll
-      for (int j = 0; j < N; ++j) {
-        z[j] = lds_ld(&R1[a + P * (j + N * b)]);
-        x[j] = lds_ld(&R1[j + line]);
+        for (int j = 0; j < N; ++j) z[j] = lds_ld(&R1[a + P * (j + N * b)]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          z[j] = lds_ld(&R1[a + P * (j + N * b)]);
+          x[j] = lds_ld(&R1[j + line]);
+        }
       }
       if constexpr (kPipe) {
         const double* __restrict__ m = metric + (size_t)6 * qs + (a + N * b);
 #pragma unroll
-        for (int kq = 0; kq < ME; ++kq)
+        for (int kq = ME0; kq < ME; ++kq)
 #pragma unroll
           for (int c = 0; c < 6; ++c) mw[kq][c] = ld_sel<NT>(&m[c * N3 + N * N * kq]);
         __builtin_amdgcn_sched_barrier(0);
       }
-      eo_pre<N>(z, ze, zo);
-      eo_pre<N>(x, xe, xo);
-      contract_dual_eo<H, N>(EDq, zo, ze, ys, xo, xe, yr);
+      if constexpr (SPLIT) {
+        eo_pre<N>(z, ze, zo);
+        cg_single<H, N, kNoF>(EDq, zo, ze, ys);
+#pragma unroll
+        for (int j = 0; j < N; ++j) x[j] = lds_ld(&R1[j + line]);
+        eo_pre<N>(x, xe, xo);
+        cg_single<H, N, kNoF>(EDq, xo, xe, yr);
+      } else {
+        eo_pre<N>(z, ze, zo);
+        eo_pre<N>(x, xe, xo);
+        cg_dual<H, N, kNoF>(EDq, zo, ze, ys, xo, xe, yr);
+      }
       double y[N];
       eo_post<N>(ys, y);
 #pragma unroll
@@ -993,7 +1069,7 @@ __device__ __forceinline__ void stiffness_wave_eo_element_cg(double* R0, double*
   if (active) {
     double te_[H], to[H], ab[N];
     eo_pre<N>(gt, te_, to);
-    contract_single_eo<H, N, false>(EDqT, to, te_, ab);
+    cg_single<H, N, kNoB>(EDqT, to, te_, ab);
     eo_post<N>(ab, ft);
     if constexpr (MASS) {
 #pragma unroll
@@ -1003,14 +1079,25 @@ __device__ __forceinline__ void stiffness_wave_eo_element_cg(double* R0, double*
   SYNC();
   if (active) {
     double z[N], x[N], ze[H], zo[H], xe[H], xo[H], ys[N], yr[N], y[N];
+    if constexpr (SPLIT) {
 #pragma unroll
-    for (int j = 0; j < N; ++j) {
-      z[j] = lds_ld(&R0[b + P * (a + N * j)]);   // flux_s(iq = a, jq = j, kq = b)
-      x[j] = lds_ld(&R1[b + P * (j + N * a)]);   // flux_r(iq = j, jq = a, kq = b)
+      for (int j = 0; j < N; ++j) z[j] = lds_ld(&R0[b + P * (a + N * j)]);   // flux_s(iq = a, jq = j, kq = b)
+      eo_pre<N>(z, ze, zo);
+      cg_single<H, N, kNoB>(EDqT, zo, ze, ys);
+#pragma unroll
+      for (int j = 0; j < N; ++j) x[j] = lds_ld(&R1[b + P * (j + N * a)]);   // flux_r(iq = j, jq = a, kq = b)
+      eo_pre<N>(x, xe, xo);
+      cg_single<H, N, kNoB>(EDqT, xo, xe, yr);
+    } else {
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        z[j] = lds_ld(&R0[b + P * (a + N * j)]);   // flux_s(iq = a, jq = j, kq = b)
+        x[j] = lds_ld(&R1[b + P * (j + N * a)]);   // flux_r(iq = j, jq = a, kq = b)
+      }
+      eo_pre<N>(z, ze, zo);
+      eo_pre<N>(x, xe, xo);
+      cg_dual<H, N, kNoB>(EDqT, zo, ze, ys, xo, xe, yr);
     }
-    eo_pre<N>(z, ze, zo);
-    eo_pre<N>(x, xe, xo);
-    contract_dual_eo<H, N>(EDqT, zo, ze, ys, xo, xe, yr);
     eo_post<N>(ys, y);
 #pragma unroll
     for (int j = 0; j < N; ++j) R0[b + P * (a + N * j)] = y[j];
@@ -1027,7 +1114,7 @@ __device__ __forceinline__ void stiffness_wave_eo_element_cg(double* R0, double*
 #pragma unroll
       for (int kq = 0; kq < N; ++kq) F[kq] = ft[kq] + (lds_ld(&R0[kq + line]) + lds_ld(&R1[kq + line]));
       eo_pre<N>(F, fe, fo);
-      contract_single_eo<H, N, false>(EBb, fe, fo, c);
+      cg_single<H, N, kNoB>(EBb, fe, fo, c);
     }
     SYNC();   // every thread has read its private lines
     if (active) {
@@ -1044,7 +1131,7 @@ __device__ __forceinline__ void stiffness_wave_eo_element_cg(double* R0, double*
 #pragma unroll
     for (int jq = 0; jq < N; ++jq) x[jq] = lds_ld(&R0[jq + line]);
     eo_pre<N>(x, xe, xo);
-    contract_single_eo<H, N, false>(EBb, xe, xo, ab);
+    cg_single<H, N, kNoB>(EBb, xe, xo, ab);
     eo_post<N>(ab, y);
 #pragma unroll
     for (int j = 0; j < N; ++j) R1[a + P * (j + N * b)] = y[j];
@@ -1056,7 +1143,7 @@ __device__ __forceinline__ void stiffness_wave_eo_element_cg(double* R0, double*
 #pragma unroll
     for (int iq = 0; iq < N; ++iq) x[iq] = lds_ld(&R1[iq + line]);
     eo_pre<N>(x, xe, xo);
-    contract_single_eo<H, N, false>(EBb, xe, xo, ab);
+    cg_single<H, N, kNoB>(EBb, xe, xo, ab);
     eo_post<N>(ab, y);
 #pragma unroll
     for (int i = 0; i < N; ++i) R0[i + line] = y[i];
