@@ -64,6 +64,14 @@ SIGNATURES = {
     "d4est_hip_plan_compute_xyz_analytic": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
     "d4est_hip_tree_map": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp]),
     "d4est_hip_plan_set_mortar_geometry_brick": (None, [_vp, _vp, ctypes.c_double, _vp]),
+    "d4est_hip_tree_map_d2": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, _vp]),
+    "d4est_hip_plan_set_hessian_brick": (None, [_vp, _vp, ctypes.c_double, _vp]),
+    "d4est_hip_plan_set_hessian_analytic": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double]),
+    "d4est_hip_plan_set_hessian_numerical": (None, [_vp, _vp, _vp, ctypes.c_int]),
+    "d4est_hip_plan_hessian_info": (ctypes.c_int, [_vp]),
+    "d4est_hip_plan_hessian_supported": (ctypes.c_int, [_vp]),
+    "d4est_hip_hessian_trace": (None, [_vp, _vp, _vp]),
+    "d4est_hip_estimator_bi_pointwise": (None, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d4est_hip_plan_set_h_types": (None, [_vp, ctypes.c_int, ctypes.c_int]),
     "d4est_hip_plan_compute_size_parameters_brick": (None, [_vp, _vp, _vp, ctypes.c_double, _vp]),
     "d4est_hip_plan_compute_size_parameters_analytic": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double]),
@@ -274,6 +282,22 @@ def tree_map(geom_type, params, tree, xi):
         if rc:
             return rc, X, D
     return 0, X, D
+
+
+def tree_map_d2(geom_type, params, tree, xi):
+    """the second derivatives of the library's analytic tree map on the HOST (d4est_hip_tree_map_d2; no GPU needed): xi[n, 3] ->
+    (status, d2[n, 3, 3, 3]) with d2[n, i, j, k] = d^2 x_i / d xi_j d xi_k; status as tree_map's"""
+    lib = load_library()
+    pr = np.zeros(5)
+    pv = np.asarray(params, dtype=np.float64).reshape(-1)
+    pr[:pv.size] = pv
+    xi = np.ascontiguousarray(np.asarray(xi, dtype=np.float64).reshape(-1, 3))
+    H = np.full((xi.shape[0], 3, 3, 3), np.nan)
+    for k in range(xi.shape[0]):
+        rc = lib.d4est_hip_tree_map_d2(int(geom_type), pr.ctypes.data_as(_vp), int(tree), xi[k].ctypes.data_as(_vp), H[k].ctypes.data_as(_vp))
+        if rc:
+            return rc, H
+    return 0, H
 
 
 def _ptr(t):
@@ -528,13 +552,65 @@ class Plan:
         D4EST_HIP_EST_*); before set_faces (whose mortar factors also form the estimator's)"""
         self.lib.d4est_hip_plan_set_estimator(self.handle, int(gradu_fcn), int(u_fcn), int(u_dirichlet_fcn), float(penalty_prefactor))
 
+    # ---- the Laplacian at the quadrature nodes (csrc/d4est_hip_hessian.hip) ----
+    def set_hessian_brick(self, elem_dq, root_len, extents):
+        """Hessian-trace coefficients of the brick geometry (arguments as set_geometry_brick)"""
+        dq = _iarr(elem_dq)
+        ex = np.ascontiguousarray(extents, dtype=np.float64)
+        assert len(dq[0]) == self.n_elements and ex.size == 6
+        self.lib.d4est_hip_plan_set_hessian_brick(self.handle, dq[1], float(root_len), ex.ctypes.data_as(_vp))
+
+    def set_hessian_analytic(self, geom_type, params, tree, q, dq, root_len):
+        """Hessian-trace coefficients of an analytic tree map, HESSIAN_ANALYTICAL (arguments as set_geometry_analytic)"""
+        pr = np.zeros(5)
+        pv = np.asarray(params, dtype=np.float64).reshape(-1)
+        pr[:pv.size] = pv
+        t, qq, d = _iarr(tree), _iarr(np.asarray(q).reshape(-1)), _iarr(dq)
+        assert len(t[0]) == self.n_elements and len(d[0]) == self.n_elements and len(qq[0]) == 3 * self.n_elements
+        self.lib.d4est_hip_plan_set_hessian_analytic(self.handle, int(geom_type), pr.ctypes.data_as(_vp), t[1], qq[1], d[1], float(root_len))
+
+    def set_hessian_numerical(self, xyz_lobatto, rst_xyz_quad=None):
+        """Hessian-trace coefficients from the node coordinates, HESSIAN_NUMERICAL: xyz_lobatto = (x, y, z) numpy arrays or one CUDA
+        tensor of 3 local_nodes; rst_xyz_quad (9 local_nodes_quad, reference SoA layout; the same kind of array) or None = dr/dx
+        from the coordinates as set_geometry_numerical forms it"""
+        if isinstance(xyz_lobatto, (list, tuple, np.ndarray)):
+            X = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.float64).reshape(-1) for a in xyz_lobatto]))
+            R = None if rst_xyz_quad is None else np.ascontiguousarray(rst_xyz_quad, dtype=np.float64).reshape(-1)
+            assert X.size == 3 * self.local_nodes and (R is None or R.size == 9 * self.local_nodes_quad)
+            self.lib.d4est_hip_plan_set_hessian_numerical(self.handle, X.ctypes.data_as(_vp), R.ctypes.data_as(_vp) if R is not None else None, 0)
+        else:
+            assert xyz_lobatto.numel() == 3 * self.local_nodes and (rst_xyz_quad is None or rst_xyz_quad.numel() == 9 * self.local_nodes_quad)
+            self.lib.d4est_hip_plan_set_hessian_numerical(self.handle, _ptr(xyz_lobatto),
+                                                          _ptr(rst_xyz_quad) if rst_xyz_quad is not None else None, 1)
+
+    def hessian_info(self):
+        """0 none, 1 brick, 2 analytic, 3 numerical"""
+        return self.lib.d4est_hip_plan_hessian_info(self.handle)
+
+    def hessian_supported(self):
+        """True when every (deg, deg_quad) bucket fits the LDS of the hessian_trace kernel (include/d4est_hip.h)"""
+        return bool(self.lib.d4est_hip_plan_hessian_supported(self.handle))
+
+    def hessian_trace(self, u, out):
+        """out[local_nodes_quad] = the Laplacian of u[local_nodes] at the quadrature nodes (CUDA tensors; out is overwritten)"""
+        assert u.numel() == self.local_nodes and out.numel() == self.local_nodes_quad
+        self.lib.d4est_hip_hessian_trace(self.handle, _ptr(u), _ptr(out))
+
+    def estimator_bi_pointwise(self, u, residual_quad, diam, eta2, terms=None, ghost_trace=None, g=None):
+        """estimator_bi with the pointwise residual (d4est_estimator_bi_new_compute, use_pointwise_residual): residual_quad holds
+        local_nodes_quad values at the quadrature nodes; everything else as estimator_bi"""
+        self._estimator(self.lib.d4est_hip_estimator_bi_pointwise, self.local_nodes_quad, u, residual_quad, diam, eta2, terms, ghost_trace, g)
+
     def estimator_bi(self, u, residual, diam, eta2, terms=None, ghost_trace=None, g=None):
         """eta2[n_elements] (and terms[4 n_elements], term-major) of d4est_estimator_bi_compute.  u, residual: CUDA tensors of
         local_nodes doubles; eta2 / terms / ghost_trace: CUDA tensors; diam (n_elements) and g (Dirichlet data on the boundary Lobatto
         face nodes, set_dirichlet_values' layout; None = 0): numpy arrays or CUDA tensors; diam None: the plan's own diam_volume
         (compute_size_parameters / compute_diameters)"""
+        self._estimator(self.lib.d4est_hip_estimator_bi, self.local_nodes, u, residual, diam, eta2, terms, ghost_trace, g)
+
+    def _estimator(self, fn, n_residual, u, residual, diam, eta2, terms, ghost_trace, g):
         import torch
-        assert u.numel() == self.local_nodes and residual.numel() == self.local_nodes
+        assert u.numel() == self.local_nodes and residual.numel() == n_residual
         assert eta2.numel() == self.n_elements and (terms is None or terms.numel() == 4 * self.n_elements)
         dev = u.device
 
@@ -547,9 +623,9 @@ class Plan:
         assert d_diam is None or d_diam.numel() == self.n_elements
         if ghost_trace is not None:
             assert ghost_trace.numel() == self.ghost_trace_size
-        self.lib.d4est_hip_estimator_bi(self.handle, _ptr(u), _ptr(ghost_trace) if ghost_trace is not None else None, _ptr(residual),
-                                        _ptr(d_diam) if d_diam is not None else None, _ptr(d_g) if d_g is not None else None, _ptr(eta2),
-                                        _ptr(terms) if terms is not None else None)
+        fn(self.handle, _ptr(u), _ptr(ghost_trace) if ghost_trace is not None else None, _ptr(residual),
+           _ptr(d_diam) if d_diam is not None else None, _ptr(d_g) if d_g is not None else None, _ptr(eta2),
+           _ptr(terms) if terms is not None else None)
         if (diam is not None and not isinstance(diam, torch.Tensor)) or (g is not None and not isinstance(g, torch.Tensor)):
             torch.cuda.current_stream(dev).synchronize() if self.torch_stream is None else self.torch_stream.synchronize()
             self.lib.d4est_hip_device_synchronize()   # (the uploaded copies must outlive the launches)

@@ -245,6 +245,7 @@ void d4est_hip_plan_destroy(d4est_hip_plan_t* plan) {
   (void)hipFree(plan->d_scratch);
   d4est_hip::analytic_xyz_destroy(plan);
   d4est_hip::sizes_destroy(plan);
+  d4est_hip::hessian_destroy(plan);
   d4est_hip::faces_destroy(plan);
   (void)hipFree(plan->d_work_p); (void)hipFree(plan->d_work_d); (void)hipFree(plan->d_work_r); (void)hipFree(plan->d_work_m); (void)hipFree(plan->d_lhs_c); (void)hipFree(plan->d_lhs_wjc);
   (void)hipFree(plan->d_lhs_block_off);
@@ -418,6 +419,21 @@ int d4est_hip_tree_map(int geom_type, const double* params, int tree, const doub
   return 0;
 }
 
+int d4est_hip_tree_map_d2(int geom_type, const double* params, int tree, const double* xi, double* d2_out) {
+  d4est_hip::TreeMapParams P;
+  const char* why = "";
+  if (const int rc = analytic_params_status(geom_type, params, &P, &why)) return rc;
+  if (tree < 0 || tree >= d4est_hip::tree_map_num_trees(geom_type)) return 4;
+  if (!xi) return 5;
+  double H[3][3][3];
+  d4est_hip::tree_map_d2(P, tree, xi, H);
+  if (d2_out)
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j)
+        for (int k = 0; k < 3; ++k) d2_out[9 * i + 3 * j + k] = H[i][j][k];
+  return 0;
+}
+
 static std::vector<d4est_hip::CellDesc> cells_from(int n, const int* tree, const int* q, const int* dq, int max_tree, const char* who) {
   std::vector<d4est_hip::CellDesc> c((size_t)std::max(n, 0));
   for (int e = 0; e < n; ++e) {
@@ -477,6 +493,43 @@ void d4est_hip_plan_compute_xyz_analytic(d4est_hip_plan_t* plan, int geom_type, 
   const std::vector<d4est_hip::CellDesc> cells =
       cells_from(plan->n_elements, elem_tree, elem_q, elem_dq, d4est_hip::tree_map_num_trees(geom_type) - 1, "plan_compute_xyz_analytic");
   d4est_hip::launch_analytic_xyz(plan, P, cells, root_len, xyz_lobatto_dev, xyz_quad_dev);
+}
+
+// ---- the Hessian trace (d4est_hip_hessian.hip) ----
+void d4est_hip_plan_set_hessian_brick(d4est_hip_plan_t* plan, const int* elem_dq, double root_len, const double* extents) {
+  check_plan(plan, "plan_set_hessian_brick");
+  if (plan->n_elements > 0 && !elem_dq) D4EST_HIP_ABORT("plan_set_hessian_brick: elem_dq is NULL");
+  if (!extents || !(root_len > 0.) || !(extents[1] > extents[0]) || !(extents[3] > extents[2]) || !(extents[5] > extents[4]))
+    D4EST_HIP_ABORT("plan_set_hessian_brick: bad brick extents / root length");
+  for (int e = 0; e < plan->n_elements; ++e)
+    if (elem_dq[e] <= 0) D4EST_HIP_ABORT("plan_set_hessian_brick: element %d has dq %d", e, elem_dq[e]);
+  d4est_hip::hessian_set_brick(plan, elem_dq, root_len, extents);
+}
+
+void d4est_hip_plan_set_hessian_analytic(d4est_hip_plan_t* plan, int geom_type, const double* params, const int* elem_tree,
+                                         const int* elem_q, const int* elem_dq, double root_len) {
+  const char* who = "plan_set_hessian_analytic";
+  check_plan(plan, who);
+  const d4est_hip::TreeMapParams P = analytic_params(geom_type, params, who);
+  if (plan->n_elements > 0 && (!elem_tree || !elem_q || !elem_dq)) D4EST_HIP_ABORT("%s: NULL element array", who);
+  if (!(root_len > 0.)) D4EST_HIP_ABORT("%s: root_len", who);
+  const std::vector<d4est_hip::CellDesc> cells =
+      cells_from(plan->n_elements, elem_tree, elem_q, elem_dq, d4est_hip::tree_map_num_trees(geom_type) - 1, who);
+  d4est_hip::hessian_set_analytic(plan, P, cells, root_len);
+}
+
+void d4est_hip_plan_set_hessian_numerical(d4est_hip_plan_t* plan, const double* xyz_lobatto, const double* rst_xyz_quad, int on_device) {
+  check_plan(plan, "plan_set_hessian_numerical");
+  if (!xyz_lobatto) D4EST_HIP_ABORT("plan_set_hessian_numerical: NULL coordinate array");
+  d4est_hip::hessian_set_numerical(plan, xyz_lobatto, rst_xyz_quad, on_device);
+}
+
+int d4est_hip_plan_hessian_info(const d4est_hip_plan_t* plan) { check_plan(plan, "plan_hessian_info"); return d4est_hip::hessian_info(plan); }
+int d4est_hip_plan_hessian_supported(const d4est_hip_plan_t* plan) { check_plan(plan, "plan_hessian_supported"); return d4est_hip::hessian_supported(plan); }
+
+void d4est_hip_hessian_trace(d4est_hip_plan_t* plan, const double* u_dev, double* del2u_quad_dev) {
+  check_plan(plan, "hessian_trace");
+  d4est_hip::hessian_trace(plan, u_dev, del2u_quad_dev);
 }
 
 void d4est_hip_plan_set_h_types(d4est_hip_plan_t* plan, int face_h_type, int volume_h_type) {
@@ -694,6 +747,18 @@ void d4est_hip_estimator_bi(d4est_hip_plan_t* plan, const double* u_dev, const d
     if (!diam_dev) D4EST_HIP_ABORT("estimator_bi: diam_dev is NULL and the plan's diam_volume has not been computed (plan_compute_size_parameters_* / plan_compute_diameters)");
   }
   d4est_hip::estimator_compute(plan, u_dev, ghost_trace_dev, residual_dev, diam_dev, g_lobatto_dev, eta2_dev, terms_dev);
+}
+
+void d4est_hip_estimator_bi_pointwise(d4est_hip_plan_t* plan, const double* u_dev, const double* ghost_trace_dev,
+                                      const double* residual_quad_dev, const double* diam_dev, const double* g_lobatto_dev,
+                                      double* eta2_dev, double* terms_dev) {
+  check_plan(plan, "estimator_bi_pointwise");
+  if (!plan->has_faces) D4EST_HIP_ABORT("estimator_bi_pointwise: the plan has no faces (plan_set_faces)");
+  if (!diam_dev) {
+    diam_dev = d4est_hip::sizes_array(plan, D4EST_HIP_SIZE_DIAM_VOLUME, nullptr);
+    if (!diam_dev) D4EST_HIP_ABORT("estimator_bi_pointwise: diam_dev is NULL and the plan's diam_volume has not been computed (plan_compute_size_parameters_* / plan_compute_diameters)");
+  }
+  d4est_hip::estimator_compute(plan, u_dev, ghost_trace_dev, residual_quad_dev, diam_dev, g_lobatto_dev, eta2_dev, terms_dev, true);
 }
 
 int d4est_hip_plan_estimator_info(const d4est_hip_plan_t* plan, int* ids, double* penalty_prefactor) {

@@ -788,6 +788,28 @@ double d4est_mesh_compute_l2_norm_sqr(p4est_t* p4est, d4est_operators_t*, d4est_
   return sum;
 }
 
+// ---- src/dGMath/d4est_hessian.c:270-368 --------------------------------------------------------------------------------------
+void d4est_hessian_compute_hessian_trace_of_field_on_quadrature_points(p4est_t* p4est, d4est_operators_t*, d4est_geometry_t*,
+                                                                       d4est_quadrature_t*, d4est_mesh_data_t*,
+                                                                       d4est_hessian_compute_method_t compute_method, double* field_lobatto,
+                                                                       double* del2field) {
+  const char* who = "d4est_hessian_compute_hessian_trace_of_field_on_quadrature_points";
+  d4est_hip_plan_t* plan = bound(p4est, who);
+  const int form = d4est_hip_plan_hessian_info(plan);   // 0 none, 1 brick, 2 analytic, 3 numerical
+  if (compute_method != HESSIAN_ANALYTICAL && compute_method != HESSIAN_NUMERICAL) COMPAT_ABORT("%s: compute method must be NUMERICAL or ANALYTICAL", who);
+  if (form == 0) COMPAT_ABORT("%s: the bound plan has no Hessian coefficients (d4est_hip_plan_set_hessian_*)", who);
+  if ((compute_method == HESSIAN_NUMERICAL) != (form == 3))
+    COMPAT_ABORT("%s: compute_method %d, the bound plan holds coefficients of form %d (1 brick, 2 analytic, 3 numerical)", who, compute_method, form);
+  if (!field_lobatto || !del2field) COMPAT_ABORT("%s: NULL vector", who);
+  const size_t ln = (size_t)d4est_hip_plan_local_nodes(plan), nq = (size_t)d4est_hip_plan_local_nodes_quad(plan);
+  double* d_u = (double*)d4est_hip_malloc(sizeof(double) * (ln + nq));
+  d4est_hip_memcpy_h2d(d_u, field_lobatto, sizeof(double) * ln);
+  d4est_hip_hessian_trace(plan, d_u, d_u + ln);
+  d4est_hip_plan_synchronize(plan);
+  d4est_hip_memcpy_d2h(del2field, d_u + ln, sizeof(double) * nq);
+  d4est_hip_free(d_u);
+}
+
 double d4est_norms_fcn_L2(p4est_t* p4est, double* field_value_errors, int num_nodes_local, void* norm_fcn_ctx, skip_element_fcn_t skip_element_fcn) {
   // d4est_norms.c:16-56: the context's p4est and mesh objects are handed on; sqrt of the LOCAL sum
   need_no_skip(skip_element_fcn, "d4est_norms_fcn_L2");

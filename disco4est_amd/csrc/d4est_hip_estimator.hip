@@ -133,6 +133,37 @@ __global__ __launch_bounds__(256) void est_residual_kernel(const double* __restr
   }
 }
 
+// term0 of d4est_estimator_bi_new_compute with use_pointwise_residual (src/Estimators/d4est_estimator_bi_new.c:471-487): the residual is
+// given at the quadrature nodes, term0 = h^2 / deg^2 sum_q w_q J_q r_q^2 (d4est_quadrature_innerproduct: no interpolation).  One
+// 256-thread workgroup per element, strided partial sums and a fixed tree reduction.
+__global__ __launch_bounds__(256) void est_pointwise_residual_kernel(const double* __restrict__ rq, const double* __restrict__ J,
+                                                                     const int* __restrict__ elem_ids, const int* __restrict__ qs_list,
+                                                                     int n_elem, const double* __restrict__ w, int NQ, int deg,
+                                                                     const double* __restrict__ diam, double* __restrict__ term0) {
+  __shared__ double red[256];
+  const int NQ2 = NQ * NQ, NQ3 = NQ2 * NQ;
+  for (int el = blockIdx.x; el < n_elem; el += gridDim.x) {
+    const int e = elem_ids[el], qs = qs_list[el];
+    double acc = 0.0;
+    for (int idx = threadIdx.x; idx < NQ3; idx += blockDim.x) {
+      const int ab = idx % NQ2, c = idx / NQ2;
+      const double r = rq[qs + idx];
+      acc += w[ab % NQ] * w[ab / NQ] * w[c] * J[qs + idx] * r * r;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+      if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      const double h = diam[e];
+      term0[e] = red[0] * (h * h / (double)(deg * deg));
+    }
+    __syncthreads();
+  }
+}
+
 // terms 1 - 3 and eta2: one wavefront per element, lanes over the mortar quadrature nodes, mortars in sequence
 __global__ __launch_bounds__(64) void est_face_kernel(const double* __restrict__ qtrace, const double* __restrict__ ghost_qtrace,
                                                       const EstMortar* __restrict__ md, const int* __restrict__ elem_first,
@@ -268,7 +299,7 @@ void estimator_setup(d4est_hip_plan* plan, const double* sj, const double* n, co
 }
 
 void estimator_compute(d4est_hip_plan* plan, const double* u, const double* ghost_trace, const double* residual, const double* diam,
-                       const double* g_lobatto, double* eta2, double* terms) {
+                       const double* g_lobatto, double* eta2, double* terms, bool pointwise) {
   EstHost* x = est_of(plan);
   if (!plan->est_requested) D4EST_HIP_ABORT("estimator_bi: the plan has no estimator set-up (d4est_hip_plan_set_estimator)");
   if (!x) D4EST_HIP_ABORT("estimator_bi: call d4est_hip_plan_set_estimator before the mortar factors (plan_set_mortar_geometry)");
@@ -290,6 +321,12 @@ void estimator_compute(d4est_hip_plan* plan, const double* u, const double* ghos
   for (const Bucket& bk : plan->buckets) {
     if (bk.n_elem == 0) continue;
     const int N = bk.N, NQ = bk.NQ;
+    if (pointwise) {
+      hipLaunchKernelGGL(est_pointwise_residual_kernel, dim3(std::min(bk.n_elem, 16384)), dim3(256), 0, plan->stream, residual, plan->d_J,
+                         plan->d_elem_ids + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_w, NQ, bk.deg, diam, t);
+      HIP_CHECK(hipGetLastError());
+      continue;
+    }
     const size_t lds = residual_lds_bytes(N, NQ);
     if (lds > 160 * 1024) D4EST_HIP_ABORT("estimator_bi: (deg, deg_quad) = (%d, %d) needs %zu bytes of LDS", bk.deg, bk.deg_quad, lds);
     hipLaunchKernelGGL(est_residual_kernel, dim3(std::min(bk.n_elem, 16384)), dim3(256), lds, plan->stream, residual, plan->d_J,

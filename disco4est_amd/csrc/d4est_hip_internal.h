@@ -177,6 +177,9 @@ struct d4est_hip_plan {
   int face_h_type = D4EST_HIP_FACE_H_EQ_J_DIV_SJ_QUAD;
   int volume_h_type = D4EST_HIP_VOL_H_EQ_DIAM;
   void* sizes = nullptr;           // d4est_hip::SizeHost
+
+  // Hessian-trace coefficients (d4est_hip_hessian.hip): allocated by d4est_hip_plan_set_hessian_*; plans that never call them keep nullptr
+  void* hess = nullptr;            // d4est_hip::HessHost
 };
 
 namespace d4est_hip {
@@ -347,8 +350,18 @@ MortarRecords mortar_records_upload(d4est_hip_plan* plan, const char* who, const
 void estimator_setup(d4est_hip_plan* plan, const double* sj, const double* n, const double* drst_m, const double* drst_p, const double* hm,
                      const double* hp);
 void estimator_destroy(d4est_hip_plan* plan);
+// pointwise: `residual` holds local_nodes_quad values at the quadrature nodes and term 0 is h^2 / p^2 sum_q w J r^2 (no interpolation)
 void estimator_compute(d4est_hip_plan* plan, const double* u, const double* ghost_trace, const double* residual, const double* diam,
-                       const double* g_lobatto, double* eta2, double* terms);
+                       const double* g_lobatto, double* eta2, double* terms, bool pointwise = false);
+
+// d4est_hip_hessian.hip: the coefficients of the Hessian trace on a plan and its apply
+void hessian_set_brick(d4est_hip_plan* plan, const int* elem_dq, double root_len, const double* extents);
+void hessian_set_analytic(d4est_hip_plan* plan, const TreeMapParams& P, const std::vector<CellDesc>& cells, double root_len);
+void hessian_set_numerical(d4est_hip_plan* plan, const double* xyz_lobatto, const double* rst_xyz_quad, int on_device);
+int hessian_info(const d4est_hip_plan* plan);
+int hessian_supported(const d4est_hip_plan* plan);
+void hessian_trace(d4est_hip_plan* plan, const double* u, double* del2u_quad);
+void hessian_destroy(d4est_hip_plan* plan);
 
 // d4est_hip_norms.hip
 void norms_setup(d4est_hip_plan* plan, const double* sj, const double* n, const double* hm, const double* hp);

@@ -22,6 +22,11 @@
 //
 // One evaluation gives x and dx/dxi (wedge_blended / wedge_plain -> wedge_to_xyz); a caller that uses one of them leaves the
 // other to dead-code elimination.  The same inline functions run on the host (d4est_hip_tree_map).
+//
+// Second derivatives d^2 x_i / d xi_j d xi_k (tree_map_d2, for the Hessian trace of d4est_hip_hessian.hip) are the chain rule through
+// the same functions -- shell_radius_d2, wedge_blended_d2, wedge_plain_d2, the picks of wedge_to_xyz, zero on the centre cube -- so
+// they are the derivatives of the map the factors come from, not a transcription of the reference's machine-generated closed forms
+// (d4est_geometry_cubed_sphere.c:585-790, whose `c` is built from s instead of t at :629).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -153,6 +158,124 @@ __host__ __device__ inline void tree_map_x(const TreeMapParams& P, int tree, con
   tree_map_eval(P, tree, xi, X, D);
 }
 
+// ---- second derivatives ----------------------------------------------------------------------------------------------------------
+// d^2 R / dc^2 of shell_radius
+__host__ __device__ inline double shell_radius_d2(double Ra, double Rb, int compactify, double c) {
+  if (!compactify) return 0.0;
+  const double m = 1.0 / (1.0 / Rb - 1.0 / Ra), t = (Ra - 2.0 * Rb) / (Ra - Rb);
+  return 2.0 * m / ((c - t) * (c - t) * (c - t));
+}
+
+// Both wedges are v = (q x, q y, q) with q = R(c) / sqrt(S): from R, S, x, y and their first and second derivatives with respect to
+// (a, b, c) -- the upper triangles of the second derivatives, [j][k] with j <= k -- the second derivatives of v with respect to xi,
+// H[i][j][k] = d^2 v_i / d xi_j d xi_k.  The lower triangle is a copy of the upper: exactly symmetric.
+__host__ __device__ inline void wedge_second(double R, double dR, double d2R, double S, const double dS[3], const double d2S[3][3],
+                                             double x, const double dx[3], const double d2x[3][3], double y, const double dy[3],
+                                             const double d2y[3][3], double H[3][3][3]) {
+  const double rs = 1.0 / sqrt(S), rs3 = rs * rs * rs, rs5 = rs3 * rs * rs, q = R * rs;
+  const double sc[3] = {2.0, 2.0, 1.0};   // d(a, b, c) / d xi
+  double drs[3], dq[3];
+  for (int k = 0; k < 3; ++k) {
+    drs[k] = -0.5 * rs3 * dS[k];
+    dq[k] = R * drs[k] + (k == 2 ? dR * rs : 0.0);
+  }
+  for (int j = 0; j < 3; ++j)
+    for (int k = j; k < 3; ++k) {
+      const double d2rs = 0.75 * rs5 * dS[j] * dS[k] - 0.5 * rs3 * d2S[j][k];
+      double d2q = R * d2rs;
+      if (j == 2) d2q += dR * drs[k];
+      if (k == 2) d2q += dR * drs[j];
+      if (j == 2 && k == 2) d2q += d2R * rs;
+      const double s = sc[j] * sc[k];
+      H[0][j][k] = H[0][k][j] = (d2q * x + dq[j] * dx[k] + dq[k] * dx[j] + q * d2x[j][k]) * s;
+      H[1][j][k] = H[1][k][j] = (d2q * y + dq[j] * dy[k] + dq[k] * dy[j] + q * d2y[j][k]) * s;
+      H[2][j][k] = H[2][k][j] = d2q * s;
+    }
+}
+
+// second derivatives of wedge_blended's v with respect to xi
+__host__ __device__ inline void wedge_blended_d2(double Ra, double Rb, int compactify, const double xi[3], double H[3][3][3]) {
+  const double kPi4 = 0.78539816339744830962;
+  const double a = 2.0 * xi[0] - 1.0, b = 2.0 * xi[1] - 1.0, c = xi[2] + 1.0;
+  double R, dR;
+  shell_radius(Ra, Rb, compactify, c, R, dR);
+  const double d2R = shell_radius_d2(Ra, Rb, compactify, c);
+  const double p = 2.0 - c;
+  const double tx = tan(a * kPi4), ty = tan(b * kPi4);
+  const double dtx = kPi4 * (1.0 + tx * tx), dty = kPi4 * (1.0 + ty * ty);
+  const double d2tx = 2.0 * kPi4 * tx * dtx, d2ty = 2.0 * kPi4 * ty * dty;
+  const double x = p * a + (1.0 - p) * tx, y = p * b + (1.0 - p) * ty;
+  const double S = 1.0 + (1.0 - p) * (tx * tx + ty * ty) + 2.0 * p;
+  // with respect to (a, b, c); dp/dc = -1
+  const double dx[3] = {p + (1.0 - p) * dtx, 0.0, tx - a};
+  const double dy[3] = {0.0, p + (1.0 - p) * dty, ty - b};
+  const double dS[3] = {(1.0 - p) * 2.0 * tx * dtx, (1.0 - p) * 2.0 * ty * dty, (tx * tx + ty * ty) - 2.0};
+  const double d2x[3][3] = {{(1.0 - p) * d2tx, 0.0, dtx - 1.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  const double d2y[3][3] = {{0.0, 0.0, 0.0}, {0.0, (1.0 - p) * d2ty, dty - 1.0}, {0.0, 0.0, 0.0}};
+  const double d2S[3][3] = {{(1.0 - p) * 2.0 * (dtx * dtx + tx * d2tx), 0.0, 2.0 * tx * dtx},
+                            {0.0, (1.0 - p) * 2.0 * (dty * dty + ty * d2ty), 2.0 * ty * dty},
+                            {0.0, 0.0, 0.0}};
+  wedge_second(R, dR, d2R, S, dS, d2S, x, dx, d2x, y, dy, d2y, H);
+}
+
+// second derivatives of wedge_plain's v with respect to xi
+__host__ __device__ inline void wedge_plain_d2(double Ra, double Rb, int compactify, const double xi[3], double H[3][3][3]) {
+  const double kPi4 = 0.78539816339744830962;
+  const double a = 2.0 * xi[0] - 1.0, b = 2.0 * xi[1] - 1.0, c = xi[2] + 1.0;
+  double R, dR;
+  shell_radius(Ra, Rb, compactify, c, R, dR);
+  const double d2R = shell_radius_d2(Ra, Rb, compactify, c);
+  const double x = tan(a * kPi4), y = tan(b * kPi4);
+  const double x1 = kPi4 * (1.0 + x * x), y1 = kPi4 * (1.0 + y * y);
+  const double x2 = 2.0 * kPi4 * x * x1, y2 = 2.0 * kPi4 * y * y1;
+  const double S = x * x + y * y + 1.0;
+  const double dx[3] = {x1, 0.0, 0.0}, dy[3] = {0.0, y1, 0.0};
+  const double dS[3] = {2.0 * x * x1, 2.0 * y * y1, 0.0};
+  const double d2x[3][3] = {{x2, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  const double d2y[3][3] = {{0.0, 0.0, 0.0}, {0.0, y2, 0.0}, {0.0, 0.0, 0.0}};
+  const double d2S[3][3] = {{2.0 * (x1 * x1 + x * x2), 0.0, 0.0}, {0.0, 2.0 * (y1 * y1 + y * y2), 0.0}, {0.0, 0.0, 0.0}};
+  wedge_second(R, dR, d2R, S, dS, d2S, x, dx, d2x, y, dy, d2y, H);
+}
+
+// d^2 x_i / d xi_j d xi_k of the map P.type (same dispatch as tree_map_eval; the caller has checked type, tree and flags)
+__host__ __device__ inline void tree_map_d2(const TreeMapParams& P, int tree, const double xi[3], double H[3][3][3]) {
+  double h[3][3][3];
+  bool cube = false;
+  if (P.type == 1) {
+    if (tree == 6) cube = true;
+    else wedge_blended_d2(P.R0, P.R1, P.compactify, xi, h);
+  } else if (tree < 6) {
+    wedge_plain_d2(P.R1, P.R2, P.compactify_outer, xi, h);
+  } else if (tree == 12) {
+    cube = true;
+  } else if (P.type == 3) {
+    wedge_plain_d2(P.R0, P.R1, P.compactify, xi, h);
+  } else {
+    wedge_blended_d2(P.R0, P.R1, 0, xi, h);
+  }
+  if (cube) {   // centre_cube is linear
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j)
+        for (int k = 0; k < 3; ++k) H[i][j][k] = 0.0;
+    return;
+  }
+  // the signed picks of wedge_to_xyz
+  const int wedge = tree % 6;
+  const int pk0 = (wedge == 3 || wedge == 5) ? 2 : (wedge == 4 ? 1 : 0);
+  const int pk1 = (wedge == 0 || wedge == 2) ? 2 : (wedge == 1 ? 1 : 0);
+  const int pk2 = (wedge == 1 || wedge == 4) ? 2 : 1;
+  const double sg0 = (wedge >= 4) ? -1.0 : 1.0;
+  const double sg1 = (wedge == 1 || wedge == 2) ? 1.0 : -1.0;
+  const double sg2 = (wedge >= 2 && wedge <= 4) ? -1.0 : 1.0;
+  for (int j = 0; j < 3; ++j)
+    for (int k = 0; k < 3; ++k) {
+      const double h0 = h[0][j][k], h1 = h[1][j][k], h2 = h[2][j][k];
+      H[0][j][k] = sg0 * (pk0 == 0 ? h0 : pk0 == 1 ? h1 : h2);
+      H[1][j][k] = sg1 * (pk1 == 0 ? h0 : pk1 == 1 ? h1 : h2);
+      H[2][j][k] = sg2 * (pk2 == 1 ? h1 : h2);
+    }
+}
+
 // inverse and determinant of a 3 x 3 matrix
 __host__ __device__ inline double invert3(const double A[3][3], double I[3][3]) {
   const double c00 = A[1][1] * A[2][2] - A[1][2] * A[2][1], c01 = A[1][2] * A[2][0] - A[1][0] * A[2][2], c02 = A[1][0] * A[2][1] - A[1][1] * A[2][0];
@@ -189,6 +312,19 @@ __host__ __device__ inline void cell_x(const TreeMapParams& P, const CellDesc& c
   double xi[3];
   for (int d = 0; d < 3; ++d) xi[d] = ((double)cell.q[d] + 0.5 * (double)cell.dq * (r[d] + 1.0)) / root_len;
   tree_map_x(P, cell.tree, xi, x);
+}
+
+// d^2 x / d r d r of `cell` at reference point r: the tree-level second derivative times (dq / (2 root_len))^2
+__host__ __device__ inline void cell_d2xdr(const TreeMapParams& P, const CellDesc& cell, double root_len, const double r[3],
+                                           double d2[3][3][3]) {
+  double xi[3];
+  for (int d = 0; d < 3; ++d) xi[d] = ((double)cell.q[d] + 0.5 * (double)cell.dq * (r[d] + 1.0)) / root_len;
+  double H[3][3][3];
+  tree_map_d2(P, cell.tree, xi, H);
+  const double s = 0.5 * (double)cell.dq / root_len, s2 = s * s;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j)
+      for (int k = 0; k < 3; ++k) d2[i][j][k] = H[i][j][k] * s2;
 }
 
 }  // namespace d4est_hip

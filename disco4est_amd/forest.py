@@ -162,6 +162,22 @@ def cube_rotations():
 # ---------------------------------------------------------------------------------------------------------------------
 # tree maps: x(tree, xi) and dx/dxi(tree, xi) for tree coordinates xi in [0,1]^3
 # ---------------------------------------------------------------------------------------------------------------------
+def complex_step_second_derivatives(mapping, tree, xi):
+    """d^2 x_i / d xi_j d xi_k [n, 3, 3, 3] of a tree map as the complex-step derivative of its own ``jacobian``: Im J(xi + i h e_k) / h
+    with h = 1e-30 has no subtractive cancellation, so it is the derivative of the Jacobian to rounding, in float64 or (xi in
+    numpy.longdouble) in long double.  Symmetrised over (j, k), which differ by rounding only."""
+    xi = np.asarray(xi)
+    real = xi.dtype if xi.dtype == np.longdouble else np.dtype(np.float64)
+    ctype = np.clongdouble if real == np.longdouble else np.complex128
+    h = real.type(1e-30)
+    H = np.empty((xi.shape[0], 3, 3, 3), dtype=real)
+    for k in range(3):
+        z = xi.astype(ctype)
+        z[:, k] += 1j * h
+        H[:, :, :, k] = np.imag(mapping.jacobian(tree, z)) / h
+    return 0.5 * (H + np.swapaxes(H, 2, 3))
+
+
 class TrilinearMap:
     """The vertex map p4est itself uses (trilinear interpolation of the tree's 8 vertices), optionally followed by a smooth warp of
     physical space ``warp.x(X,Y,Z)``, ``warp.jacobian(X,Y,Z)`` (e.g. mesh.SineMap) that makes every element curved."""
@@ -253,15 +269,21 @@ class CubedSphere7Map:
         return np.stack([s * comp[i] for (i, s) in self._PICK[tree]], axis=1)
 
     def jacobian(self, tree, xi):
+        """dx/dxi [n, 3, 3] in the dtype of xi: float64 as a rule; complex or long-double xi (complex_step_second_derivatives, the
+        long-double dense references) is carried through"""
         if tree == 6:
-            return np.broadcast_to(2 * self.Clength * np.eye(3), (xi.shape[0], 3, 3)).copy()
+            return np.broadcast_to(2 * self.Clength * np.eye(3), (xi.shape[0], 3, 3)).astype(xi.dtype)
         _, _, _, dqx, dqy, dq = self._wedge(xi)
         comp = (dqx, dqy, dq)
-        D = np.zeros((xi.shape[0], 3, 3))
+        D = np.zeros((xi.shape[0], 3, 3), dtype=xi.dtype)
         for row, (i, s) in enumerate(self._PICK[tree]):
             for k in range(3):
                 D[:, row, k] = s * comp[i][k]
         return D
+
+    def second_derivatives(self, tree, xi):
+        """d^2 x_i / d xi_j d xi_k, [n, 3, 3, 3] (complex_step_second_derivatives of jacobian)"""
+        return complex_step_second_derivatives(self, tree, xi)
 
 
 def cubed_sphere_7tree_connectivity():
@@ -323,16 +345,21 @@ class _ShellsMap:
         return np.stack([s * comp[i] for (i, s) in CubedSphere7Map._PICK[tree % 6]], axis=1)
 
     def jacobian(self, tree, xi):
+        """dx/dxi [n, 3, 3] in the dtype of xi (float64, complex or long double), as CubedSphere7Map.jacobian"""
         assert 0 <= tree < self.num_trees
         if tree == 12:
-            return np.broadcast_to(2 * self.Clength * np.eye(3), (xi.shape[0], 3, 3)).copy()
+            return np.broadcast_to(2 * self.Clength * np.eye(3), (xi.shape[0], 3, 3)).astype(xi.dtype)
         _, _, _, dqx, dqy, dq = self._wedge(tree, xi)
         comp = (dqx, dqy, dq)
-        D = np.zeros((xi.shape[0], 3, 3))
+        D = np.zeros((xi.shape[0], 3, 3), dtype=xi.dtype)
         for row, (i, s) in enumerate(CubedSphere7Map._PICK[tree % 6]):
             for k in range(3):
                 D[:, row, k] = s * comp[i][k]
         return D
+
+    def second_derivatives(self, tree, xi):
+        """d^2 x_i / d xi_j d xi_k, [n, 3, 3, 3] (complex_step_second_derivatives of jacobian)"""
+        return complex_step_second_derivatives(self, tree, xi)
 
     @property
     def params(self):

@@ -180,6 +180,12 @@ void d4est_hip_plan_compute_xyz_analytic(d4est_hip_plan_t* plan, int geom_type, 
  * x_out[3] = x(tree, xi) and dxdxi_out[9] = d x_i / d xi_j (row-major) at tree coordinates xi[3] in [0,1]^3; either output may be
  * NULL.  Returns 0, or non-zero -- without aborting -- for an unknown type, bad radii, a rejected flag or a tree out of range. */
 int d4est_hip_tree_map(int geom_type, const double* params, int tree, const double* xi, double* x_out, double* dxdxi_out);
+/* The map's second derivatives on the HOST, likewise without a HIP call: d2_out[9 i + 3 j + k] = d^2 x_i / d xi_j d xi_k at xi[3], the
+ * chain rule through the functions that give x and dx/dxi (what d4est_geometry_cubed_sphere_D2X, src/Geometry/
+ * d4est_geometry_cubed_sphere.c:585-790, gives for the 13-tree sphere from machine-generated closed forms; those are not transcribed,
+ * and that file's `c` is built from s instead of t at :629).  Exactly symmetric in (j, k); zero on the centre cube.  Return codes:
+ * those of d4est_hip_tree_map. */
+int d4est_hip_tree_map_d2(int geom_type, const double* params, int tree, const double* xi, double* d2_out /*27*/);
 
 /* ---- volume kernels (device vectors of local_nodes doubles) ---------------------- */
 /* Au = K u : replaces d4est_laplacian_apply_stiffness_matrix (src/dGMath/d4est_laplacian.c:198-234)
@@ -326,9 +332,50 @@ void d4est_hip_plan_set_estimator(d4est_hip_plan_t* plan, int gradu_fcn, int u_f
  * at p = 19 (160 KB); a plan beyond it aborts here. */
 void d4est_hip_estimator_bi(d4est_hip_plan_t* plan, const double* u_dev, const double* ghost_trace_dev, const double* residual_dev,
                             const double* diam_dev, const double* g_lobatto_dev, double* eta2_dev, double* terms_dev);
+/* The estimator with the POINTWISE (strong-form) residual: d4est_estimator_bi_new_compute(..., use_pointwise_residual = 1)
+ * (src/Estimators/d4est_estimator_bi_new.c:386-567), what the *_anares drivers call (src/Problems/cds_anares.c:303-343).  Identical to
+ * d4est_hip_estimator_bi except for term 0: residual_quad_dev holds local_nodes_quad values r_q at the quadrature nodes and
+ * term 0 = h^2 / deg^2 sum_q w_q J_q r_q^2 (:471-487, d4est_quadrature_innerproduct; no interpolation, no LDS limit).  Terms 1 - 3 and
+ * eta2 take the same kernels as d4est_hip_estimator_bi.  Out of scope: a compactified factor set distinct from the physical one
+ * (d4est_factors_compactified != d4est_factors_physical) and estimator_vtk_per_face. */
+void d4est_hip_estimator_bi_pointwise(d4est_hip_plan_t* plan, const double* u_dev, const double* ghost_trace_dev,
+                                      const double* residual_quad_dev, const double* diam_dev, const double* g_lobatto_dev,
+                                      double* eta2_dev, double* terms_dev);
 /* 1 and the three ids and the prefactor of d4est_hip_plan_set_estimator (either output may be NULL) when the plan has the estimator,
  * else 0 -- for hosts that check a caller's penalty functions against the plan (the compat library's d4est_estimator_bi_compute) */
 int d4est_hip_plan_estimator_info(const d4est_hip_plan_t* plan, int* ids, double* penalty_prefactor);
+/* ---- the Laplacian of a field at the quadrature nodes (csrc/d4est_hip_hessian.hip) ---------------------------------------------------
+ * d4est_hessian_compute_hessian_trace_of_field_on_quadrature_points (src/dGMath/d4est_hessian.c:270-368).  With R_ai = dr_a/dx_i,
+ *   Lap u (q) = sum_b c_b(q) V(D_b u)(q) + sum_ab G_ab(q) V(D_a D_b u)(q),   G_ab = sum_i R_ai R_bi,
+ *   c_b = sum_i sum_a R_ai d2rdrdx[b][i][a],   d2rdrdx[m][n][k] = - sum_al R_ml R_an d^2 x_l / dr_a dr_k      (:41-58, :127-138).
+ * The nine coefficients per quadrature node depend on the mesh only; one of the three set-up calls forms them once, into plan-owned
+ * storage of 9 local_nodes_quad doubles that plan_destroy frees.  Plans that never call them allocate nothing and run as before.
+ *   _brick      d^2x/dr dr = 0 (src/Geometry/d4est_geometry_brick.c:8): c = 0, G diagonal; arguments as plan_set_geometry_brick.
+ *   _analytic   HESSIAN_ANALYTICAL (:180-226): dx/dr and d^2x/dr dr of the analytic tree map at every quadrature node (Gauss or Lobatto
+ *               by the plan's quad_type), dx/dr inverted to R; arguments, flag rules and rejections as plan_set_geometry_analytic.
+ *   _numerical  HESSIAN_NUMERICAL (:227-262): d^2 x_d1 / dr_d2 dr_d3 = V(D_d3 D_d2 x_d1) from xyz_lobatto (x | y | z, 3 local_nodes);
+ *               R from rst_xyz_quad (the reference's SoA layout, 9 local_nodes_quad) or, when that is NULL, from V(D x) inverted as
+ *               plan_set_geometry_numerical forms it.  on_device: both arrays are device (1) or host (0) pointers.
+ * All run on the plan's stream with no host synchronisation after the uploads (device arrays handed over with on_device = 1 must
+ * stay valid until the stream has passed the call); the numerical form's scratch is released later, by the first apply that finds the
+ * set-up kernels finished.  A later set-up call replaces the coefficients (it waits for the earlier one's kernels).  Aborts ([D4EST_HIP_ABORT]) on a NULL plan, a bad
+ * type / tree / flag / extent, or a (deg, deg_quad) bucket beyond the apply kernel's LDS: ask d4est_hip_plan_hessian_supported first. */
+void d4est_hip_plan_set_hessian_brick(d4est_hip_plan_t* plan, const int* elem_dq, double root_len, const double* extents);
+void d4est_hip_plan_set_hessian_analytic(d4est_hip_plan_t* plan, int geom_type, const double* params, const int* elem_tree,
+                                         const int* elem_q, const int* elem_dq, double root_len);
+void d4est_hip_plan_set_hessian_numerical(d4est_hip_plan_t* plan, const double* xyz_lobatto, const double* rst_xyz_quad, int on_device);
+/* 0 none, 1 brick, 2 analytic, 3 numerical */
+int d4est_hip_plan_hessian_info(const d4est_hip_plan_t* plan);
+/* 1 if every (deg, deg_quad) bucket of the plan fits the apply kernel's LDS, else 0; never aborts on a valid plan.  The kernel holds
+ * one element's u, three N x N and six N x NQ planes and three N x NQ tables: 8 (N^3 + 3 N^2 + 9 N NQ) bytes <= 163840 (160 KB),
+ * N = deg + 1, NQ = deg_quad + 1.  Every deg <= 19 fits with any deg_quad a plan accepts (N = 20, NQ = 24: 108160 bytes);
+ * the first that does not is deg = deg_quad = 23 (165888 bytes). */
+int d4est_hip_plan_hessian_supported(const d4est_hip_plan_t* plan);
+/* del2u_quad_dev[local_nodes_quad] (OVERWRITTEN) <- u_dev[local_nodes]: replaces the element loop of :291-359, 9 apply_dij and 12
+ * interpolations per element.  One workgroup per element per (deg, deg_quad) bucket on the plan's stream, no host synchronisation, no
+ * atomics: bit-identical from call to call.  The symmetric pairs D_a D_b = D_b D_a are folded (the reference sums all nine) and the
+ * 1-D tables B D and B D D are formed once, so the result differs from the reference's by rounding.  Aborts without a set-up call. */
+void d4est_hip_hessian_trace(d4est_hip_plan_t* plan, const double* u_dev, double* del2u_quad_dev);
 /* ---- element size parameters and [mesh_parameters] face_h_type / volume_h_type (csrc/d4est_hip_sizes.hip) ----------------------------
  * The ids follow the reference's enums d4est_mesh_face_h_t / d4est_mesh_volume_h_t (src/Mesh/d4est_mesh.h:33-48). */
 #define D4EST_HIP_FACE_H_EQ_J_DIV_SJ_QUAD 0                 /* J / sj at every mortar quadrature node (the default) */

@@ -303,6 +303,14 @@ double d4est_quadrature_innerproduct(d4est_operators_t *d4est_ops,d4est_geometry
  * device (d4est_hip_compute_dudr).  The ghost elements' part needs the ghost layer, which is opaque here: dudr_ghost is not written,
  * and a bound plan that has ghost sides aborts when dudr_ghost is asked for (the engine exchanges traces, not element data) */
 void d4est_laplacian_compute_dudr(p4est_t *p4est,d4est_ghost_t *d4est_ghost,d4est_ghost_data_t *d4est_ghost_data,d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geom,d4est_quadrature_t *d4est_quad,d4est_mesh_data_t *d4est_factors,double *dudr_local[3],double *dudr_ghost[3],double *D4EST_RESTRICT u,int local_nodes,int which_field);
+/* src/dGMath/d4est_hessian.h (d4est_hessian.c:270-368) on the bound plan: del2field[local_nodes_quad] = the Laplacian of the host
+ * vector field_lobatto[local_nodes] at the quadrature nodes (d4est_hip_hessian_trace).  The opaque pointers are not read.  The plan must
+ * carry the coefficients of the form compute_method names -- HESSIAN_ANALYTICAL: d4est_hip_plan_set_hessian_analytic or _brick (the
+ * brick's D2X is analytic and zero), HESSIAN_NUMERICAL: _set_hessian_numerical -- and any other combination aborts */
+typedef int d4est_hessian_compute_method_t;                     /* enum {HESSIAN_ANALYTICAL, HESSIAN_NUMERICAL}, d4est_hessian.h:14 */
+#define HESSIAN_ANALYTICAL 0
+#define HESSIAN_NUMERICAL 1
+void d4est_hessian_compute_hessian_trace_of_field_on_quadrature_points(p4est_t *p4est,d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geom,d4est_quadrature_t *d4est_quad,d4est_mesh_data_t *d4est_factors,d4est_hessian_compute_method_t compute_method,double *field_lobatto,double *del2field);
 #endif /* D4EST_HIP_COMPAT_NO_TYPES */
 
 /* ---- binding (not in the reference) ------------------------------------------------------------------------------------------ */
