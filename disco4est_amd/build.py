@@ -34,6 +34,7 @@ SOURCES = [
     "d4est_hip_amr.hip",
     "d4est_hip_sizes.hip",
     "d4est_hip_hessian.hip",
+    "d4est_hip_nonlinear.hip",
 ]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]

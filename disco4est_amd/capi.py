@@ -138,6 +138,13 @@ SIGNATURES = {
     "d4est_hip_cg_solve": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_double_p]),
     "d4est_hip_cg_solve_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_double_p]),
     "d4est_hip_fcg_solve": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp, _vp, _c_double_p]),
+    "d4est_hip_plan_set_nonlinear_power": (None, [_vp, _vp, _vp, ctypes.c_int]),
+    "d4est_hip_apply_nonlinear_term": (None, [_vp, _vp, ctypes.c_int, _vp]),
+    "d4est_hip_plan_nonlinear_fused": (ctypes.c_int, [_vp]),
+    "d4est_hip_plan_linearise": (None, [_vp, _vp]),
+    "d4est_hip_build_residual": (None, [_vp, _vp, _vp, _vp, _vp]),
+    "d4est_hip_newton_solve": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _c_double_p, _c_int_p]),
     "d4est_hip_multigrid_check": (ctypes.c_int, [ctypes.c_int, _vp, _vp]),
     "d4est_hip_multigrid_create": (_vp, [ctypes.c_int, _vp, _vp]),
     "d4est_hip_multigrid_destroy": (None, [_vp]),
@@ -838,6 +845,27 @@ class Plan:
                                               int(imax), float(atol), float(rtol), hist.ctypes.data_as(_c_double_p))
         return u, Au, it, hist[:it + 1]
 
+    def _pc_pair(self, pc):
+        """(d4est_hip_pc_fn, ctx) of a preconditioner argument: None, an object with `pc_fn` / `pc_ctx`, or a Python callable"""
+        if pc is None:
+            return None, None
+        if hasattr(pc, "pc_fn"):
+            return ctypes.c_void_p(pc.pc_fn), ctypes.c_void_p(pc.pc_ctx)
+
+        def call(_ctx, r, z):
+            try:
+                pc(r, z)
+            except BaseException:   # (as set_comm: a dropped exception would leave z unwritten)
+                import sys
+                import traceback
+                sys.stderr.write("[D4EST_HIP_ABORT] exception in a preconditioner callback:\n")
+                traceback.print_exc()
+                sys.stderr.flush()
+                os.abort()
+        cb = self.PC_FN(call)
+        self._cb_pc = cb
+        return ctypes.cast(cb, ctypes.c_void_p), None
+
     def fcg_solve(self, u, rhs, Au, imax, atol, rtol, pc=None):
         """FCG on apply_lhs from u (advanced in place); returns (iterations, history |r_k|).  pc: None (the identity), an object
         with `pc_fn` / `pc_ctx` (a C d4est_hip_pc_fn and its context, passed straight through: no Python in the loop), or a
@@ -845,26 +873,71 @@ class Plan:
         for t in (u, rhs, Au):
             assert t.numel() == self.local_nodes
         hist = np.zeros(max(int(imax), 1))
-        fn, ctx = None, None
-        if pc is not None and hasattr(pc, "pc_fn"):
-            fn, ctx = ctypes.c_void_p(pc.pc_fn), ctypes.c_void_p(pc.pc_ctx)
-        elif pc is not None:
-            def call(_ctx, r, z):
-                try:
-                    pc(r, z)
-                except BaseException:   # (as set_comm: a dropped exception would leave z unwritten)
-                    import sys
-                    import traceback
-                    sys.stderr.write("[D4EST_HIP_ABORT] exception in a preconditioner callback:\n")
-                    traceback.print_exc()
-                    sys.stderr.flush()
-                    os.abort()
-            cb = self.PC_FN(call)
-            self._cb_pc = cb
-            fn = ctypes.cast(cb, ctypes.c_void_p)
+        fn, ctx = self._pc_pair(pc)
         it = self.lib.d4est_hip_fcg_solve(self.handle, _ptr(u), _ptr(rhs), _ptr(Au), int(imax), float(atol), float(rtol), fn, ctx,
                                           hist.ctypes.data_as(_c_double_p))
         return it, hist[:it]
+
+    # ---- nonlinear problems: the power term a (b + u)^k, its linearisation and the Newton loop (d4est_hip_nonlinear.hip)
+    LINEARISE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p)
+
+    def set_nonlinear_power(self, a_quad, b_quad, k):
+        """registers f(x, u) = a (b + u)^k: float64 CUDA tensors of local_nodes_quad entries (b_quad None: b = 0; a_quad None: the term
+        is off).  The VALUES ARE CAPTURED by this call, as by set_lhs_coefficient; |k| <= 16"""
+        for t in (a_quad, b_quad):
+            assert t is None or t.numel() == self.local_nodes_quad
+        self.lib.d4est_hip_plan_set_nonlinear_power(self.handle, _ptr(a_quad) if a_quad is not None else None,
+                                                    _ptr(b_quad) if b_quad is not None else None, int(k))
+
+    def apply_nonlinear_term(self, u, out, beta=0):
+        """out = beta out + V^T W J a (b + V u)^k (beta 0 or 1), one kernel where nonlinear_fused() holds"""
+        assert u.numel() == self.local_nodes and out.numel() == self.local_nodes
+        self.lib.d4est_hip_apply_nonlinear_term(self.handle, _ptr(u), int(beta), _ptr(out))
+
+    def nonlinear_fused(self):
+        return bool(self.lib.d4est_hip_plan_nonlinear_fused(self.handle))
+
+    def linearise(self, u0):
+        """the zeroth-order coefficient of apply_lhs becomes c = k a (b + V u0)^(k-1): set_lhs_coefficient(c) in one kernel"""
+        assert u0.numel() == self.local_nodes
+        self._lhs_coeff = None
+        self.lib.d4est_hip_plan_linearise(self.handle, _ptr(u0))
+
+    def build_residual(self, u, out, rhs=None, ghost_trace=None):
+        """out = A u + N(u) - rhs with the boundary data currently set on the plan"""
+        assert u.numel() == self.local_nodes and out.numel() == self.local_nodes
+        self.lib.d4est_hip_build_residual(self.handle, _ptr(u), _ptr(ghost_trace) if ghost_trace is not None else None,
+                                          _ptr(rhs) if rhs is not None else None, _ptr(out))
+
+    def newton_solve(self, u, rhs=None, g_lobatto=None, atol=1e-15, rtol=1e-10, imin=0, imax=10, krylov_imax=200, krylov_atol=1e-15,
+                     krylov_rtol=1e-10, pc=None, on_linearise=None):
+        """d4est_solver_newton_solve with FCG on u (advanced in place); g_lobatto: Dirichlet data as a float64 CUDA tensor or None; pc as
+        in fcg_solve; on_linearise(u0_ptr): a Python callable run after every linearisation (refresh the preconditioner there).
+        Returns (ierr, iterations, history |F| of iterations + 1 entries)"""
+        assert u.numel() == self.local_nodes and (rhs is None or rhs.numel() == self.local_nodes)
+        assert g_lobatto is None or g_lobatto.numel() == self.lib.d4est_hip_plan_bndry_nodes(self.handle)
+        fn, ctx = self._pc_pair(pc)
+        cb = None
+        if on_linearise is not None:
+            def call(_ctx, u0):
+                try:
+                    on_linearise(u0)
+                except BaseException:   # (as set_comm: a dropped exception would leave the preconditioner stale)
+                    import sys
+                    import traceback
+                    sys.stderr.write("[D4EST_HIP_ABORT] exception in a linearisation callback:\n")
+                    traceback.print_exc()
+                    sys.stderr.flush()
+                    os.abort()
+            self._cb_lin = self.LINEARISE_FN(call)
+            cb = ctypes.cast(self._cb_lin, ctypes.c_void_p)
+        hist = np.zeros(int(imax) + 1)
+        its = ctypes.c_int(0)
+        ierr = self.lib.d4est_hip_newton_solve(self.handle, _ptr(u), _ptr(rhs) if rhs is not None else None,
+                                               _ptr(g_lobatto) if g_lobatto is not None else None, float(atol), float(rtol), int(imin),
+                                               int(imax), int(krylov_imax), float(krylov_atol), float(krylov_rtol), fn, ctx, cb, None,
+                                               hist.ctypes.data_as(_c_double_p), ctypes.byref(its))
+        return ierr, its.value, hist[:its.value + 1]
 
     def copy_blocks(self, n_blocks, src, src_off, dst, dst_off, length):
         """src/dst: float64 CUDA tensors; src_off/dst_off: int64 CUDA tensors; length: int32 CUDA tensor"""

@@ -251,6 +251,7 @@ void d4est_hip_plan_destroy(d4est_hip_plan_t* plan) {
   (void)hipFree(plan->d_lhs_block_off);
   d4est_hip::lhs_chain_destroy(plan);
   d4est_hip::krylov_destroy(plan);
+  d4est_hip::nonlinear_destroy(plan);
   (void)hipFree(plan->d_reduce); (void)hipFree(plan->d_ghost_trace);
   if (plan->h_stage) (void)hipHostFree(plan->h_stage);
   for (int i = 0; i < 4; ++i) (void)hipFree(plan->d_host[i]);

@@ -180,6 +180,9 @@ struct d4est_hip_plan {
 
   // Hessian-trace coefficients (d4est_hip_hessian.hip): allocated by d4est_hip_plan_set_hessian_*; plans that never call them keep nullptr
   void* hess = nullptr;            // d4est_hip::HessHost
+
+  // nonlinear power term f(x, u) = a (b + u)^k (d4est_hip_nonlinear.hip): allocated by d4est_hip_plan_set_nonlinear_power
+  void* nonlin = nullptr;          // d4est_hip::NonlinHost
 };
 
 namespace d4est_hip {
@@ -402,6 +405,9 @@ int cg_solve(d4est_hip_plan* plan, double* u, const double* rhs, double* Au, int
 int fcg_solve(d4est_hip_plan* plan, double* u, const double* rhs, double* Au, int imax, double atol, double rtol, d4est_hip_pc_fn pc,
               void* pc_ctx, double* hist_out);
 void krylov_destroy(d4est_hip_plan* plan);
+
+// d4est_hip_nonlinear.hip
+void nonlinear_destroy(d4est_hip_plan* plan);
 
 
 }  // namespace d4est_hip

@@ -1,0 +1,513 @@
+// The nonlinear power term f(x, u) = a(x) (b(x) + u)^k of the reference's shipped nonlinear problems on a plan: the residual term, its
+// linearisation and the Newton loop around the device FCG solve.
+//
+// Replaces, for all local elements at once:
+//   d4est_quadrature_apply_fofufofvlj + axpy 1.0   (src/Quadrature/d4est_quadrature.c:776-936, as called from
+//                                                   src/Problems/ConstantDensityStar/constant_density_star_fcns.h:360-437)
+//   the callbacks neg_2pi_rho_up1_neg5 / neg_10pi_rho_up1_neg4 (constant_density_star_fcns.h:334-357) and
+//   two_punctures_neg_1o8_K2_psi_neg7 / two_punctures_plus_7o8_K2_psi_neg8 (src/Problems/TwoPunctures/two_punctures_fcns.h:252-320)
+//   constant_density_star_build_residual           (constant_density_star_fcns.h:439-482)
+//   d4est_solver_newton_solve                      (src/Solver/d4est_solver_newton.c:135-365)
+//
+// Design (gfx950): one kernel body, templated on {term, coefficient}.  Both start with V u in registers -- the forward half of
+// mass_like_body (d4est_hip_volume.hip): NQ*NQ threads own one element, every thread ends with the NQ values of its (a, b) column at the
+// quadrature nodes.  The term form multiplies by w J a (b + V u)^k there and runs the three transposed contractions back to the nodes
+// (out = beta out + V^T W J f): u in, out out, J / a / b streamed once -- 8 + 8 + 24 r bytes per DoF, r = (NQ / N)^3, no
+// quadrature-sized temporary.  The coefficient form stops at the quadrature nodes and writes c = k a (b + V u0)^(k-1) and w J c, the two
+// arrays d4est_hip_plan_set_lhs_coefficient and the first apply_lhs after it would have produced in a copy and a second pass.
+// The power is a product of |k| factors (k < 0: one division of 1 by the product); k is wave-uniform, the loop does not diverge.
+#include <algorithm>
+#include <cmath>
+#include <mutex>
+#include <unordered_map>
+
+#include "d4est_hip_internal.h"
+#include "d4est_hip_wave.h"
+#include "d4est_hip_mwave.h"
+
+namespace d4est_hip {
+
+struct NonlinHost {
+  double* d_a = nullptr;     // plan-owned copies of the caller's arrays (local_nodes_quad each); d_a == nullptr: the term is off
+  double* d_b = nullptr;     // nullptr: b = 0
+  int k = 0;
+  double* d_uq = nullptr;    // composed path only: V u at the quadrature nodes
+  // Newton loop: F(u), the step, the Krylov solver's A u; one device scalar and its pinned host mirror
+  double *d_f = nullptr, *d_step = nullptr, *d_Au = nullptr, *d_norm = nullptr, *h_norm = nullptr;
+};
+
+static NonlinHost* host_of(const d4est_hip_plan* plan) { return static_cast<NonlinHost*>(plan->nonlin); }
+
+struct PowArgs {
+  const double* a;
+  const double* b;   // may be null
+  int k;
+  int beta;          // term form: 0 overwrite, 1 accumulate
+};
+
+// base^k by repeated multiplication (the reference's callbacks multiply out; no pow)
+__device__ __forceinline__ double pow_int(double base, int k) {
+  const int m = k < 0 ? -k : k;
+  double p = 1.0;
+  for (int i = 0; i < m; ++i) p *= base;
+  return k < 0 ? 1.0 / p : p;
+}
+__device__ __forceinline__ double power_term(double a, double b, double u, int k) { return a * pow_int(b + u, k); }
+// d/du of the above: k a (b + u)^(k-1); k = 0: exactly 0 (not 0 * (b + u)^-1)
+__device__ __forceinline__ double power_coeff(double a, double b, double u, int k) {
+  return k == 0 ? 0.0 : ((double)k * a) * pow_int(b + u, k - 1);
+}
+
+// dst += the LDS image (store_element_image of d4est_hip_wave.h with the reference's axpy 1.0)
+template <int N, int PL, int PN>
+__device__ __forceinline__ void add_element_image(double* __restrict__ dst, const double* R, int te) {
+  constexpr int N3 = N * N * N, NL = (N3 + PL - 1) / PL;
+#pragma unroll
+  for (int q = 0; q < NL; ++q) {
+    const int idx = te + PL * q;
+    const int i = idx % N, j = (idx / N) % N, k = idx / (N * N);
+    if (N3 % PL == 0 || idx < N3) dst[idx] = dst[idx] + R[i + PN * (j + N * k)];
+  }
+}
+
+// Bop / BopT: the even-odd tables of B^T / B (Bucket::d_EBb / d_EBf), as mass_like_body takes them with EO = true
+template <int N, int NQ, bool COEFF>
+__device__ __forceinline__ void nonlin_body(double* smem, int wg, const double* __restrict__ u, double* __restrict__ out,
+                                            const double* __restrict__ Jq, const int* __restrict__ ns_list,
+                                            const int* __restrict__ qs_list, int n_bucket, const double* __restrict__ Bop,
+                                            const double* __restrict__ BopT, const double* __restrict__ wq, PowArgs P,
+                                            double* __restrict__ c_out, double* __restrict__ wjc_out) {
+  using C = WaveCfg<N, NQ>;
+  constexpr int PL = C::PL, PN = C::PN, PQ = C::PQ;
+
+  const int tid = threadIdx.x;
+  const int slot = tid / PL;
+  const int te = tid - slot * PL;
+  const int a = te % NQ, b = te / NQ;
+  const int ei = wg * C::EPB + slot;
+  const bool active = (slot < C::EPB) && (ei < n_bucket);
+  double* R0 = smem + (active ? slot : 0) * C::LDS_PER_ELEM;
+  double* R1 = R0 + C::FS;
+
+  int ns = 0, qs = 0;
+  if (active) {
+    ns = ns_list[ei];
+    qs = qs_list[ei];
+  }
+
+  // ---- forward: g = (V u)(a, b, :) ----
+  double g[NQ];
+  if (active) load_element_image<N, PL, PN>(R0, u + ns, te);
+  __syncthreads();
+  if (active && a < N && b < N) {  // r
+    double x[N], y[NQ];
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[i] = lds_ld(&R0[i + PN * (a + N * b)]);
+    fwd<N, NQ, true, false>(BopT, x, y);
+#pragma unroll
+    for (int iq = 0; iq < NQ; ++iq) R1[a + PN * (iq + NQ * b)] = y[iq];
+  }
+  __syncthreads();
+  if (active && b < N) {  // s
+    double x[N], y[NQ];
+#pragma unroll
+    for (int j = 0; j < N; ++j) x[j] = lds_ld(&R1[j + PN * (a + NQ * b)]);
+    fwd<N, NQ, true, false>(BopT, x, y);
+#pragma unroll
+    for (int jq = 0; jq < NQ; ++jq) R0[b + PN * (a + NQ * jq)] = y[jq];
+  }
+  __syncthreads();
+  if (active) {  // t
+    double x[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) x[k] = lds_ld(&R0[k + PN * (a + NQ * b)]);
+    fwd<N, NQ, true, false>(BopT, x, g);
+  }
+
+  // ---- pointwise, at the thread's NQ quadrature nodes ----
+  if constexpr (COEFF) {
+    if (active) {
+      const double wab = wq[b] * wq[a];
+#pragma unroll
+      for (int kq = 0; kq < NQ; ++kq) {
+        const int q = qs + a + NQ * (b + NQ * kq);
+        const double c = power_coeff(P.a[q], P.b ? P.b[q] : 0.0, g[kq], P.k);
+        c_out[q] = c;
+        wjc_out[q] = (wq[kq] * wab) * (Jq[q] * c);   // the rounding of lhs_wjc_kernel (d4est_hip_solver.hip)
+      }
+    }
+    return;
+  } else {
+    double c[N];
+    if (active) {
+      const double wab = wq[a] * wq[b];
+#pragma unroll
+      for (int kq = 0; kq < NQ; ++kq) {
+        const int q = qs + a + NQ * (b + NQ * kq);
+        const double sc = (wq[kq] * wab) * Jq[q];
+        g[kq] = power_term(P.a[q], P.b ? P.b[q] : 0.0, g[kq], P.k) * sc;
+      }
+      bwd<NQ, N, true, false, false>(Bop, g, c);
+    }
+    // ---- backward: V^T, as mass_like_body ----
+    __syncthreads();
+    if (active) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) R0[b + PQ * (a + NQ * k)] = c[k];
+    }
+    __syncthreads();
+    if (active && b < N) {
+      double x[NQ], y[N];
+#pragma unroll
+      for (int jq = 0; jq < NQ; ++jq) x[jq] = lds_ld(&R0[jq + PQ * (a + NQ * b)]);
+      bwd<NQ, N, true, false, false>(Bop, x, y);
+#pragma unroll
+      for (int j = 0; j < N; ++j) R1[a + PQ * (j + N * b)] = y[j];
+    }
+    __syncthreads();
+    if (active && a < N && b < N) {
+      double x[NQ], o[N];
+#pragma unroll
+      for (int iq = 0; iq < NQ; ++iq) x[iq] = lds_ld(&R1[iq + PQ * (a + N * b)]);
+      bwd<NQ, N, true, false, false>(Bop, x, o);
+#pragma unroll
+      for (int i = 0; i < N; ++i) R0[i + PN * (a + N * b)] = o[i];
+    }
+    __syncthreads();
+    if (active) {
+      if (P.beta) add_element_image<N, PL, PN>(out + ns, R0, te);
+      else store_element_image<N, PL, PN>(out + ns, R0, te);
+    }
+  }
+}
+
+template <int N, int NQ, bool COEFF>
+__global__ __launch_bounds__((WaveCfg<N, NQ>::THREADS)) void nonlin_kernel(
+    const double* __restrict__ u, double* __restrict__ out, const double* __restrict__ Jq, const int* __restrict__ ns_list,
+    const int* __restrict__ qs_list, int n_bucket, const double* __restrict__ Bop, const double* __restrict__ BopT,
+    const double* __restrict__ wq, PowArgs P, double* __restrict__ c_out, double* __restrict__ wjc_out) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  nonlin_body<N, NQ, COEFF>(smem, blockIdx.x, u, out, Jq, ns_list, qs_list, n_bucket, Bop, BopT, wq, P, c_out, wjc_out);
+}
+
+// Mixed-degree plans: all buckets with deg_quad = deg <= 7 in ONE launch (the rule of mass_like_multi_kernel): one 64-lane workgroup
+// per work unit, which looks its bucket up (wave-uniform) and runs that degree's body
+struct NonlinMulti {
+  static constexpr int MAXB = 7;
+  int n = 0;
+  int wg_end[MAXB] = {};       // exclusive prefix of the buckets' workgroup counts
+  int N[MAXB] = {};
+  int n_elem[MAXB] = {};
+  int elem_offset[MAXB] = {};  // into the plan's bucket-ordered ns / qs lists
+  const double* EBf[MAXB] = {};
+  const double* EBb[MAXB] = {};
+  const double* wq[MAXB] = {};
+};
+
+template <bool COEFF>
+__global__ __launch_bounds__(64) void nonlin_multi_kernel(const double* __restrict__ u, double* __restrict__ out,
+                                                          const double* __restrict__ Jq, const int* __restrict__ ns_list_all,
+                                                          const int* __restrict__ qs_list_all, PowArgs P, double* __restrict__ c_out,
+                                                          double* __restrict__ wjc_out, NonlinMulti A) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int blk = blockIdx.x;
+  int bi = 0;
+  while (bi + 1 < A.n && blk >= A.wg_end[bi]) ++bi;
+  const int wg = blk - (bi > 0 ? A.wg_end[bi - 1] : 0);
+  const int off = A.elem_offset[bi], nb = A.n_elem[bi];
+  const double* EBb = A.EBb[bi];
+  const double* EBf = A.EBf[bi];
+  const double* wq = A.wq[bi];
+#define D4EST_CASE(N_)                                                                                                              \
+  case N_:                                                                                                                          \
+    nonlin_body<N_, N_, COEFF>(smem, wg, u, out, Jq, ns_list_all + off, qs_list_all + off, nb, EBb, EBf, wq, P, c_out, wjc_out);    \
+    break;
+  switch (A.N[bi]) {
+    D4EST_CASE(2) D4EST_CASE(3) D4EST_CASE(4) D4EST_CASE(5) D4EST_CASE(6) D4EST_CASE(7) D4EST_CASE(8)
+    default: break;
+  }
+#undef D4EST_CASE
+}
+
+// composed path (a bucket without a compiled pair): the pointwise step between d4est_hip_interpolate and the integral / the w J c pass
+template <bool COEFF>
+__global__ __launch_bounds__(256) void nonlin_pointwise_kernel(long long n, double* __restrict__ uq, PowArgs P) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const double b = P.b ? P.b[i] : 0.0;
+    uq[i] = COEFF ? power_coeff(P.a[i], b, uq[i], P.k) : power_term(P.a[i], b, uq[i], P.k);
+  }
+}
+
+__global__ __launch_bounds__(256) void nonlin_add_kernel(int n, const double* __restrict__ x, double* __restrict__ y) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) y[i] = y[i] + x[i];
+}
+__global__ __launch_bounds__(256) void nonlin_negate_kernel(int n, double* __restrict__ x) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) x[i] = -1. * x[i];
+}
+
+static int grid_for(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096)); }
+
+// the (deg + 1, deg_quad + 1) pairs with a compiled kernel: those of D4EST_HIP_FAST_PAIRS and D4EST_HIP_BIG_PAIRS, the coverage of
+// d4est_hip_apply_galerkin_integral's one-kernel path (d4est_hip_volume.hip)
+#define D4EST_HIP_NONLIN_PAIRS(X)                                                                                       \
+  X(2, 2) X(3, 3) X(4, 4) X(5, 5) X(6, 6) X(7, 7) X(8, 8) X(9, 9) X(10, 10) X(11, 11) X(12, 12) X(13, 13) X(14, 14)     \
+  X(15, 15) X(16, 16) X(2, 3) X(3, 4) X(4, 5) X(8, 9) X(3, 6) X(4, 6) X(8, 10) X(17, 17) X(18, 18) X(19, 19) X(20, 20)
+
+static bool pair_built(int N, int NQ) {
+#define X(N_, NQ_) if (N == N_ && NQ == NQ_) return WaveCfg<N_, NQ_>::LDS_BYTES <= 160 * 1024;
+  D4EST_HIP_NONLIN_PAIRS(X)
+#undef X
+  return false;
+}
+
+static bool plan_fused(const d4est_hip_plan* plan) {
+  for (const Bucket& bk : plan->buckets)
+    if (bk.n_elem > 0 && !pair_built(bk.N, bk.NQ)) return false;
+  return true;
+}
+
+template <typename K>
+static void set_lds_limit(K kernel, size_t bytes) {   // once per kernel instance (no driver call in the hot path)
+  if (bytes <= 64 * 1024) return;
+  static std::mutex mu;
+  static std::unordered_map<const void*, size_t> done;
+  const void* key = reinterpret_cast<const void*>(kernel);
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = done.find(key);
+  if (it != done.end() && it->second >= bytes) return;
+  HIP_CHECK(hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  done[key] = bytes;
+}
+
+// every bucket of a plan for which plan_fused() holds
+template <bool COEFF>
+static void launch_fused(d4est_hip_plan* plan, const double* u, double* out, PowArgs P, double* c_out, double* wjc_out) {
+  unsigned covered = 0u;
+  {
+    NonlinMulti A;
+    size_t lds = 0;
+    int wgs = 0;
+    for (size_t i = 0; i < plan->buckets.size() && i < 32; ++i) {
+      const Bucket& bk = plan->buckets[i];
+      if (bk.n_elem == 0 || bk.N != bk.NQ || bk.N < 2 || bk.N > 8 || A.n == NonlinMulti::MAXB) continue;
+      size_t l = 0;
+      int epb = 1;
+#define X(N_) if (bk.N == N_) { l = WaveCfg<N_, N_>::LDS_BYTES; epb = WaveCfg<N_, N_>::EPB; }
+      X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+#undef X
+      lds = std::max(lds, l);
+      wgs += (bk.n_elem + epb - 1) / epb;
+      const int j = A.n++;
+      A.wg_end[j] = wgs; A.N[j] = bk.N; A.n_elem[j] = bk.n_elem; A.elem_offset[j] = bk.elem_offset;
+      A.EBf[j] = bk.d_EBf; A.EBb[j] = bk.d_EBb; A.wq[j] = bk.d_w;
+      covered |= 1u << i;
+    }
+    if (A.n >= 2)
+      hipLaunchKernelGGL((nonlin_multi_kernel<COEFF>), dim3(wgs), dim3(64), lds, plan->stream, u, out, plan->d_J, plan->d_ns_list,
+                         plan->d_qs_list, P, c_out, wjc_out, A);
+    else
+      covered = 0u;
+  }
+  size_t bucket_index = 0;
+  for (const Bucket& bk : plan->buckets) {
+    const size_t this_bucket = bucket_index++;
+    if (bk.n_elem == 0) continue;
+    if (this_bucket < 32 && ((covered >> this_bucket) & 1u)) continue;
+    bool done = false;
+#define X(N_, NQ_)                                                                                                          \
+  if (!done && bk.N == N_ && bk.NQ == NQ_) {                                                                                \
+    using C = WaveCfg<N_, NQ_>;                                                                                             \
+    if (C::LDS_BYTES <= 160 * 1024) {                                                                                       \
+      const int grid = (bk.n_elem + C::EPB - 1) / C::EPB;                                                                   \
+      set_lds_limit(nonlin_kernel<N_, NQ_, COEFF>, C::LDS_BYTES);                                                           \
+      hipLaunchKernelGGL((nonlin_kernel<N_, NQ_, COEFF>), dim3(grid), dim3(C::THREADS), C::LDS_BYTES, plan->stream, u, out, \
+                         plan->d_J, plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_EBb, \
+                         bk.d_EBf, bk.d_w, P, c_out, wjc_out);                                                              \
+      done = true;                                                                                                          \
+    }                                                                                                                       \
+  }
+    D4EST_HIP_NONLIN_PAIRS(X)
+#undef X
+    if (!done) D4EST_HIP_ABORT("nonlinear term: no kernel for (N, NQ) = (%d, %d)", bk.N, bk.NQ);   // plan_fused() excludes this
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+static NonlinHost* need_term(d4est_hip_plan* plan, const char* who) {
+  NonlinHost* h = host_of(plan);
+  if (!h || !h->d_a) D4EST_HIP_ABORT("%s: no power term is set (d4est_hip_plan_set_nonlinear_power)", who);
+  if (!plan->has_geometry) D4EST_HIP_ABORT("%s: d4est_hip_plan_set_geometry was not called", who);
+  return h;
+}
+
+static size_t nq_alloc(const d4est_hip_plan* plan) { return std::max<size_t>((size_t)plan->local_nodes_quad, 1) * sizeof(double); }
+
+static void ensure_uq(d4est_hip_plan* plan, NonlinHost* h) {
+  if (!h->d_uq) HIP_CHECK(hipMalloc(&h->d_uq, nq_alloc(plan)));
+}
+
+void nonlinear_destroy(d4est_hip_plan* plan) {
+  NonlinHost* h = host_of(plan);
+  if (!h) return;
+  (void)hipFree(h->d_a); (void)hipFree(h->d_b); (void)hipFree(h->d_uq);
+  (void)hipFree(h->d_f); (void)hipFree(h->d_step); (void)hipFree(h->d_Au); (void)hipFree(h->d_norm);
+  if (h->h_norm) (void)hipHostFree(h->h_norm);
+  delete h;
+  plan->nonlin = nullptr;
+}
+
+}  // namespace d4est_hip
+
+using d4est_hip::NonlinHost;
+using d4est_hip::PowArgs;
+
+extern "C" {
+
+void d4est_hip_plan_set_nonlinear_power(d4est_hip_plan_t* plan, const double* a_quad_dev, const double* b_quad_dev, int k) {
+  if (!plan) D4EST_HIP_ABORT("plan_set_nonlinear_power: NULL plan");
+  if (k < -16 || k > 16) D4EST_HIP_ABORT("plan_set_nonlinear_power: k = %d is outside [-16, 16]", k);
+  NonlinHost* h = d4est_hip::host_of(plan);
+  if (!h) { h = new NonlinHost; plan->nonlin = h; }
+  const size_t bytes = (size_t)plan->local_nodes_quad * sizeof(double);
+  if (!a_quad_dev) {   // the term is off
+    (void)hipFree(h->d_a); h->d_a = nullptr;
+    (void)hipFree(h->d_b); h->d_b = nullptr;
+    h->k = 0;
+    return;
+  }
+  // the values are CAPTURED here, as d4est_hip_plan_set_lhs_coefficient captures its coefficient
+  if (!h->d_a) HIP_CHECK(hipMalloc(&h->d_a, d4est_hip::nq_alloc(plan)));
+  HIP_CHECK(hipMemcpyAsync(h->d_a, a_quad_dev, bytes, hipMemcpyDeviceToDevice, plan->stream));
+  if (b_quad_dev) {
+    if (!h->d_b) HIP_CHECK(hipMalloc(&h->d_b, d4est_hip::nq_alloc(plan)));
+    HIP_CHECK(hipMemcpyAsync(h->d_b, b_quad_dev, bytes, hipMemcpyDeviceToDevice, plan->stream));
+  } else {
+    (void)hipFree(h->d_b); h->d_b = nullptr;
+  }
+  h->k = k;
+}
+
+void d4est_hip_apply_nonlinear_term(d4est_hip_plan_t* plan, const double* u_dev, int beta, double* out_dev) {
+  if (!plan) D4EST_HIP_ABORT("apply_nonlinear_term: NULL plan");
+  if (beta != 0 && beta != 1) D4EST_HIP_ABORT("apply_nonlinear_term: beta = %d (0 or 1)", beta);
+  if (!u_dev || !out_dev) D4EST_HIP_ABORT("apply_nonlinear_term: NULL vector");
+  NonlinHost* h = d4est_hip::host_of(plan);
+  const int n = plan->local_nodes;
+  if (!h || !h->d_a) {   // the term is off: out = beta out
+    if (!beta && n > 0) HIP_CHECK(hipMemsetAsync(out_dev, 0, (size_t)n * sizeof(double), plan->stream));
+    return;
+  }
+  if (!plan->has_geometry) D4EST_HIP_ABORT("apply_nonlinear_term: d4est_hip_plan_set_geometry was not called");
+  if (n == 0) return;
+  const PowArgs P = {h->d_a, h->d_b, h->k, beta};
+  if (d4est_hip::plan_fused(plan)) {
+    d4est_hip::launch_fused<false>(plan, u_dev, out_dev, P, nullptr, nullptr);
+    return;
+  }
+  // composed: interpolate, pointwise, integrate (+ axpy 1.0)
+  d4est_hip::ensure_uq(plan, h);
+  d4est_hip::launch_mass_like(plan, 2, u_dev, h->d_uq);
+  const long long nq = plan->local_nodes_quad;
+  hipLaunchKernelGGL((d4est_hip::nonlin_pointwise_kernel<false>), dim3(d4est_hip::grid_for(nq)), dim3(256), 0, plan->stream, nq, h->d_uq, P);
+  if (!beta) {
+    d4est_hip::launch_mass_like(plan, 1, h->d_uq, out_dev);
+  } else {
+    if (!plan->d_work_m) HIP_CHECK(hipMalloc(&plan->d_work_m, (size_t)n * sizeof(double)));
+    d4est_hip::launch_mass_like(plan, 1, h->d_uq, plan->d_work_m);
+    hipLaunchKernelGGL(d4est_hip::nonlin_add_kernel, dim3(d4est_hip::grid_for(n)), dim3(256), 0, plan->stream, n, plan->d_work_m, out_dev);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+void d4est_hip_plan_linearise(d4est_hip_plan_t* plan, const double* u0_dev) {
+  if (!plan) D4EST_HIP_ABORT("plan_linearise: NULL plan");
+  if (!u0_dev) D4EST_HIP_ABORT("plan_linearise: NULL vector");
+  NonlinHost* h = d4est_hip::need_term(plan, "plan_linearise");
+  // the state d4est_hip_plan_set_lhs_coefficient(plan, c) leaves: a captured graph is dropped, the operator generation bumped, the
+  // coefficient form selected (it replaces element blocks / a Galerkin chain), the plan-owned copy holds c
+  if (plan->cheby_graph) { (void)hipGraphExecDestroy(plan->cheby_graph); plan->cheby_graph = nullptr; }
+  ++plan->op_generation;
+  plan->lhs_wjc_valid = false;
+  plan->d_lhs_blocks = nullptr;
+  d4est_hip::lhs_chain_destroy(plan);
+  if (!plan->d_lhs_c) HIP_CHECK(hipMalloc(&plan->d_lhs_c, d4est_hip::nq_alloc(plan)));
+  if (!plan->d_lhs_wjc) HIP_CHECK(hipMalloc(&plan->d_lhs_wjc, d4est_hip::nq_alloc(plan)));
+  plan->d_lhs_coeff = plan->d_lhs_c;   // non-null = the term is on (the caller's array is never read after the capture)
+  if (plan->local_nodes == 0) return;
+  const PowArgs P = {h->d_a, h->d_b, h->k, 0};
+  if (d4est_hip::plan_fused(plan)) {
+    d4est_hip::launch_fused<true>(plan, u0_dev, nullptr, P, plan->d_lhs_c, plan->d_lhs_wjc);
+    plan->lhs_wjc_valid = true;   // ... and w J c is already formed (set_lhs_coefficient leaves it to the first apply)
+    return;
+  }
+  // composed: V u0 into the coefficient array, c in place; w J c by the first apply (ensure_lhs_wjc)
+  d4est_hip::launch_mass_like(plan, 2, u0_dev, plan->d_lhs_c);
+  const long long nq = plan->local_nodes_quad;
+  hipLaunchKernelGGL((d4est_hip::nonlin_pointwise_kernel<true>), dim3(d4est_hip::grid_for(nq)), dim3(256), 0, plan->stream, nq, plan->d_lhs_c, P);
+  HIP_CHECK(hipGetLastError());
+}
+
+int d4est_hip_plan_nonlinear_fused(const d4est_hip_plan_t* plan) {
+  if (!plan) D4EST_HIP_ABORT("plan_nonlinear_fused: NULL plan");
+  return d4est_hip::plan_fused(plan) ? 1 : 0;
+}
+
+void d4est_hip_build_residual(d4est_hip_plan_t* plan, const double* u_dev, const double* ghost_trace_dev, const double* rhs_dev,
+                              double* out_dev) {
+  if (!plan) D4EST_HIP_ABORT("build_residual: NULL plan");
+  d4est_hip_apply_aij(plan, u_dev, ghost_trace_dev, out_dev);
+  d4est_hip_apply_nonlinear_term(plan, u_dev, 1, out_dev);
+  if (rhs_dev) d4est_hip::launch_residual_inplace_sub(plan, plan->local_nodes, rhs_dev, out_dev);
+}
+
+int d4est_hip_newton_solve(d4est_hip_plan_t* plan, double* u_dev, const double* rhs_dev, const double* g_lobatto_dev, double atol,
+                           double rtol, int imin, int imax, int krylov_imax, double krylov_atol, double krylov_rtol, d4est_hip_pc_fn pc,
+                           void* pc_ctx, d4est_hip_linearise_fn on_linearise, void* cb_ctx, double* fnrm_history_host, int* its_host) {
+  if (!plan) D4EST_HIP_ABORT("newton_solve: NULL plan");
+  if (!u_dev) D4EST_HIP_ABORT("newton_solve: NULL vector");
+  if (plan->n_ghost > 0 || plan->ghost_trace_doubles > 0) D4EST_HIP_ABORT("newton_solve: the plan has ghost sides (single-rank plans only)");
+  if (!plan->has_faces) D4EST_HIP_ABORT("newton_solve: the plan has no faces (plan_set_faces)");
+  if (imin < 0 || imax < 0 || krylov_imax < 0) D4EST_HIP_ABORT("newton_solve: imin = %d, imax = %d, krylov_imax = %d", imin, imax, krylov_imax);
+  NonlinHost* h = d4est_hip::need_term(plan, "newton_solve");
+  const int n = plan->local_nodes;
+  const size_t bytes = std::max<size_t>((size_t)n, 1) * sizeof(double);
+  if (!h->d_f) {
+    HIP_CHECK(hipMalloc(&h->d_f, bytes));
+    HIP_CHECK(hipMalloc(&h->d_step, bytes));
+    HIP_CHECK(hipMalloc(&h->d_Au, bytes));
+    HIP_CHECK(hipMalloc(&h->d_norm, sizeof(double)));
+    HIP_CHECK(hipHostMalloc((void**)&h->h_norm, sizeof(double), hipHostMallocDefault));
+  }
+  const int g = d4est_hip::grid_for(n);
+  // the residual carries the inhomogeneous boundary values, the Jacobian the zeroed ones (d4est_solver_newton.c:120-123)
+  auto residual_norm = [&]() {
+    d4est_hip_plan_set_dirichlet_values(plan, g_lobatto_dev, 1);
+    d4est_hip_build_residual(plan, u_dev, nullptr, rhs_dev, h->d_f);
+    d4est_hip_plan_set_dirichlet_values(plan, nullptr, 1);
+    d4est_hip::launch_dot(plan, n, h->d_f, h->d_f, h->d_norm);
+    if (plan->allreduce_fn) plan->allreduce_fn(plan->comm_ctx, h->d_norm, 1);
+    HIP_CHECK(hipMemcpyAsync(h->h_norm, h->d_norm, sizeof(double), hipMemcpyDeviceToHost, plan->stream));
+    HIP_CHECK(hipStreamSynchronize(plan->stream));   // the one host read per Newton iteration
+    return std::sqrt(*h->h_norm);
+  };
+  double fnrm = residual_norm();                                             // :196-223
+  if (fnrm_history_host) fnrm_history_host[0] = fnrm;
+  const double stop_tol = atol + rtol * fnrm;                                // :226
+  int itc = 0;
+  while ((fnrm > stop_tol || itc < imin) && itc < imax) {                    // :234
+    if (n > 0) hipLaunchKernelGGL(d4est_hip::nonlin_negate_kernel, dim3(g), dim3(256), 0, plan->stream, n, h->d_f);   // :238
+    HIP_CHECK(hipMemsetAsync(h->d_step, 0, bytes, plan->stream));            // :246
+    d4est_hip_plan_linearise(plan, u_dev);
+    if (on_linearise) on_linearise(cb_ctx, u_dev);
+    (void)d4est_hip::fcg_solve(plan, h->d_step, h->d_f, h->d_Au, krylov_imax, krylov_atol, krylov_rtol, pc, pc_ctx, nullptr);   // :248-263
+    if (n > 0) hipLaunchKernelGGL(d4est_hip::nonlin_add_kernel, dim3(g), dim3(256), 0, plan->stream, n, h->d_step, u_dev);   // :266, the full step
+    HIP_CHECK(hipGetLastError());
+    fnrm = residual_norm();                                                  // :269-305
+    ++itc;
+    if (fnrm_history_host) fnrm_history_host[itc] = fnrm;
+  }
+  if (its_host) *its_host = itc;
+  return fnrm > stop_tol ? 1 : 0;                                            // :346-348
+}
+
+}  // extern "C"

@@ -606,6 +606,61 @@ typedef void (*d4est_hip_pc_fn)(void* ctx, const double* r_dev, double* z_dev);
  * host synchronisation per iteration (the preconditioner dominates).  Au_dev ends as A u of the start, as in the reference. */
 int d4est_hip_fcg_solve(d4est_hip_plan_t* plan, double* u_dev, const double* rhs_dev, double* Au_dev, int imax, double atol, double rtol,
                         d4est_hip_pc_fn pc, void* pc_ctx, double* history_host);
+/* ---- nonlinear problems -Laplace(u) + f(x, u) = 0 on one plan (csrc/d4est_hip_nonlinear.hip) -----------------------------------------
+ * The reference takes f as a host callback (d4est_xyzu_fcn_t), which a device cannot call.  The callbacks of its shipped nonlinear
+ * problems have one shape, f(x, u) = a(x) (b(x) + u)^k with a small integer k, and the Jacobian callback is k a (b + u)^(k-1):
+ *   neg_2pi_rho_up1_neg5 / neg_10pi_rho_up1_neg4 (src/Problems/ConstantDensityStar/constant_density_star_fcns.h:347-357 / :334-344):
+ *     a = -2 pi rho(x), b = 0, k = 5
+ *   two_punctures_neg_1o8_K2_psi_neg7 / two_punctures_plus_7o8_K2_psi_neg8 (src/Problems/TwoPunctures/two_punctures_fcns.h:252-284 /
+ *     :288-320): a = -K^2 / 8 (0 inside puncture_eps), b = 1 + sum_n m_n / (2 r_n), k = -7
+ * a and b depend on the mesh only: the caller evaluates them once per mesh at the quadrature nodes (d4est_hip_plan_compute_xyz_analytic
+ * gives xyz_quad on the device).
+ *
+ * d4est_hip_plan_set_nonlinear_power registers the term.  a_quad_dev, b_quad_dev: local_nodes_quad doubles each, element e at
+ * quad_stride[e] (device arrays; their values are CAPTURED by this call into plan-owned copies, as d4est_hip_plan_set_lhs_coefficient
+ * captures its coefficient -- call it again when a or b changes; the caller's arrays are not read afterwards).  b_quad_dev == NULL: b = 0.
+ * a_quad_dev == NULL switches the term off (it then contributes zero; plan_linearise and newton_solve abort).  |k| <= 16, else abort.
+ * The power is |k| multiplications (k < 0: one division of 1 by the product), never pow: the ConstantDensityStar callbacks multiply out,
+ * and TwoPunctures' pow(psi^2, 3.5) differs from the product in the last bits only. */
+void d4est_hip_plan_set_nonlinear_power(d4est_hip_plan_t* plan, const double* a_quad_dev, const double* b_quad_dev, int k);
+/* out = beta out + V^T W J f(x, V u) per element, beta = 0 or 1: the loop of d4est_quadrature_apply_fofufofvlj followed by axpy 1.0
+ * (constant_density_star_fcns.h:360-437 with src/Quadrature/d4est_quadrature.c:776-936).  ONE kernel -- interpolate, pointwise,
+ * integrate, no quadrature-sized temporary -- for every (deg, deg_quad) pair d4est_hip_apply_galerkin_integral serves with a one-kernel
+ * path (deg_quad = deg <= 19, and deg_quad - deg in {1, 2, 3} at the compiled pairs; mixed-degree plans: the deg_quad = deg <= 7
+ * buckets in one launch).  A plan with an element outside these pairs runs d4est_hip_interpolate, a pointwise kernel and
+ * d4est_hip_apply_galerkin_integral instead; d4est_hip_plan_nonlinear_fused returns 1 when the plan takes the one-kernel form. */
+void d4est_hip_apply_nonlinear_term(d4est_hip_plan_t* plan, const double* u_dev, int beta, double* out_dev);
+int d4est_hip_plan_nonlinear_fused(const d4est_hip_plan_t* plan);
+/* Sets the plan's zeroth-order coefficient to c = k a (b + V u0)^(k-1) (k = 0: c = 0), the Jacobian callback at u0
+ * (constant_density_star_fcns.h:528-603): one kernel writes the plan-owned coefficient and the pre-combined w J c of the operator
+ * kernels.  Afterwards the plan is in the state d4est_hip_plan_set_lhs_coefficient(plan, c) leaves, with w J c already formed: the
+ * coefficient form replaces element blocks / a Galerkin chain, and the term is part of d4est_hip_apply_lhs, _cheby_iterate, _cg_eigs,
+ * the Krylov solves.  d4est_hip_plan_set_lhs_coefficient(plan, NULL) switches it off again.  Aborts if no power term is set. */
+void d4est_hip_plan_linearise(d4est_hip_plan_t* plan, const double* u0_dev);
+/* out = A u + N(u) - rhs: the reference's build_residual (constant_density_star_fcns.h:439-482) -- d4est_hip_apply_aij with the boundary
+ * data currently set on the plan, the nonlinear term with beta = 1, one axpy.  rhs_dev == NULL: no right-hand side; ghost_trace_dev as
+ * in d4est_hip_apply_aij. */
+void d4est_hip_build_residual(d4est_hip_plan_t* plan, const double* u_dev, const double* ghost_trace_dev, const double* rhs_dev,
+                              double* out_dev);
+/* called by d4est_hip_newton_solve after every d4est_hip_plan_linearise(plan, u0): where the caller refreshes its preconditioner
+ * (d4est_hip_plan_linearise on the coarse plans with the projected u0, block rebuilds, eigenvalue reuse flags) */
+typedef void (*d4est_hip_linearise_fn)(void* ctx, const double* u0_dev);
+/* d4est_solver_newton_solve (src/Solver/d4est_solver_newton.c:135-365) with d4est_hip_fcg_solve as its Krylov function:
+ * F = A u + N(u) - rhs with the Dirichlet data g_lobatto_dev (layout of d4est_hip_plan_set_dirichlet_values, device array, NULL =
+ * homogeneous); stop_tol = atol + rtol |F(u)| at the initial guess; while (|F| > stop_tol || itc < imin) && itc < imax: linearise at u,
+ * on_linearise(cb_ctx, u) if non-NULL, solve J step = -F from step = 0 by FCG (krylov_imax, krylov_atol, krylov_rtol, pc / pc_ctx as in
+ * d4est_hip_fcg_solve), u += step (always the full step, no line search), new F.  Returns 1 if |F| > stop_tol at exit, else 0.
+ * The residual carries the inhomogeneous boundary values and the Jacobian the zeroed ones (:120-123): the routine switches the plan's
+ * Dirichlet data between g_lobatto_dev and homogeneous and leaves the plan homogeneous, linearised at the last-but-one iterate.
+ * |F| comes from the plan's dot product and allreduce hook and is read to the host once per Newton iteration; fnrm_history_host
+ * (optional, imax + 1 doubles) receives its + 1 norms, its_host (optional) the iteration count.
+ * Single-rank plans only: aborts if the plan has ghost sides.
+ * Known limit: a coarse plan that reads this plan's w J c through d4est_hip_plan_set_lhs_galerkin_chain and replays a Chebyshev hipGraph
+ * captured under D4EST_HIP_TUNE_GRAPH would replay the previous linearisation; newton_solve is unsupported with that tuning key on chain
+ * plans. */
+int d4est_hip_newton_solve(d4est_hip_plan_t* plan, double* u_dev, const double* rhs_dev, const double* g_lobatto_dev, double atol,
+                           double rtol, int imin, int imax, int krylov_imax, double krylov_atol, double krylov_rtol, d4est_hip_pc_fn pc,
+                           void* pc_ctx, d4est_hip_linearise_fn on_linearise, void* cb_ctx, double* fnrm_history_host, int* its_host);
 /* pack / unpack of face-trace blocks for the ghost exchange: dst[dst_off[b]+i] = src[src_off[b]+i], i < len[b];
  * the three index arrays are DEVICE arrays of n_blocks entries; runs on the plan's stream.  Replaces the per-mirror
  * memcpy loop of d4est_ghost_data_exchange (src/Mesh/d4est_ghost_data.c:196-236). */
