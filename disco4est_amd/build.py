@@ -35,6 +35,7 @@ SOURCES = [
     "d4est_hip_sizes.hip",
     "d4est_hip_hessian.hip",
     "d4est_hip_nonlinear.hip",
+    "d4est_hip_probe.hip",
 ]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]

@@ -215,6 +215,15 @@ SIGNATURES = {
     "d4est_hip_amr_interpolate_field": (None, [_vp, _vp, _vp]),
     "d4est_hip_amr_describe": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int]),
     "d4est_hip_amr_advance": (None, [_vp]),
+    "d4est_hip_probe_create": (_vp, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_int]),
+    "d4est_hip_probe_destroy": (None, [_vp]),
+    "d4est_hip_probe_n_points": (ctypes.c_int, [_vp]),
+    "d4est_hip_probe_info": (None, [_vp, _vp, _vp, _vp]),
+    "d4est_hip_probe_element_info": (None, [_vp, _vp, _vp]),
+    "d4est_hip_probe_eval": (None, [_vp, ctypes.c_int, _vp, ctypes.c_longlong, _vp]),
+    "d4est_hip_probe_set_map": (None, [_vp, ctypes.c_int, _vp]),
+    "d4est_hip_probe_eval_gradient": (None, [_vp, _vp, _vp, ctypes.c_int]),
+    "d4est_hip_probe_xyz": (None, [_vp, _vp]),
 }
 
 # [mesh_parameters] face_h_type / volume_h_type by the reference's names (d4est_mesh_face_h_t / d4est_mesh_volume_h_t) and the size
@@ -1100,6 +1109,76 @@ class Amr:
     def destroy(self):
         if self.handle:
             self.lib.d4est_hip_amr_destroy(self.handle)
+            self.handle = None
+
+
+GEOM_BRICK = 0
+
+
+class Probe:
+    """Point probes on a plan (d4est_hip_probe_*): the points (tree[n], abc[n, 3] tree coordinates) are located once among the plan's
+    elements -- cells = (elem_tree, elem_q[ne, 3], elem_dq) and root_len, what mesh.BrickMesh.cells() / forest.ForestMesh.cells() return --
+    and then evaluated on the device: eval (values), eval_gradient (reference-space or physical gradient), xyz.  Fields and outputs are
+    float64 CUDA tensors.  The probe must be destroyed before its plan."""
+
+    def __init__(self, plan, tree, abc, cells, root_len):
+        self.lib = load_library()
+        self.plan = plan   # keeps the plan alive as long as the probe
+        t = _iarr(np.asarray(tree).reshape(-1))
+        a = np.ascontiguousarray(np.asarray(abc, dtype=np.float64).reshape(-1))
+        self.n_points = len(t[0])
+        assert a.size == 3 * self.n_points
+        et, eq, ed = _iarr(cells[0]), _iarr(np.asarray(cells[1]).reshape(-1)), _iarr(cells[2])
+        assert len(et[0]) == plan.n_elements and len(ed[0]) == plan.n_elements and len(eq[0]) == 3 * plan.n_elements
+        self.handle = self.lib.d4est_hip_probe_create(plan.handle, self.n_points, t[1], a.ctypes.data_as(_vp), et[1], eq[1], ed[1],
+                                                      float(root_len), 0)
+
+    def info(self):
+        """(err[n], elem[n], rst[n, 3]) as numpy arrays: err 0 found / 1 not on this plan, the local element id (-1), the element's rst (NaN)"""
+        err = np.empty(self.n_points, dtype=np.int32)
+        elem = np.empty(self.n_points, dtype=np.int32)
+        rst = np.empty((self.n_points, 3), dtype=np.float64)
+        self.lib.d4est_hip_probe_info(self.handle, err.ctypes.data_as(_vp), elem.ctypes.data_as(_vp), rst.ctypes.data_as(_vp))
+        return err, elem, rst
+
+    def element_info(self):
+        """(nodal_stride[n], deg[n]) of the located elements (0 where err = 1)"""
+        ns = np.empty(self.n_points, dtype=np.int32)
+        deg = np.empty(self.n_points, dtype=np.int32)
+        self.lib.d4est_hip_probe_element_info(self.handle, ns.ctypes.data_as(_vp), deg.ctypes.data_as(_vp))
+        return ns, deg
+
+    def eval(self, u, out, n_fields=1, field_stride=0):
+        """out[f * n_points + p] = field f (at u[f * field_stride:]) at point p; NaN where err = 1.  Stream-ordered, no synchronisation."""
+        assert out.numel() >= n_fields * self.n_points
+        assert u.numel() >= (n_fields - 1) * field_stride + self.plan.local_nodes
+        if self.n_points == 0 or n_fields == 0:
+            return
+        self.lib.d4est_hip_probe_eval(self.handle, int(n_fields), _ptr(u), int(field_stride), _ptr(out))
+
+    def set_map(self, geom_type, params):
+        """the map of the plan's geometry: capi.GEOM_BRICK with the six extents, or a sphere type with its params (forest maps: .params)"""
+        pr = np.zeros(6)
+        pv = np.asarray(params, dtype=np.float64).reshape(-1)
+        pr[:pv.size] = pv
+        self.lib.d4est_hip_probe_set_map(self.handle, int(geom_type), pr.ctypes.data_as(_vp))
+
+    def eval_gradient(self, u, grad, physical=False):
+        """grad[d * n_points + p]: the reference-space gradient, or with physical=True (after set_map) d/dx, d/dy, d/dz"""
+        assert grad.numel() >= 3 * self.n_points and u.numel() >= self.plan.local_nodes
+        if self.n_points == 0:
+            return
+        self.lib.d4est_hip_probe_eval_gradient(self.handle, _ptr(u), _ptr(grad), 1 if physical else 0)
+
+    def xyz(self):
+        """physical coordinates [n, 3] of the points through the map of set_map (NaN where err = 1)"""
+        out = np.empty((self.n_points, 3), dtype=np.float64)
+        self.lib.d4est_hip_probe_xyz(self.handle, out.ctypes.data_as(_vp))
+        return out
+
+    def destroy(self):
+        if self.handle:
+            self.lib.d4est_hip_probe_destroy(self.handle)
             self.handle = None
 
 

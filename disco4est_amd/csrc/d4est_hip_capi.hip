@@ -404,6 +404,10 @@ static d4est_hip::TreeMapParams analytic_params(int geom_type, const double* par
   return P;
 }
 
+void d4est_hipi_tree_map_params(int geom_type, const double* params, const char* who, d4est_hip::TreeMapParams* out) {
+  *out = analytic_params(geom_type, params, who);
+}
+
 int d4est_hip_tree_map(int geom_type, const double* params, int tree, const double* xi, double* x_out, double* dxdxi_out) {
   d4est_hip::TreeMapParams P;
   const char* why = "";

@@ -49,6 +49,9 @@ std::map<const void*, CoordReg> g_coord;
 std::map<const void*, const double*> g_diam;   // d4est_hip_compat_bind_element_diameters
 struct SchwarzReg { d4est_hip_schwarz_t* sz; int iter; double atol, rtol; };
 std::map<const void*, SchwarzReg> g_schwarz;
+// d4est_hip_compat_bind_forest: where the bound plan's elements sit (copies) and the map for data.xyz (geom_type < 0: none)
+struct ForestReg { std::vector<int> tree, q, dq; double root_len; int geom_type; double params[6]; };
+std::map<const void*, ForestReg> g_forest;
 double* g_tr_h = nullptr;   // pinned staging of the transfer shims
 double* g_tr_d = nullptr;
 size_t g_tr_cap = 0;
@@ -642,7 +645,27 @@ void cg_eigs(p4est_t* p4est, d4est_elliptic_data_t* vecs, d4est_elliptic_eqns_t*
 
 void d4est_hip_compat_bind_mesh(const void* p4est, d4est_hip_plan_t* plan) {
   if (plan) g_bound[p4est] = plan;
-  else { g_bound.erase(p4est); g_bound_lhs.erase(p4est); g_flux.erase(p4est); g_coord.erase(p4est); g_schwarz.erase(p4est); g_diam.erase(p4est); }
+  else { g_bound.erase(p4est); g_bound_lhs.erase(p4est); g_flux.erase(p4est); g_coord.erase(p4est); g_schwarz.erase(p4est); g_diam.erase(p4est); g_forest.erase(p4est); }
+}
+void d4est_hip_compat_bind_forest(const void* p4est, const int* elem_tree, const int* elem_q, const int* elem_dq, double root_len, int geom_type,
+                                  const double* params) {
+  if (!elem_tree) { g_forest.erase(p4est); return; }
+  const char* who = "d4est_hip_compat_bind_forest";
+  const int ne = d4est_hip_plan_n_elements(bound(p4est, who));
+  if (!elem_q || !elem_dq) COMPAT_ABORT("%s: NULL element array", who);
+  if (geom_type >= 0 && !params) COMPAT_ABORT("%s: geometry type %d without params", who, geom_type);
+  ForestReg r;
+  r.tree.assign(elem_tree, elem_tree + ne);
+  r.q.assign(elem_q, elem_q + 3 * (size_t)ne);
+  r.dq.assign(elem_dq, elem_dq + ne);
+  r.root_len = root_len;
+  r.geom_type = geom_type;
+  for (int i = 0; i < 6; ++i) r.params[i] = 0.0;
+  if (geom_type >= 0) {
+    const int np = geom_type == D4EST_HIP_GEOM_BRICK ? 6 : geom_type == D4EST_HIP_GEOM_CUBED_SPHERE_7TREE ? 3 : 5;
+    std::copy(params, params + np, r.params);
+  }
+  g_forest[p4est] = r;
 }
 void d4est_hip_compat_bind_element_diameters(const void* p4est, const double* diam_volume) {
   if (diam_volume) g_diam[p4est] = diam_volume;
@@ -786,6 +809,48 @@ double d4est_mesh_compute_l2_norm_sqr(p4est_t* p4est, d4est_operators_t*, d4est_
   if (l2_array) d4est_hip_memcpy_d2h(l2_array, d_sum + 1, sizeof(double) * (size_t)ne);
   d4est_hip_free(d_v);
   return sum;
+}
+
+// ---- src/Mesh/d4est_mesh.c:3294-3362: one point through a d4est_hip_probe on the bound plan (locate, rst, value; xyz with a map)
+d4est_mesh_interpolate_data_t d4est_mesh_interpolate_at_tree_coord(p4est_t* p4est, d4est_operators_t*, d4est_geometry_t*, double abc[3],
+                                                                   int tree_id, double* f, int) {
+  const char* who = "d4est_mesh_interpolate_at_tree_coord";
+  d4est_hip_plan_t* plan = bound(p4est, who);
+  auto fr = g_forest.find(p4est);
+  if (fr == g_forest.end()) COMPAT_ABORT("%s: no forest registered for p4est %p (d4est_hip_compat_bind_forest)", who, p4est);
+  if (!abc || !f) COMPAT_ABORT("%s: NULL abc or field", who);
+  const ForestReg& r = fr->second;
+  const size_t ln = (size_t)d4est_hip_plan_local_nodes(plan);
+  d4est_mesh_interpolate_data_t data;
+  std::memset(&data, 0, sizeof(data));
+  d4est_hip_probe_t* pr = d4est_hip_probe_create(plan, 1, &tree_id, abc, r.tree.data(), r.q.data(), r.dq.data(), r.root_len, 0);
+  int elem = -1;
+  d4est_hip_probe_info(pr, &data.err, &elem, data.rst);
+  if (data.err != 0) {
+    data.rst[0] = data.rst[1] = data.rst[2] = 0.0;
+    data.f_at_xyz = std::nan("");
+    d4est_hip_probe_destroy(pr);
+    return data;
+  }
+  double* d_u = (double*)d4est_hip_malloc(sizeof(double) * (ln + 1));
+  d4est_hip_memcpy_h2d(d_u, f, sizeof(double) * ln);
+  d4est_hip_probe_eval(pr, 1, d_u, 0, d_u + ln);
+  d4est_hip_plan_synchronize(plan);
+  d4est_hip_memcpy_d2h(&data.f_at_xyz, d_u + ln, sizeof(double));
+  d4est_hip_free(d_u);
+  if (r.geom_type >= 0) {
+    d4est_hip_probe_set_map(pr, r.geom_type, r.params);
+    d4est_hip_probe_xyz(pr, data.xyz);
+  }
+  for (int d = 0; d < 3; ++d) {
+    data.abc[d] = abc[d];
+    data.q[d] = r.q[3 * (size_t)elem + d];
+  }
+  data.dq = r.dq[elem];
+  data.id = elem;
+  d4est_hip_probe_element_info(pr, &data.nodal_stride, nullptr);
+  d4est_hip_probe_destroy(pr);
+  return data;
 }
 
 // ---- src/dGMath/d4est_hessian.c:270-368 --------------------------------------------------------------------------------------

@@ -409,5 +409,9 @@ void krylov_destroy(d4est_hip_plan* plan);
 // d4est_hip_nonlinear.hip
 void nonlinear_destroy(d4est_hip_plan* plan);
 
+// d4est_hip_capi.hip (defined among its extern "C" entry points; not in the header: internal): {geom_type, params} of the analytic entry
+// points -> TreeMapParams; aborts with `who` on a bad type, radius or flag
+extern "C" void d4est_hipi_tree_map_params(int geom_type, const double* params, const char* who, TreeMapParams* out);
+
 
 }  // namespace d4est_hip

@@ -150,6 +150,15 @@ class BrickMesh:
                     rst[3 * i + j, s:s + q3] = inv[:, i, j]
         return J, rst.reshape(-1)
 
+    def cells(self):
+        """(tree, q[n,3], dq) of the local elements -- d4est_element_data_t::tree, ::q, ::dq in units of this mesh's cells, root length =
+        self.root_len -- for capi.Probe and the other entry points that take where the elements sit in the forest"""
+        return (np.zeros(self.n_elements, dtype=np.int32), self.ijk.astype(np.int32), np.ones(self.n_elements, dtype=np.int32))
+
+    @property
+    def root_len(self):
+        return 1 << self.level
+
     def field(self, mapping=None, seed=102321, noise=1.0):
         """u = x^2 + y^2 + z^2 + noise * U[0,1) at the Lobatto nodes
         (the reference speed-up test's input, d4est_test_laplacian_speedup.c:429-432)."""
@@ -361,6 +370,14 @@ class HangingBrickMesh(BrickMesh):
         self.global_nodal_stride = np.concatenate([[0], np.cumsum(g3)[:-1]])
         self.global_nodes = int(g3.sum())
         self.global_nodal_offset = int(self.global_nodal_stride[first]) if count > 0 else 0
+
+    def cells(self):
+        """(tree, q[n,3], dq) of the local elements in units of the fine grid, root length = self.root_len (see BrickMesh.cells)"""
+        return (np.zeros(self.n_elements, dtype=np.int32), self.org.astype(np.int32), self.size.astype(np.int32))
+
+    @property
+    def root_len(self):
+        return 1 << (self.level + 1)
 
     def _ref_coords(self, e, nodes_1d):
         n = nodes_1d.size

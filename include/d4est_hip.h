@@ -990,6 +990,57 @@ int d4est_hip_amr_describe(const d4est_hip_amr_t* amr, char* buf, int len);
  * degrees become current and the object is ready for the next level (the balance state is dropped; synchronises the stream). */
 void d4est_hip_amr_advance(d4est_hip_amr_t* amr);
 
+/* ---- point probes: field value and gradient at tree coordinates (csrc/d4est_hip_probe.hip) -----------------------------------------
+ * d4est_mesh_interpolate_at_tree_coord (src/Mesh/d4est_mesh.c:3294-3362) with d4est_operators_interpolate
+ * (src/dGMath/d4est_operators.c:2289-2340) for a batch of points, the field resident on the device: what the TwoPunctures drivers read
+ * at the punctures after every AMR level (src/Problems/TwoPunctures/two_punctures_cactus_13tree_with_opt_puncture_finder.c:951-978),
+ * and, in bulk, line-outs and resampling.  A probe object holds the located points of ONE plan; it is the caller's, keeps a pointer to
+ * the plan and MUST NOT OUTLIVE IT (destroy the probe first).  All kernels run on the plan's stream; after create nothing allocates and
+ * eval / eval_gradient do not synchronise with the host.  No atomics and fixed reduction orders: the same bits on every call.
+ *
+ * create (d4est_mesh.c:3308-3328): tree[n_points] and abc[3 n_points] (point p at abc[3 p + d], tree coordinates in [0, 1]^3), host arrays
+ * or, with on_device != 0, device arrays -- then the three element arrays are device arrays too.  elem_tree / elem_q / elem_dq / root_len:
+ * where every LOCAL element of the plan sits in the forest, the layout of d4est_hip_plan_set_geometry_analytic (on a brick elem_tree is
+ * all zero).  One wavefront per point scans the elements for  q[d] / root_len <= abc[d] <= (q[d] + dq) / root_len,  d = 0, 1, 2, in the
+ * point's tree -- inclusive on both ends, the bounds rounded as at :3322-3326 -- and takes the LOWEST matching local element id: the
+ * first match of the reference's loop in quadrant order for a point on a face, edge or corner between elements.  err = 0 found, 1 not
+ * found (data.err, :3360): the tree is out of range, abc is outside [0, 1]^3, or the quadrant is a ghost or another rank's; multi-rank
+ * callers reduce the err == 0 values themselves.  rst[d] = 2 (abc[d] - amin) / (amax - amin) - 1 in that order of operations (:3339).
+ * The points' deg and nodal_stride are taken from the plan.  n_points = 0 is valid: every call on such a probe is a no-op.  synchronises. */
+typedef struct d4est_hip_probe d4est_hip_probe_t;
+d4est_hip_probe_t* d4est_hip_probe_create(d4est_hip_plan_t* plan, int n_points, const int* tree, const double* abc, const int* elem_tree,
+                                          const int* elem_q, const int* elem_dq, double root_len, int on_device);
+void d4est_hip_probe_destroy(d4est_hip_probe_t* probe);
+int d4est_hip_probe_n_points(const d4est_hip_probe_t* probe);
+/* host outputs, any may be NULL: err_host[n_points]; elem_host[n_points] (data.id as a local element id, -1 where err = 1);
+ * rst_host[3 n_points] (point p at 3 p + d; NaN where err = 1).  synchronises the stream. */
+void d4est_hip_probe_info(const d4est_hip_probe_t* probe, int* err_host, int* elem_host, double* rst_host);
+/* likewise the located elements' nodal_stride (data.nodal_stride) and deg, n_points each (0 where err = 1); either may be NULL */
+void d4est_hip_probe_element_info(const d4est_hip_probe_t* probe, int* nodal_stride_host, int* deg_host);
+/* d4est_operators_interpolate (d4est_operators.c:2289-2340) of n_fields fields, field f at u_dev + f * field_stride (doubles; each a
+ * nodal vector of the plan):  out_dev[f * n_points + p] = sum_{k,j,i} l_k(t) l_j(s) l_i(r) u_f[nodal_stride + (k N + j) N + i],  i
+ * fastest (d4est_kron_vec1_o_vec2_o_vec3_dot_x_sum as called at :2320-2330), l_i the product form of d4est_lgl_lagrange_1d
+ * (src/dGMath/d4est_lgl.c:59-68) on the engine's Lobatto nodes (D4EST_HIP_TABLE_LOBATTO_NODES), factors taken in its order.  Degrees 1 ..
+ * 19, mixed degrees in one launch: one wavefront per point forms the three basis vectors once for all fields, its lanes own (j, k)
+ * columns and loop over i, a fixed-order wave reduction follows.  A point with err = 1 gets a quiet NaN (the reference leaves f_at_xyz
+ * unset). */
+void d4est_hip_probe_eval(d4est_hip_probe_t* probe, int n_fields, const double* u_dev, long long field_stride, double* out_dev);
+/* The analytic map the plan's geometry was set with, for eval_gradient(physical = 1) and probe_xyz: geom_type D4EST_HIP_GEOM_BRICK with
+ * params = extents {X0, X1, Y0, Y1, Z0, Z1} of d4est_hip_plan_set_geometry_brick (x_d = X0_d + (X1_d - X0_d) abc_d, one tree), or one
+ * of the four sphere types with the params of d4est_hip_plan_set_geometry_analytic.  Aborts like that call on a bad type, radius or
+ * flag, and when a found point's tree is not one of the map's. */
+#define D4EST_HIP_GEOM_BRICK 0
+void d4est_hip_probe_set_map(d4est_hip_probe_t* probe, int geom_type, const double* params);
+/* grad_dev[d * n_points + p], d = 0, 1, 2.  physical = 0: the reference-space gradient (du/dr, du/ds, du/dt) from the derivative of the
+ * same product-form basis at the point, d/dr through l'_i(r) l_j(s) l_k(t) and likewise in s and t.  physical = 1: (du/dx, du/dy, du/dz)
+ * = sum_i (du/dr_i) dr_i/dx_d with dr/dx the inverse of the 3 x 3 Jacobian of the map of probe_set_map AT THE POINT, dx/d(abc) scaled by
+ * the element's dq / root_len / 2 -- the plan stores no inverse Jacobian at the nodes that could be interpolated, only the combined metric
+ * (csrc/d4est_hip_norms.hip:21-22).  physical = 1 without a map aborts.  err = 1: quiet NaN. */
+void d4est_hip_probe_eval_gradient(d4est_hip_probe_t* probe, const double* u_dev, double* grad_dev, int physical);
+/* data.xyz (d4est_mesh.c:3332): xyz_host[3 p + d] = the map of probe_set_map at (tree, abc) of point p (NaN where err = 1).  Needs a map;
+ * synchronises the stream. */
+void d4est_hip_probe_xyz(d4est_hip_probe_t* probe, double* xyz_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -311,6 +311,24 @@ typedef int d4est_hessian_compute_method_t;                     /* enum {HESSIAN
 #define HESSIAN_ANALYTICAL 0
 #define HESSIAN_NUMERICAL 1
 void d4est_hessian_compute_hessian_trace_of_field_on_quadrature_points(p4est_t *p4est,d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geom,d4est_quadrature_t *d4est_quad,d4est_mesh_data_t *d4est_factors,d4est_hessian_compute_method_t compute_method,double *field_lobatto,double *del2field);
+/* src/Mesh/d4est_mesh.h:63-80 and :208 (d4est_mesh.c:3294-3362) on the bound plan: the value of the host nodal vector f at tree
+ * coordinates abc of tree tree_id, through a one-point d4est_hip_probe (locate, rst, the product-form Lagrange value; include/d4est_hip.h
+ * "point probes").  The struct is the reference's, member for member (p4est_qcoord_t = int32_t), returned by value.  Where the forest's
+ * elements sit is opaque here: register it with d4est_hip_compat_bind_forest (required; aborts without).  err = 1 when no local element
+ * of the bound plan contains the point; as in the reference only err is then set -- here the other members are zero, f_at_xyz a NaN.
+ * xyz is filled when a map was registered with the forest, else zero.  print is ignored (the reference's printf is commented out). */
+typedef struct {
+  int err;
+  double f_at_xyz;
+  int nodal_stride;
+  double xyz [3];
+  double rst [3];
+  double abc [3];
+  int id;
+  int q [3];
+  int dq;
+} d4est_mesh_interpolate_data_t;
+d4est_mesh_interpolate_data_t d4est_mesh_interpolate_at_tree_coord(p4est_t *p4est,d4est_operators_t *d4est_ops,d4est_geometry_t *d4est_geom,double abc[3],int tree_id,double *f,int print);
 #endif /* D4EST_HIP_COMPAT_NO_TYPES */
 
 /* ---- binding (not in the reference) ------------------------------------------------------------------------------------------ */
@@ -332,6 +350,12 @@ void d4est_hip_compat_bind_coordinates(const void* p4est, double* xyz_lobatto[3]
 /* d4est_factors->diam_volume (host array of the local elements, stays the caller's): the h of the estimator's residual term; takes
  * precedence over the diam_volume the plan computed itself */
 void d4est_hip_compat_bind_element_diameters(const void* p4est, const double* diam_volume);
+/* where the local elements of the bound plan sit in the forest -- d4est_element_data_t::tree, ::q[3], ::dq of every local element in
+ * traversal order, root_len = P4EST_ROOT_LEN (host arrays, COPIED; call after every d4est_hip_compat_bind_mesh) -- and, optionally, the
+ * map for data.xyz: geom_type / params of d4est_hip_probe_set_map, or geom_type < 0 for none.  For d4est_mesh_interpolate_at_tree_coord;
+ * elem_tree = NULL removes the registration */
+void d4est_hip_compat_bind_forest(const void* p4est, const int* elem_tree, const int* elem_q, const int* elem_dq, double root_len,
+                                  int geom_type, const double* params);
 /* the Schwarz smoother of this mesh and its three [d4est_solver_schwarz] CG options, for d4est_solver_schwarz_iterate; NULL unbinds */
 void d4est_hip_compat_bind_schwarz(const void* p4est, d4est_hip_schwarz_t* sz, int subdomain_iter, double subdomain_atol, double subdomain_rtol);
 /* the reference's Schwarz metadata as the flat arrays d4est_hip_schwarz_create takes; outputs caller-allocated:
