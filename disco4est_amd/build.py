@@ -36,6 +36,7 @@ SOURCES = [
     "d4est_hip_hessian.hip",
     "d4est_hip_nonlinear.hip",
     "d4est_hip_probe.hip",
+    "d4est_hip_problem.hip",
 ]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]

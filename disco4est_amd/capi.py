@@ -224,7 +224,61 @@ SIGNATURES = {
     "d4est_hip_probe_set_map": (None, [_vp, ctypes.c_int, _vp]),
     "d4est_hip_probe_eval_gradient": (None, [_vp, _vp, _vp, ctypes.c_int]),
     "d4est_hip_probe_xyz": (None, [_vp, _vp]),
+    "d4est_hip_field_eval": (None, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_longlong, _vp]),
+    "d4est_hip_plan_compute_xyz_brick": (None, [_vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]),
+    "d4est_hip_plan_set_puncture_term_brick": (None, [_vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_double, _vp]),
+    "d4est_hip_plan_set_puncture_term_analytic": (None, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double]),
+    "d4est_hip_plan_set_puncture_term_xyz": (None, [_vp, _vp, ctypes.c_int, _vp]),
+    "d4est_hip_plan_set_cds_term_brick": (None, [_vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_double, _vp]),
+    "d4est_hip_plan_set_cds_term_analytic": (None, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double]),
+    "d4est_hip_plan_set_cds_term_xyz": (None, [_vp, _vp, ctypes.c_int, _vp]),
+    "d4est_hip_plan_nonlinear_coefficients": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "d4est_hip_plan_compute_boundary_xyz_brick": (None, [_vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
+    "d4est_hip_plan_compute_boundary_xyz_analytic": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double, _vp]),
+    "d4est_hip_plan_set_robin_by_id_brick": (None, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_double, _vp]),
+    "d4est_hip_plan_set_robin_by_id_analytic": (None, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double]),
 }
+
+# problem fields and Robin callbacks by id (D4EST_HIP_FIELD_* / D4EST_HIP_ROBIN_*)
+FIELD = {"PUNCTURE_K2": 0, "PUNCTURE_A": 1, "PUNCTURE_B": 2, "CDS_A": 3, "CDS_PSI": 4, "INV_R": 5}
+ROBIN_COEFF = {"INV_R": 0, "BRICK": 1}
+ROBIN_RHS = {"ZERO": 0, "INV_R": 1}
+MAX_PUNCTURES = 10
+
+
+def puncture_params(C, P, S, M, puncture_eps=1e-15):
+    """the flat parameter vector of the puncture fields: {num_punctures, puncture_eps, then per puncture C[3], P[3], S[3], M}"""
+    C, P, S = (np.asarray(a, dtype=np.float64).reshape(-1, 3) for a in (C, P, S))
+    M = np.asarray(M, dtype=np.float64).reshape(-1)
+    n = M.size
+    assert C.shape[0] == n and P.shape[0] == n and S.shape[0] == n and 1 <= n < MAX_PUNCTURES
+    return np.concatenate([[float(n), float(puncture_eps)], np.concatenate([C, P, S, M[:, None]], axis=1).reshape(-1)])
+
+
+def _field_params(field_id, params):
+    fid = FIELD[field_id] if isinstance(field_id, str) else int(field_id)
+    assert 0 <= fid <= 5, "unknown field id"
+    if fid == 5:
+        return fid, np.zeros(1), 0
+    pr = np.ascontiguousarray(params, dtype=np.float64).reshape(-1)
+    if fid <= 2:
+        assert pr.size >= 2 and pr[0] == int(pr[0]) and 1 <= pr[0] < MAX_PUNCTURES and pr.size == 2 + 10 * int(pr[0]), "puncture params"
+    else:
+        assert pr.size == 8, "star params: cx, cy, cz, R, rho0, C0, alpha, beta"
+    return fid, pr, pr.size
+
+
+def field_eval(field_id, params, xyz, out, stream=None):
+    """out[i] = the problem field `field_id` (capi.FIELD name or id) at the points xyz = x[n] | y[n] | z[n]; float64 CUDA tensors.  One
+    thread per point on `stream` (a torch stream or a raw handle; default: torch's current stream), no synchronisation"""
+    import torch
+    fid, pr, n_params = _field_params(field_id, params)
+    n = out.numel()
+    assert xyz.numel() == 3 * n
+    if stream is None:
+        stream = torch.cuda.current_stream(out.device)
+    h = getattr(stream, "cuda_stream", stream)
+    load_library().d4est_hip_field_eval(ctypes.c_void_p(int(h)), fid, pr.ctypes.data_as(_vp), n_params, _ptr(xyz), n, _ptr(out))
 
 # [mesh_parameters] face_h_type / volume_h_type by the reference's names (d4est_mesh_face_h_t / d4est_mesh_volume_h_t) and the size
 # parameter arrays (D4EST_HIP_SIZE_*)
@@ -353,6 +407,7 @@ class Plan:
         """stream: a torch.cuda.Stream (its raw hipStream_t is passed through) or an int handle."""
         h = getattr(stream, "cuda_stream", stream)
         self.torch_stream = stream if hasattr(stream, "cuda_stream") else None   # parallel.attach makes it current around the exchange
+        self._stream_handle = int(h)   # the raw hipStream_t, for calls outside the plan that must be ordered with it (field_eval)
         self.lib.d4est_hip_plan_set_stream(self.handle, ctypes.c_void_p(int(h)))
 
     def last_kernel(self):
@@ -545,6 +600,7 @@ class Plan:
         keep = [_iarr(sides[k]) for k in ("side_nbr", "side_nbr_face", "side_reorder", "side_mortar_stride", "side_bndry_stride",
                                          "ghost_deg", "ghost_deg_quad")]
         self._keep_sides = keep
+        self.total_mortar_nodes = int(sides["total_mortar_nodes"])
         if "side_hang" in sides and np.any(np.asarray(sides["side_hang"]) != 0):
             hk = [_iarr(sides[k]) for k in ("side_hang", "side_sub", "side_nbr4", "side_orientation")]
             self._keep_hang = hk
@@ -947,6 +1003,124 @@ class Plan:
                                                int(imax), int(krylov_imax), float(krylov_atol), float(krylov_rtol), fn, ctx, cb, None,
                                                hist.ctypes.data_as(_c_double_p), ctypes.byref(its))
         return ierr, its.value, hist[:its.value + 1]
+
+    # ---- problem data on the device (csrc/d4est_hip_problem.hip)
+    def _brick_source(self, brick):
+        """brick = (elem_q[n, 3], elem_dq, root_len, extents) -> ctypes arguments (kept alive by the caller)"""
+        q, dq = _iarr(np.asarray(brick[0]).reshape(-1)), _iarr(brick[1])
+        ex = np.ascontiguousarray(brick[3], dtype=np.float64)
+        assert len(q[0]) == 3 * self.n_elements and len(dq[0]) == self.n_elements and ex.size == 6
+        return (q, dq, ex), (q[1], dq[1], float(brick[2]), ex.ctypes.data_as(_vp))
+
+    def _analytic_source(self, analytic):
+        """analytic = (geom_type, params, tree, q, dq, root_len) -> ctypes arguments"""
+        geom_type, params, tree, q, dq, root_len = analytic[:6]
+        pr = np.zeros(5)
+        pv = np.asarray(params, dtype=np.float64).reshape(-1)
+        pr[:pv.size] = pv
+        t, qq, d = _iarr(tree), _iarr(np.asarray(q).reshape(-1)), _iarr(dq)
+        assert len(t[0]) == self.n_elements and len(d[0]) == self.n_elements and len(qq[0]) == 3 * self.n_elements
+        return (pr, t, qq, d), (int(geom_type), pr.ctypes.data_as(_vp), t[1], qq[1], d[1], float(root_len))
+
+    def compute_xyz_brick(self, elem_q, elem_dq, root_len, extents, xyz_lobatto=None, xyz_quad=None):
+        """node coordinates of the single-tree brick on the device, the layout of compute_xyz_analytic"""
+        keep, args = self._brick_source((elem_q, elem_dq, root_len, extents))
+        assert xyz_lobatto is None or xyz_lobatto.numel() >= 3 * self.local_nodes
+        assert xyz_quad is None or xyz_quad.numel() >= 3 * self.local_nodes_quad
+        self.lib.d4est_hip_plan_compute_xyz_brick(self.handle, *args, _ptr(xyz_lobatto) if xyz_lobatto is not None else None,
+                                                  _ptr(xyz_quad) if xyz_quad is not None else None)
+
+    def _set_term(self, name, field_id, params, brick, analytic, xyz):
+        assert (brick is not None) + (analytic is not None) + (xyz is not None) == 1, "one of brick / analytic / xyz"
+        _, pr, n_params = _field_params(field_id, params)
+        pp = pr.ctypes.data_as(_vp)
+        if brick is not None:
+            keep, args = self._brick_source(brick)
+            getattr(self.lib, "d4est_hip_plan_set_%s_term_brick" % name)(self.handle, pp, n_params, *args)
+        elif analytic is not None:
+            keep, args = self._analytic_source(analytic)
+            getattr(self.lib, "d4est_hip_plan_set_%s_term_analytic" % name)(self.handle, pp, n_params, *args)
+        else:
+            assert xyz.numel() == 3 * self.local_nodes_quad
+            getattr(self.lib, "d4est_hip_plan_set_%s_term_xyz" % name)(self.handle, pp, n_params, _ptr(xyz))
+
+    def set_puncture_term(self, params, brick=None, analytic=None, xyz=None):
+        """the puncture term a (b + u)^-7 (a = -K2/8, b = 1 + sum m/(2r); capi.puncture_params) set on the plan by one kernel from
+        brick = (elem_q, elem_dq, root_len, extents), analytic = (geom_type, params, tree, q, dq, root_len) or xyz = the caller's
+        x | y | z at the quadrature nodes (a CUDA tensor); afterwards the plan is as set_nonlinear_power(a, b, -7) leaves it"""
+        self._set_term("puncture", "PUNCTURE_A", params, brick, analytic, xyz)
+
+    def set_cds_term(self, params, brick=None, analytic=None, xyz=None):
+        """the ConstantDensityStar term a u^5, a = -2 pi rho (params = cx, cy, cz, R, rho0, C0, alpha, beta); sources as
+        set_puncture_term; afterwards the plan is as set_nonlinear_power(a, None, 5) leaves it"""
+        self._set_term("cds", "CDS_A", params, brick, analytic, xyz)
+
+    def nonlinear_coefficients(self, device=None):
+        """(a, b, k) of the power term that is set: torch VIEWS of the plan-owned arrays (b None when b = 0), or None when the term is
+        off; valid until the term changes or the plan is destroyed"""
+        import torch
+        pa, pb, k = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int()
+        if not self.lib.d4est_hip_plan_nonlinear_coefficients(self.handle, ctypes.byref(pa), ctypes.byref(pb), ctypes.byref(k)):
+            return None
+        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        n = self.local_nodes_quad
+
+        def view(p):
+            if not p.value:
+                return None
+            if n == 0:
+                return torch.empty(0, dtype=torch.float64, device=dev)
+
+            class _View:
+                __cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (int(p.value), False), "version": 2, "strides": None}
+
+            t = torch.as_tensor(_View(), device=dev)
+            t._d4est_hip_plan = self
+            return t
+        return view(pa), view(pb), k.value
+
+    def compute_boundary_xyz(self, xyz_mortar, brick=None, analytic=None):
+        """x | y | z at the mortar quadrature nodes of every boundary side, indexed like sj (components total_mortar_nodes apart):
+        xyz_mortar is a float64 CUDA tensor of 3 total_mortar_nodes; entries of other sides are left untouched.  Sources as
+        set_puncture_term's brick / analytic; needs set_faces"""
+        assert (brick is None) != (analytic is None), "one of brick / analytic"
+        assert xyz_mortar.numel() == 3 * self.total_mortar_nodes
+        if brick is not None:
+            keep, args = self._brick_source(brick)
+            self.lib.d4est_hip_plan_compute_boundary_xyz_brick(self.handle, *args, _ptr(xyz_mortar))
+        else:
+            keep, args = self._analytic_source(analytic)
+            self.lib.d4est_hip_plan_compute_boundary_xyz_analytic(self.handle, *args, _ptr(xyz_mortar))
+
+    def set_robin_by_id(self, coeff_id, rhs_id, brick=None, analytic=None):
+        """Robin data from callback ids (capi.ROBIN_COEFF / capi.ROBIN_RHS names or ids) evaluated at the boundary mortar nodes on the
+        device: the state set_robin_values leaves.  'BRICK' needs the brick source; set_robin_values(None, None) switches back"""
+        assert (brick is None) != (analytic is None), "one of brick / analytic"
+        c = ROBIN_COEFF[coeff_id] if isinstance(coeff_id, str) else int(coeff_id)
+        r = ROBIN_RHS[rhs_id] if isinstance(rhs_id, str) else int(rhs_id)
+        assert c in (0, 1) and r in (0, 1), "unknown Robin id"
+        assert not (c == 1 and brick is None), "ROBIN_COEFF_BRICK needs the brick source"
+        if brick is not None:
+            keep, args = self._brick_source(brick)
+            self.lib.d4est_hip_plan_set_robin_by_id_brick(self.handle, c, r, *args)
+        else:
+            keep, args = self._analytic_source(analytic)
+            self.lib.d4est_hip_plan_set_robin_by_id_analytic(self.handle, c, r, *args)
+
+    def dirichlet_from_field(self, field_id, params, xyz_lobatto, out=None):
+        """Dirichlet data of a problem field (e.g. 'CDS_PSI') in set_dirichlet_values' layout: the three Lobatto coordinate vectors of
+        xyz_lobatto (x | y | z, 3 local_nodes) gathered to the boundary face nodes, then field_eval.  Returns the CUDA tensor"""
+        import torch
+        nb = self.lib.d4est_hip_plan_bndry_nodes(self.handle)
+        assert xyz_lobatto.numel() == 3 * self.local_nodes
+        bx = torch.empty(3 * nb, dtype=torch.float64, device=xyz_lobatto.device)
+        for d in range(3):
+            self.boundary_gather(xyz_lobatto[d * self.local_nodes:(d + 1) * self.local_nodes], bx[d * nb:(d + 1) * nb])
+        if out is None:
+            out = torch.empty(nb, dtype=torch.float64, device=xyz_lobatto.device)
+        assert out.numel() == nb
+        field_eval(field_id, params, bx, out, getattr(self, "_stream_handle", 0))   # the plan's own stream (0: the default stream)
+        return out
 
     def copy_blocks(self, n_blocks, src, src_off, dst, dst_off, length):
         """src/dst: float64 CUDA tensors; src_off/dst_off: int64 CUDA tensors; length: int32 CUDA tensor"""

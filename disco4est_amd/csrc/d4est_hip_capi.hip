@@ -35,11 +35,7 @@ void check_plan(const d4est_hip_plan_t* plan, const char* fn) {
 
 // any change of the plan's state invalidates a captured cheby_iterate graph (D4EST_HIP_TUNE_GRAPH)
 static void drop_graph(d4est_hip_plan_t* plan) {
-  if (plan->cheby_graph) { (void)hipGraphExecDestroy(plan->cheby_graph); plan->cheby_graph = nullptr; }
-  ++plan->op_generation;   // (every caller of this function changes the plan's state)
-  // w J c of the fused operator kernels is derived from J and the coefficient: every setter that can change either comes through here
-  // (plan_set_jacobian included), so the cached stream can never outlive its inputs
-  plan->lhs_wjc_valid = false;
+  d4est_hip::plan_operator_changed(plan);
 }
 
 }  // namespace

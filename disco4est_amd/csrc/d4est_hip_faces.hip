@@ -3256,6 +3256,25 @@ void faces_set_robin(d4est_hip_plan* plan, const double* coeff_quad, const doubl
   }
 }
 
+const double* faces_sj(d4est_hip_plan* plan, const char* who) {
+  if (!plan->has_face_geometry) D4EST_HIP_ABORT("%s: call d4est_hip_plan_set_mortar_geometry first (needs sj)", who);
+  return g_face_host[plan].d_sj;
+}
+
+void faces_robin_arrays(d4est_hip_plan* plan, const char* who, double** robin_c, double** robin_r) {
+  if (!plan->has_face_geometry) D4EST_HIP_ABORT("%s: call d4est_hip_plan_set_mortar_geometry first (needs sj)", who);
+  FaceHost& fh = g_face_host[plan];
+  const size_t tm = (size_t)plan->total_mortar_nodes;
+  if (!fh.d_robin_c) {
+    HIP_CHECK(hipMalloc(&fh.d_robin_c, std::max<size_t>(tm, 1) * sizeof(double)));
+    HIP_CHECK(hipMalloc(&fh.d_robin_r, std::max<size_t>(tm, 1) * sizeof(double)));
+  }
+  fh.robin = true;
+  plan->bc_inhomogeneous = true;
+  *robin_c = fh.d_robin_c;
+  *robin_r = fh.d_robin_r;
+}
+
 // resident workgroups per CU assumed by the persistent fast kernels (experiment knob: D4EST_HIP_FACE_WG_PER_CU)
 static int face_wg_per_cu() {
   static int v = -1;

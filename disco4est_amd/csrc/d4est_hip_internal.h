@@ -190,6 +190,15 @@ namespace d4est_hip {
 // and 12 = the same kernels with the 16-product body where auto / 11 take the collocated-gradient body (deg_quad = deg)
 inline bool tune_wave_eo(int tw) { return tw < 0 || tw == 11 || tw == 12; }
 
+// what every setter that changes the plan's state does first (drop_graph of d4est_hip_capi.hip, and the setters of the other units)
+inline void plan_operator_changed(d4est_hip_plan* plan) {
+  if (plan->cheby_graph) { (void)hipGraphExecDestroy(plan->cheby_graph); plan->cheby_graph = nullptr; }
+  ++plan->op_generation;   // (every caller of this function changes the plan's state)
+  // w J c of the fused operator kernels is derived from J and the coefficient: every setter that can change either comes through here
+  // (plan_set_jacobian included), so the cached stream can never outlive its inputs
+  plan->lhs_wjc_valid = false;
+}
+
 struct TreeMapParams;
 struct CellDesc;
 void launch_analytic_geometry(d4est_hip_plan* plan, const TreeMapParams& P, const CellDesc* d_cells, double root_len);
@@ -199,6 +208,15 @@ void faces_set_geometry_analytic(d4est_hip_plan* plan, const TreeMapParams& P, c
 void launch_analytic_xyz(d4est_hip_plan* plan, const TreeMapParams& P, const std::vector<CellDesc>& cells, double root_len,
                          double* xyz_lobatto, double* xyz_quad);
 void analytic_xyz_destroy(d4est_hip_plan* plan);
+// the staging half of launch_analytic_xyz, for the other units that evaluate a map at the plan's nodes (d4est_hip_problem.hip): the
+// cell descriptions copied to the device on the plan's stream (through the plan's pinned buffer) and the cached 1-D node tables --
+// bucket bi's Lobatto nodes at d_nodes + (2 bi) stride, its quadrature nodes (Gauss or Lobatto by quad_type) at d_nodes + (2 bi + 1) stride
+struct NodeTables {
+  const CellDesc* d_cells;
+  const double* d_nodes;
+  int stride;
+};
+NodeTables stage_cells_and_nodes(d4est_hip_plan* plan, const std::vector<CellDesc>& cells);
 
 // d4est_hip_sizes.hip: element size parameters (d4est_mesh_init_element_size_parameters_local / _ghost) on the plan's stream.
 // cells: the local elements followed by n_ghost ghost elements (n_ghost = 0: local elements only); brick != nullptr: the brick
@@ -245,6 +263,10 @@ int reorient_face_order(int f_m, int f_p, int o, int i);  // dGMath/d4est_refere
 int face_reorder_code(int f_m, int f_p, int o);            // dGMath/d4est_operators.c:2031-2050
 void faces_set_dirichlet(d4est_hip_plan* plan, const double* g_lobatto, int on_device);
 void faces_set_robin(d4est_hip_plan* plan, const double* coeff_quad, const double* rhs_quad, int on_device);
+// raw sj at the mortar nodes (side_mortar_stride[s] + k) and the plan's Robin arrays sj coeff / sj rhs, allocated if need be and switched
+// on as faces_set_robin does -- the caller fills the boundary sides' entries on the plan's stream; both abort with `who` without sj
+const double* faces_sj(d4est_hip_plan* plan, const char* who);
+void faces_robin_arrays(d4est_hip_plan* plan, const char* who, double** robin_c, double** robin_r);
 void launch_traces(d4est_hip_plan* plan, const double* u, double* trace, bool ghost, const int* elist = nullptr, int n_list = 0, int parts = 3 /* see launch_flux */);
 // Chebyshev update carried by the flux kernel's epilogue (flux_wave_kernel<true>): r = alpha (rhs - Au), p = r + beta p, u += p
 struct ChebyFuse {
@@ -408,6 +430,9 @@ void krylov_destroy(d4est_hip_plan* plan);
 
 // d4est_hip_nonlinear.hip
 void nonlinear_destroy(d4est_hip_plan* plan);
+// the plan-owned a (and, with_b, b; else b is dropped and *b = nullptr) of the power term with exponent k, allocated if need be: the
+// state d4est_hip_plan_set_nonlinear_power leaves, for a caller that writes the values itself on the plan's stream
+void nonlinear_term_arrays(d4est_hip_plan* plan, int k, bool with_b, double** a, double** b);
 
 // d4est_hip_capi.hip (defined among its extern "C" entry points; not in the header: internal): {geom_type, params} of the analytic entry
 // points -> TreeMapParams; aborts with `who` on a bad type, radius or flag

@@ -346,6 +346,20 @@ static void ensure_uq(d4est_hip_plan* plan, NonlinHost* h) {
   if (!h->d_uq) HIP_CHECK(hipMalloc(&h->d_uq, nq_alloc(plan)));
 }
 
+void nonlinear_term_arrays(d4est_hip_plan* plan, int k, bool with_b, double** a, double** b) {
+  NonlinHost* h = host_of(plan);
+  if (!h) { h = new NonlinHost; plan->nonlin = h; }
+  if (!h->d_a) HIP_CHECK(hipMalloc(&h->d_a, nq_alloc(plan)));
+  if (with_b) {
+    if (!h->d_b) HIP_CHECK(hipMalloc(&h->d_b, nq_alloc(plan)));
+  } else {
+    (void)hipFree(h->d_b); h->d_b = nullptr;
+  }
+  h->k = k;
+  *a = h->d_a;
+  *b = h->d_b;
+}
+
 void nonlinear_destroy(d4est_hip_plan* plan) {
   NonlinHost* h = host_of(plan);
   if (!h) return;
@@ -366,25 +380,30 @@ extern "C" {
 void d4est_hip_plan_set_nonlinear_power(d4est_hip_plan_t* plan, const double* a_quad_dev, const double* b_quad_dev, int k) {
   if (!plan) D4EST_HIP_ABORT("plan_set_nonlinear_power: NULL plan");
   if (k < -16 || k > 16) D4EST_HIP_ABORT("plan_set_nonlinear_power: k = %d is outside [-16, 16]", k);
-  NonlinHost* h = d4est_hip::host_of(plan);
-  if (!h) { h = new NonlinHost; plan->nonlin = h; }
   const size_t bytes = (size_t)plan->local_nodes_quad * sizeof(double);
   if (!a_quad_dev) {   // the term is off
+    NonlinHost* h = d4est_hip::host_of(plan);
+    if (!h) { h = new NonlinHost; plan->nonlin = h; }
     (void)hipFree(h->d_a); h->d_a = nullptr;
     (void)hipFree(h->d_b); h->d_b = nullptr;
     h->k = 0;
     return;
   }
   // the values are CAPTURED here, as d4est_hip_plan_set_lhs_coefficient captures its coefficient
-  if (!h->d_a) HIP_CHECK(hipMalloc(&h->d_a, d4est_hip::nq_alloc(plan)));
-  HIP_CHECK(hipMemcpyAsync(h->d_a, a_quad_dev, bytes, hipMemcpyDeviceToDevice, plan->stream));
-  if (b_quad_dev) {
-    if (!h->d_b) HIP_CHECK(hipMalloc(&h->d_b, d4est_hip::nq_alloc(plan)));
-    HIP_CHECK(hipMemcpyAsync(h->d_b, b_quad_dev, bytes, hipMemcpyDeviceToDevice, plan->stream));
-  } else {
-    (void)hipFree(h->d_b); h->d_b = nullptr;
-  }
-  h->k = k;
+  double *d_a = nullptr, *d_b = nullptr;
+  d4est_hip::nonlinear_term_arrays(plan, k, b_quad_dev != nullptr, &d_a, &d_b);
+  HIP_CHECK(hipMemcpyAsync(d_a, a_quad_dev, bytes, hipMemcpyDeviceToDevice, plan->stream));
+  if (b_quad_dev) HIP_CHECK(hipMemcpyAsync(d_b, b_quad_dev, bytes, hipMemcpyDeviceToDevice, plan->stream));
+}
+
+int d4est_hip_plan_nonlinear_coefficients(const d4est_hip_plan_t* plan, const double** a_dev, const double** b_dev, int* k) {
+  if (!plan) D4EST_HIP_ABORT("plan_nonlinear_coefficients: NULL plan");
+  const NonlinHost* h = d4est_hip::host_of(plan);
+  if (!h || !h->d_a) return 0;
+  if (a_dev) *a_dev = h->d_a;
+  if (b_dev) *b_dev = h->d_b;
+  if (k) *k = h->k;
+  return 1;
 }
 
 void d4est_hip_apply_nonlinear_term(d4est_hip_plan_t* plan, const double* u_dev, int beta, double* out_dev) {

@@ -2135,8 +2135,7 @@ struct XyzHost {
   hipEvent_t copied = nullptr;
 };
 
-void launch_analytic_xyz(d4est_hip_plan* plan, const TreeMapParams& P, const std::vector<CellDesc>& cells, double root_len,
-                         double* xyz_lobatto, double* xyz_quad) {
+NodeTables stage_cells_and_nodes(d4est_hip_plan* plan, const std::vector<CellDesc>& cells) {
   XyzHost* xh = static_cast<XyzHost*>(plan->xyz);
   if (!xh) {
     xh = new XyzHost;
@@ -2167,6 +2166,12 @@ void launch_analytic_xyz(d4est_hip_plan* plan, const TreeMapParams& P, const std
     HIP_CHECK(hipMemcpyAsync(xh->d_cells, xh->h_cells, cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice, plan->stream));
   }
   HIP_CHECK(hipEventRecord(xh->copied, plan->stream));
+  return NodeTables{xh->d_cells, xh->d_nodes, xh->stride};
+}
+
+void launch_analytic_xyz(d4est_hip_plan* plan, const TreeMapParams& P, const std::vector<CellDesc>& cells, double root_len,
+                         double* xyz_lobatto, double* xyz_quad) {
+  const NodeTables nt = stage_cells_and_nodes(plan, cells);
   for (size_t bi = 0; bi < plan->buckets.size(); ++bi) {
     const Bucket& bk = plan->buckets[bi];
     if (bk.n_elem == 0) continue;
@@ -2177,7 +2182,7 @@ void launch_analytic_xyz(d4est_hip_plan* plan, const TreeMapParams& P, const std
       const long long threads = (long long)bk.n_elem * Nn * Nn * Nn;
       hipLaunchKernelGGL(analytic_xyz_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, plan->stream,
                          plan->d_elem_ids + bk.elem_offset, (which ? plan->d_qs_list : plan->d_ns_list) + bk.elem_offset, bk.n_elem, Nn,
-                         xh->d_nodes + (2 * bi + which) * xh->stride, xh->d_cells, P, root_len,
+                         nt.d_nodes + (2 * bi + which) * nt.stride, nt.d_cells, P, root_len,
                          (size_t)(which ? plan->local_nodes_quad : plan->local_nodes), out);
     }
   }

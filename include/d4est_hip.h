@@ -470,7 +470,8 @@ void d4est_hip_ip_energy_norm_sqr(d4est_hip_plan_t* plan, const double* v_dev, c
 void d4est_hip_masked_sum(d4est_hip_plan_t* plan, const double* elem_dev, const int* skip_dev, double* sum_dev);
 /* total_bndry_nodes of plan_set_faces, and a device volume vector's values at the Lobatto face nodes of every boundary side in the layout
  * of d4est_hip_plan_set_dirichlet_values (side_bndry_stride; d4est_operators_apply_slicer order): where a host evaluates Dirichlet data
- * from the node coordinates (the three coordinate vectors gathered one by one) */
+ * from the node coordinates (the three coordinate vectors gathered one by one).  On the device: d4est_hip_field_eval (e.g. CDS_PSI) on
+ * the three gathered vectors stored x | y | z gives the array d4est_hip_plan_set_dirichlet_values(on_device = 1) takes */
 int d4est_hip_plan_bndry_nodes(const d4est_hip_plan_t* plan);
 void d4est_hip_plan_boundary_gather(d4est_hip_plan_t* plan, const double* vol_dev, double* bndry_dev);
 /* Dirichlet values on the Lobatto face nodes of every boundary side (EVAL_BNDRY_FCN_ON_LOBATTO,
@@ -614,7 +615,8 @@ int d4est_hip_fcg_solve(d4est_hip_plan_t* plan, double* u_dev, const double* rhs
  *   two_punctures_neg_1o8_K2_psi_neg7 / two_punctures_plus_7o8_K2_psi_neg8 (src/Problems/TwoPunctures/two_punctures_fcns.h:252-284 /
  *     :288-320): a = -K^2 / 8 (0 inside puncture_eps), b = 1 + sum_n m_n / (2 r_n), k = -7
  * a and b depend on the mesh only: the caller evaluates them once per mesh at the quadrature nodes (d4est_hip_plan_compute_xyz_analytic
- * gives xyz_quad on the device).
+ * gives xyz_quad on the device), or leaves it to d4est_hip_plan_set_puncture_term_* / _set_cds_term_* (below, "problem data on the
+ * device"), which write a and b of the two shipped problems into the plan from forest coordinates in one kernel.
  *
  * d4est_hip_plan_set_nonlinear_power registers the term.  a_quad_dev, b_quad_dev: local_nodes_quad doubles each, element e at
  * quad_stride[e] (device arrays; their values are CAPTURED by this call into plan-owned copies, as d4est_hip_plan_set_lhs_coefficient
@@ -1040,6 +1042,113 @@ void d4est_hip_probe_eval_gradient(d4est_hip_probe_t* probe, const double* u_dev
 /* data.xyz (d4est_mesh.c:3332): xyz_host[3 p + d] = the map of probe_set_map at (tree, abc) of point p (NaN where err = 1).  Needs a map;
  * synchronises the stream. */
 void d4est_hip_probe_xyz(d4est_hip_probe_t* probe, double* xyz_host);
+
+/* ---- problem data on the device: puncture and star source fields, Robin data by id (csrc/d4est_hip_problem.hip) ------------------------
+ * The coefficient functions of the reference's shipped nonlinear drivers (TwoPunctures, multi-puncture, ConstantDensityStar) evaluated
+ * where the coordinates already are, so that no array of quadrature size crosses the bus when the mesh changes.  All arithmetic of this
+ * unit is compiled without floating-point contraction (no fused multiply-add): a field's value does not depend on the kernel that
+ * evaluates it, and the term entries below give the bits of d4est_hip_field_eval on the coordinates of d4est_hip_plan_compute_xyz_*.
+ *
+ * Field ids (x, y, z -> one double):
+ *   PUNCTURE_K2  confAij_sqr (src/Problems/TwoPunctures/two_punctures_fcns.h:180-248).  Not a transcription of the Levi-Civita loops:
+ *                per puncture n = (x - C) / r, P.n and S x n are formed once, the six independent components of the symmetric
+ *                A_ij = sum_n (1 / r^2) (n_i P_j + n_j P_i - (delta_ij - n_i n_j) P.n + (2 / r) ((S x n)_i n_j + (S x n)_j n_i))
+ *                are accumulated over the punctures, and K2 = sum_ij (3/2 A_ij)^2 with the diagonal once and the off-diagonal twice.
+ *   PUNCTURE_A   -K2 / 8, the `a` of two_punctures_neg_1o8_K2_psi_neg7 (:252-284), and exactly 0.0 where r > puncture_eps fails
+ *   PUNCTURE_B   1 + sum_n m_n / (2 r_n) (:263-274), the `b` of the same callback (psi_0 = b + u)
+ *   CDS_A        -2 pi rho(x), the `a` of neg_2pi_rho_up1_neg5 (src/Problems/ConstantDensityStar/constant_density_star_fcns.h:276-301,
+ *                :347-357): -2 pi rho0 for r^2 <= R^2, else 0
+ *   CDS_PSI      psi_fcn (:246-273): 1 + beta / r for r^2 > R^2, else C0 u_alpha (:88-111); the analytic solution and the Dirichlet
+ *                boundary function (:303-330)
+ *   INV_R        1 / sqrt(x^2 + y^2 + z^2): two_punctures_robin_coeff_sphere_fcn (two_punctures_fcns.h:640-655),
+ *                constant_density_star_robin_coeff_sphere_fcn and _robin_bc_rhs_for_res_fcn (constant_density_star_fcns.h:9-24, :42-57)
+ * Two behaviours of the reference are kept:
+ *   (a) compute_confAij moves a point that lies exactly on a puncture to r = puncture_eps (:202-203): n = 0 there, the puncture
+ *       contributes nothing and K2 is finite;
+ *   (b) the test r > puncture_eps of the two power callbacks reads r after the loop, i.e. the distance to the LAST puncture only
+ *       (:264-277).  On and within puncture_eps of the last puncture a = 0.0; exactly on an earlier puncture a is finite and b = +inf, so
+ *       that the power kernels give a (1 / inf^7) = 0, not NaN.
+ * params (host doubles): the puncture fields take {num_punctures, puncture_eps, then per puncture C[3], P[3], S[3], M}, n_params =
+ * 2 + 10 num_punctures, 1 <= num_punctures <= 9 (the reference's num_punctures < MAX_PUNCTURES = 10); the star fields take {cx, cy, cz,
+ * R, rho0, C0, alpha, beta}, n_params = 8 (alpha from the reference's bisection, constant_density_star_fcns.h:151-243, which stays on the
+ * host); INV_R takes none (params may be NULL).  A bad id or count aborts.
+ *
+ * d4est_hip_field_eval: out_dev[i] = field(xyz_dev[i], xyz_dev[n + i], xyz_dev[2 n + i]), the x | y | z layout of
+ * d4est_hip_plan_compute_xyz_analytic; one thread per point on hip_stream (a hipStream_t, NULL = the default stream), no host
+ * synchronisation, no allocation. */
+#define D4EST_HIP_FIELD_PUNCTURE_K2 0
+#define D4EST_HIP_FIELD_PUNCTURE_A 1
+#define D4EST_HIP_FIELD_PUNCTURE_B 2
+#define D4EST_HIP_FIELD_CDS_A 3
+#define D4EST_HIP_FIELD_CDS_PSI 4
+#define D4EST_HIP_FIELD_INV_R 5
+#define D4EST_HIP_MAX_PUNCTURES 10
+void d4est_hip_field_eval(void* hip_stream, int field_id, const double* params, int n_params, const double* xyz_dev, long long n,
+                          double* out_dev);
+/* x | y | z of the single-tree brick at the plan's Lobatto and / or quadrature nodes (either output may be NULL), the layout and node
+ * order of d4est_hip_plan_compute_xyz_analytic: x_d = X0_d + (X1_d - X0_d) (q_d + dq (r_d + 1) / 2) / root_len
+ * (d4est_geometry_brick_X, src/Geometry/d4est_geometry_brick.c:119-149, on one tree).  elem_q[3 e + d] / elem_dq[e]: the elements'
+ * corner and side length in p4est units, extents = {X0, X1, Y0, Y1, Z0, Z1} as in d4est_hip_plan_set_geometry_brick. */
+void d4est_hip_plan_compute_xyz_brick(d4est_hip_plan_t* plan, const int* elem_q, const int* elem_dq, double root_len,
+                                      const double* extents, double* xyz_lobatto_dev, double* xyz_quad_dev);
+/* The puncture term a (b + u)^-7, a = PUNCTURE_A, b = PUNCTURE_B, and the star term a u^5, a = CDS_A, b = NULL, set on a plan by ONE
+ * kernel: a workgroup per element, a thread per quadrature node takes the node's tree coordinate from the element's q / dq and the
+ * plan's quadrature abscissae (Gauss or Lobatto by the plan's quad_type), evaluates the map, then a and b, and writes them into the
+ * plan-owned arrays d4est_hip_plan_set_nonlinear_power would have filled by copy.  No xyz_quad temporary, no caller-side a / b, no
+ * copy; mixed-degree plans in one launch.  Afterwards the plan is in the state set_nonlinear_power(a, b, k) leaves (k = -7 / k = 5):
+ * d4est_hip_apply_nonlinear_term, _plan_linearise, _build_residual and _newton_solve work unchanged.  Replaces the caller-side loop over
+ * xyz_quad with the callbacks cited above.  Coordinate sources:
+ *   _brick     elem_q, elem_dq, root_len, extents as in d4est_hip_plan_compute_xyz_brick
+ *   _analytic  geom_type, geom_params, elem_tree, elem_q, elem_dq, root_len as in d4est_hip_plan_set_geometry_analytic
+ *   _xyz       the caller's xyz_quad_dev (x | y | z, 3 local_nodes_quad doubles), for numerical geometry
+ * Stream-ordered after a staging copy of the element descriptions; the term's values equal d4est_hip_field_eval on the coordinates of
+ * d4est_hip_plan_compute_xyz_brick / _analytic bit for bit. */
+void d4est_hip_plan_set_puncture_term_brick(d4est_hip_plan_t* plan, const double* params, int n_params, const int* elem_q,
+                                            const int* elem_dq, double root_len, const double* extents);
+void d4est_hip_plan_set_puncture_term_analytic(d4est_hip_plan_t* plan, const double* params, int n_params, int geom_type,
+                                               const double* geom_params, const int* elem_tree, const int* elem_q, const int* elem_dq,
+                                               double root_len);
+void d4est_hip_plan_set_puncture_term_xyz(d4est_hip_plan_t* plan, const double* params, int n_params, const double* xyz_quad_dev);
+void d4est_hip_plan_set_cds_term_brick(d4est_hip_plan_t* plan, const double* params, int n_params, const int* elem_q, const int* elem_dq,
+                                       double root_len, const double* extents);
+void d4est_hip_plan_set_cds_term_analytic(d4est_hip_plan_t* plan, const double* params, int n_params, int geom_type,
+                                          const double* geom_params, const int* elem_tree, const int* elem_q, const int* elem_dq,
+                                          double root_len);
+void d4est_hip_plan_set_cds_term_xyz(d4est_hip_plan_t* plan, const double* params, int n_params, const double* xyz_quad_dev);
+/* the plan-owned a and b (device, local_nodes_quad doubles; *b_dev NULL: b = 0) and k of the power term that is set; returns 0 and
+ * writes nothing when the term is off.  Any output may be NULL.  The arrays live until the term is switched off or the plan destroyed. */
+int d4est_hip_plan_nonlinear_coefficients(const d4est_hip_plan_t* plan, const double** a_dev, const double** b_dev, int* k);
+/* xyz_m_mortar_quad of the boundary faces (src/Mesh/d4est_mesh.c:514-640, consumed at src/dGMath/d4est_laplacian_flux.c:47-112,
+ * :200-204): x | y | z at the mortar quadrature nodes of every boundary side, indexed like sj -- side_mortar_stride[s] + k, the
+ * components total_mortar_nodes apart (3 total_mortar_nodes doubles), k = a + NQ b over the face's two axes in increasing order, the
+ * order in which the boundary flux kernels read sj and the Robin arrays.  The map is evaluated AT the face's quadrature points
+ * (d4est_mesh.c:604-625), not interpolated from Lobatto nodes.  Entries of sides that are not boundary sides are left untouched.
+ * Needs plan_set_faces; no ghost data is read (boundary sides are local).  Sources as for the term entries.  Unlike them, these two
+ * entries and d4est_hip_plan_set_robin_by_id_* below are set-up calls that SYNCHRONISE: each builds the list of boundary sides on the
+ * host, uploads it, and waits for its kernel before freeing the list. */
+void d4est_hip_plan_compute_boundary_xyz_brick(d4est_hip_plan_t* plan, const int* elem_q, const int* elem_dq, double root_len,
+                                               const double* extents, double* xyz_mortar_dev);
+void d4est_hip_plan_compute_boundary_xyz_analytic(d4est_hip_plan_t* plan, int geom_type, const double* geom_params, const int* elem_tree,
+                                                  const int* elem_q, const int* elem_dq, double root_len, double* xyz_mortar_dev);
+/* Robin data from callback ids: one kernel over the boundary sides' mortar nodes evaluates the map, the coefficient and the right-hand
+ * side and writes sj coeff and sj rhs into the plan's Robin arrays -- the state d4est_hip_plan_set_robin_values leaves, without a
+ * coordinate array in between.  coeff_id: ROBIN_COEFF_INV_R (the sphere callbacks cited at INV_R) or ROBIN_COEFF_BRICK
+ * (two_punctures_robin_coeff_brick_fcn, two_punctures_fcns.h:612-638: n_axis x_axis / r^2; on a brick the normal of face f is
+ * +-e_axis, so the coefficient is sign(f) x_axis / r^2 and no normal array is read); rhs_id: ROBIN_RHS_ZERO (two_punctures_robin_bc_rhs_fcn
+ * :659-673, constant_density_star_robin_bc_rhs_for_jac_fcn :26-40) or ROBIN_RHS_INV_R (constant_density_star_robin_bc_rhs_for_res_fcn
+ * :42-57).  ROBIN_COEFF_BRICK exists on the _brick source only.  Needs the mortar factors (sj);
+ * d4est_hip_plan_set_robin_values(plan, NULL, ...) still switches back to Dirichlet.
+ * Dirichlet data needs no entry of its own: d4est_hip_field_eval(CDS_PSI) on the three d4est_hip_plan_boundary_gather'ed Lobatto
+ * coordinate vectors (stored x | y | z) gives the array d4est_hip_plan_set_dirichlet_values(on_device = 1) takes.
+ * Not built: the Lorentzian and Stamm problem functions, the Cactus-data variants, the alpha bisection. */
+#define D4EST_HIP_ROBIN_COEFF_INV_R 0
+#define D4EST_HIP_ROBIN_COEFF_BRICK 1
+#define D4EST_HIP_ROBIN_RHS_ZERO 0
+#define D4EST_HIP_ROBIN_RHS_INV_R 1
+void d4est_hip_plan_set_robin_by_id_brick(d4est_hip_plan_t* plan, int coeff_id, int rhs_id, const int* elem_q, const int* elem_dq,
+                                          double root_len, const double* extents);
+void d4est_hip_plan_set_robin_by_id_analytic(d4est_hip_plan_t* plan, int coeff_id, int rhs_id, int geom_type, const double* geom_params,
+                                             const int* elem_tree, const int* elem_q, const int* elem_dq, double root_len);
 
 #ifdef __cplusplus
 }
