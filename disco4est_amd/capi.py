@@ -123,6 +123,7 @@ SIGNATURES = {
     "d4est_hip_build_rhs_with_strong_bc": (None, [_vp, _vp, ctypes.c_int, _vp]),
     "d4est_hip_build_rhs_with_strong_bc_host": (None, [_vp, _c_double_p, ctypes.c_int, _c_double_p]),
     "d4est_hip_plan_set_lhs_coefficient": (None, [_vp, _vp]),
+    "d4est_hip_plan_lhs_coefficient_arrays": (ctypes.c_int, [_vp, _vp, _vp]),
     "d4est_hip_plan_matrix_nodes": (ctypes.c_longlong, [_vp]),
     "d4est_hip_compute_weighted_mass_blocks": (None, [_vp, _vp, _vp]),
     "d4est_hip_plan_set_lhs_element_blocks": (None, [_vp, _vp, _vp]),
@@ -1063,21 +1064,34 @@ class Plan:
         if not self.lib.d4est_hip_plan_nonlinear_coefficients(self.handle, ctypes.byref(pa), ctypes.byref(pb), ctypes.byref(k)):
             return None
         dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        return self._quad_view(pa, dev), self._quad_view(pb, dev), k.value
+
+    def _quad_view(self, p, dev):
+        """a torch VIEW of local_nodes_quad plan-owned doubles at the device pointer p (a ctypes.c_void_p; NULL: None)"""
+        import torch
         n = self.local_nodes_quad
+        if not p.value:
+            return None
+        if n == 0:
+            return torch.empty(0, dtype=torch.float64, device=dev)
 
-        def view(p):
-            if not p.value:
-                return None
-            if n == 0:
-                return torch.empty(0, dtype=torch.float64, device=dev)
+        class _View:
+            __cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (int(p.value), False), "version": 2, "strides": None}
 
-            class _View:
-                __cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (int(p.value), False), "version": 2, "strides": None}
+        t = torch.as_tensor(_View(), device=dev)
+        t._d4est_hip_plan = self
+        return t
 
-            t = torch.as_tensor(_View(), device=dev)
-            t._d4est_hip_plan = self
-            return t
-        return view(pa), view(pb), k.value
+    def lhs_coefficient_arrays(self, device=None):
+        """(c, w J c) of the coefficient form that is set (set_lhs_coefficient / linearise): torch VIEWS of the plan-owned arrays, w J c
+        None while it is not formed (the first apply that needs it forms it), or None when no coefficient form is set; the views follow
+        every later set_lhs_coefficient / linearise on the plan's stream and are valid until the plan is destroyed"""
+        import torch
+        pc, pw = ctypes.c_void_p(), ctypes.c_void_p()
+        if not self.lib.d4est_hip_plan_lhs_coefficient_arrays(self.handle, ctypes.byref(pc), ctypes.byref(pw)):
+            return None
+        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        return self._quad_view(pc, dev), self._quad_view(pw, dev)
 
     def compute_boundary_xyz(self, xyz_mortar, brick=None, analytic=None):
         """x | y | z at the mortar quadrature nodes of every boundary side, indexed like sj (components total_mortar_nodes apart):

@@ -634,6 +634,14 @@ void d4est_hip_plan_set_lhs_coefficient(d4est_hip_plan_t* plan, const double* co
   }
 }
 
+int d4est_hip_plan_lhs_coefficient_arrays(const d4est_hip_plan_t* plan, const double** c_dev, const double** wjc_dev) {
+  if (!plan) D4EST_HIP_ABORT("plan_lhs_coefficient_arrays: NULL plan");
+  if (!plan->d_lhs_coeff) return 0;
+  if (c_dev) *c_dev = plan->d_lhs_c;
+  if (wjc_dev) *wjc_dev = plan->lhs_wjc_valid ? plan->d_lhs_wjc : nullptr;
+  return 1;
+}
+
 void d4est_hip_apply_inverse_mass_matrix(d4est_hip_plan_t* plan, const double* in_dev, double* out_dev) {
   check_plan(plan, "apply_inverse_mass_matrix");
   d4est_hip::launch_mass_like(plan, 4, in_dev, out_dev, nullptr, 1);

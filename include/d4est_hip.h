@@ -520,6 +520,12 @@ void d4est_hip_build_rhs_with_strong_bc_host(d4est_hip_plan_t* plan, const doubl
  * The term then is part of d4est_hip_apply_lhs, _cheby_iterate, _cg_eigs and _schwarz_smooth; set on a Schwarz subdomain plan
  * (same array: the copies' quad_stride alias it) it is part of the subdomain operator.  d4est_hip_apply_aij stays the Laplacian. */
 void d4est_hip_plan_set_lhs_coefficient(d4est_hip_plan_t* plan, const double* coeff_quad_dev);
+/* The coefficient form as the plan holds it (read-only, for checks and diagnostics): *c_dev = the plan-owned copy of c, *wjc_dev = the
+ * pre-combined w J c of the operator kernels (device, local_nodes_quad doubles each, element e at quad_stride[e]), or NULL while w J c is
+ * not formed -- d4est_hip_plan_set_lhs_coefficient and a d4est_hip_plan_linearise on the composed path leave it to the first apply that
+ * needs it.  Returns 0 and writes nothing when no coefficient form is set, else 1.  Either output pointer may be NULL.  The arrays live
+ * until the plan is destroyed; their contents change with every set_lhs_coefficient / plan_linearise, on the plan's stream. */
+int d4est_hip_plan_lhs_coefficient_arrays(const d4est_hip_plan_t* plan, const double** c_dev, const double** wjc_dev);
 /* ---- the multigrid MATRIX OPERATOR: the zeroth-order term on the coarse levels (csrc/d4est_hip_mgmatrix.hip) -------------------------
  * With use_matrix_operator = 1 (e.g. constant_density_star_mgpc_newton_petsc.c:591-602) the reference holds the term
  * V^T W J f(x, u0) V as ONE DENSE BLOCK PER ELEMENT on the finest level (d4est_solver_multigrid_matrix_setup_fofufofvlilj_operator,

@@ -79,8 +79,39 @@ def test_newton_loop_counts():
     assert len(hist) == 2
 
 
+def _macro_pairs(source, macro):
+    """the X(N, NQ) list of `#define macro(X) ...` (continuation lines included) in csrc/<source>"""
+    txt = open(os.path.join(ROOT, "disco4est_amd", "csrc", source)).read()
+    found = re.findall(r"^#define\s+%s\(X\)((?:[^\n]*\\\n)*[^\n]*)\n" % re.escape(macro), txt, flags=re.M)
+    assert len(found) == 1, "%s: %d definitions of %s" % (source, len(found), macro)
+    body = found[0].replace("\\\n", " ")
+    pairs = [(int(a), int(b)) for a, b in re.findall(r"X\(\s*(\d+)\s*,\s*(\d+)\s*\)", body)]
+    assert re.sub(r"X\(\s*\d+\s*,\s*\d+\s*\)", "", body).strip() == "", "%s holds more than X(N, NQ) entries: %r" % (macro, body)
+    return pairs
+
+
+def test_sweep_covers_the_compiled_pairs():
+    """tests/test_nonlinear_sweep_gpu.py launches what D4EST_HIP_NONLIN_PAIRS compiles, no more and no less; the macro is the union of
+    the two pair lists of the Galerkin integral's one-kernel path, as its comment says; and every listed pair fits pair_built's LDS limit
+    (WaveCfg::LDS_BYTES = 2 EPB NQ^2 (NQ | 1) doubles), so none of them silently composes"""
+    from tests.test_nonlinear_sweep_gpu import PAIRS, elements_per_workgroup
+    nonlin = _macro_pairs("d4est_hip_nonlinear.hip", "D4EST_HIP_NONLIN_PAIRS")
+    assert len(nonlin) == len(set(nonlin)) == 26
+    assert PAIRS == nonlin
+    fast = _macro_pairs("d4est_hip_volume.hip", "D4EST_HIP_FAST_PAIRS")
+    big = _macro_pairs("d4est_hip_volume.hip", "D4EST_HIP_BIG_PAIRS")
+    assert not set(fast) & set(big) and len(fast + big) == len(set(fast + big))
+    assert set(nonlin) == set(fast) | set(big)
+    for N, NQ in nonlin:
+        assert 2 <= N <= NQ
+        assert elements_per_workgroup(NQ) == max(1, 64 // (NQ * NQ))
+        lds = 2 * max(1, 64 // (NQ * NQ)) * NQ * NQ * (NQ | 1) * 8
+        assert lds <= 160 * 1024, (N, NQ, lds)
+    assert 2 * 256 * 17 * 8 == 69632 and 2 * 400 * 21 * 8 == 134400      # (16,16) and (20,20): past 64 KB, the opt-in limit
+
+
 _SYMBOLS = ["d4est_hip_plan_set_nonlinear_power", "d4est_hip_apply_nonlinear_term", "d4est_hip_plan_linearise", "d4est_hip_build_residual",
-            "d4est_hip_newton_solve"]
+            "d4est_hip_newton_solve", "d4est_hip_plan_lhs_coefficient_arrays"]
 
 
 def test_entry_points_are_declared_and_exported(hiplib):
