@@ -415,7 +415,9 @@ class Plan:
         return self.lib.d4est_hip_plan_last_kernel(self.handle).decode()
 
     def face_path(self):
-        """'direct' or 'two-phase': which face kernels the full operator runs on this plan."""
+        """which face kernels the full operator runs on this plan: 'direct', 'direct+volume', 'two-phase' or 'hybrid...: direct+volume on C
+        clean elements, two-phase on D' -- on a plan with ghost sides under set_tuning(14, 2): '... on C clean elements (G beside ghost
+        sides), two-phase on D'."""
         return self.lib.d4est_hip_plan_face_path(self.handle).decode()
 
     def stream_mode(self):

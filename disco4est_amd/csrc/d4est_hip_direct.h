@@ -14,6 +14,11 @@ struct DirectSide {
   int geom;            // scalar offset of the side's mortar data (7 combined factors at 7*geom; Dirichlet / Robin data at geom)
   int pad;
 };
+// kind 2 on the hybrid operator's element lists of a plan with ghost sides (VOL & 32): the (+) block -- a ghost element's, as its owner's
+// trace kernel wrote it, in that element's own face order; the kernel re-orients it with the side's code like any kind-2 block -- sits in the
+// ghost trace buffer, not in the trace array the other kind-2 sides of the launch read; never exported
+// (bit 5 of kcf, which only kind 1 uses otherwise: every field of the descriptor stays a scalar operand)
+constexpr int DIRECT_KCF_GHOST = 32;
 // kind 2 only: offset of the (+) block in the ghost trace buffer, in its own array (read inside the ghost branch)
 typedef long long DirectGhostOff;
 
@@ -45,7 +50,10 @@ struct DirectVol {
   const double* EGf = nullptr;
   const double* EBb = nullptr;
   const double* EGb = nullptr;
-  const double* affine = nullptr;    // AFF: 6 numbers per element
+  union {
+    const double* affine = nullptr;  // AFF: 6 numbers per element
+    const double* ghost_buf;         // ghost-aware hybrid instances (VOL & 32; streamed metric, never AFF): the plan's ghost trace buffer, which
+  };                                 // a kind-2 side with DIRECT_KCF_GHOST reads instead of ghost_qtrace (same slot: the kernel-argument layout stays)
   const double* wq = nullptr;        // AFF: quadrature weights
   int qs0 = 0, qs_stride = 0;
   const int* qs_list = nullptr;      // quadrature offset per element where the offsets are not affine (qs_stride < 0): a Schwarz

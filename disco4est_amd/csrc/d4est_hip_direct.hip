@@ -153,7 +153,11 @@ __device__ __forceinline__ void direct_load_geom(double* gq, int kind, bool on, 
 // element's sub-mortar trace, written by trace_hp_mfma16_kernel before this kernel -- sits in the plan's trace array (passed as
 // ghost_qtrace), and the side's own mortar-node block (u, du/dr_0..2: what the trace kernels would write) is exported to that
 // array at nbr_ns, for the record flux kernel of the big element across it, which runs after this kernel.
-template <int N, int NQ, bool EO, bool FUSE, int VOL = 0 /* 0 faces only; + volume term: 1 streamed metric, 2 affine metric; + 4: and the zeroth-order term; + 8: stream mode (non-temporal metric / factor loads and A u stores); + 16: hanging-aware */>
+// VOL & 32 (with 16; the hybrid operator's ghost-adjacent elements on a sharded plan): a kind-2 side with DIRECT_KCF_GHOST in its kcf is a
+// conforming side against a GHOST element of the same degree -- its (+) block comes from the ghost trace buffer (DirectVol::ghost_buf,
+// filled by the exchange before this launch), in mortar-node order like every kind-2 block, and nothing is exported (nbr_ns = -1: the
+// ring's trace kernel writes the side's own block for the exchange).  The other kind-2 sides of the element keep reading ghost_qtrace.
+template <int N, int NQ, bool EO, bool FUSE, int VOL = 0 /* 0 faces only; + volume term: 1 streamed metric, 2 affine metric; + 4: and the zeroth-order term; + 8: stream mode (non-temporal metric / factor loads and A u stores); + 16: hanging-aware; + 32: ghost-aware */>
 __global__ __launch_bounds__(64 * kDirectWPB, 4) void faces_direct_kernel(const double* __restrict__ u, const double* __restrict__ ghost_qtrace,
                                                              double* __restrict__ Au, const DirectSide* __restrict__ sides,
                                                              const DirectGhostOff* __restrict__ ghost_off,
@@ -358,7 +362,11 @@ __global__ __launch_bounds__(64 * kDirectWPB, 4) void faces_direct_kernel(const 
 #pragma unroll
           for (int c = 0; c < 4; ++c) qp[c] = lds_ld(&s_S[(4 + c) * QS + kp]);
         } else if (kind == 2) {
-          const double* __restrict__ p = K->ghost_qtrace + K->ghost_off[6 * (size_t)e + 2 * d + h] + reorder_index(code, NQ - 1, a, b);
+          const double* __restrict__ gb = K->ghost_qtrace;
+          if constexpr ((VOL & 32) != 0) {
+            if ((kcf[h] & DIRECT_KCF_GHOST) != 0) gb = K->vol.ghost_buf;   // (wave-uniform: a scalar select between the two bases)
+          }
+          const double* __restrict__ p = gb + K->ghost_off[6 * (size_t)e + 2 * d + h] + reorder_index(code, NQ - 1, a, b);
 #pragma unroll
           for (int c = 0; c < 4; ++c) qp[c] = p[c * T];
         } else if ((VOL & 16) != 0 && kind == 3) {
@@ -728,11 +736,20 @@ bool direct_fused_ok(const d4est_hip_plan* plan) {
 // with the plan's zeroth-order term (plan_set_lhs_coefficient) in its volume stage.
 // dh / bk: the direct tables and the bucket they belong to -- the plan's own (uniform conforming plans) or one clean-element bucket of
 // the hybrid operator (hybrid = true: offsets by element id from the side table / d_qs_by_elem, streamed metric).
+// sub: this launch works on another element list than the tables' own (the hybrid operator's ghost-adjacent list of a bucket); the tables
+// themselves are not touched.
+struct DirectSubList {
+  const int* list;   // device list of element ids (never null)
+  int n;
+  bool ghost2;       // kind-2 sides with DIRECT_KCF_GHOST read the ghost buffer beside the trace array (VOL & 32; hanging- / mixed-aware tables only)
+};
 static void launch_direct_core(d4est_hip_plan* plan, DirectHost* dh, const Bucket& bk, bool hybrid, const int* d_qs_by_elem, const double* u,
                                const double* ghost_trace, double* Au, const DirectFuse* cf, const double* robin_c, const double* robin_r,
-                               int vol_term) {
+                               int vol_term, const DirectSubList* sub = nullptr) {
   if (!plan->has_face_geometry) D4EST_HIP_ABORT("apply flux: plan_set_mortar_geometry was not called");
-  const int n = dh->d_list ? dh->n_list : plan->n_elements;
+  if (sub && (!sub->list || dh->mw)) D4EST_HIP_ABORT("direct face kernel: a sub-list launch needs a list and a one-wavefront bucket");
+  const int* const elem_list = sub ? sub->list : dh->d_list;
+  const int n = sub ? sub->n : (dh->d_list ? dh->n_list : plan->n_elements);
   if (n == 0) return;
   if (plan->ghost_trace_doubles > 0 && !ghost_trace) D4EST_HIP_ABORT("apply flux: plan has ghost sides but no ghost trace buffer was given");
   static const bool no_remap = std::getenv("D4EST_HIP_NO_XCD_REMAP") != nullptr;
@@ -785,11 +802,16 @@ static void launch_direct_core(d4est_hip_plan* plan, DirectHost* dh, const Bucke
   if (dh->hang) {
     if (!(vmode == 1 || vmode == 9)) D4EST_HIP_ABORT("direct face kernel: the hanging-aware form exists for the plain whole operator only (vmode %d)", vmode);
     vmode |= 16;
+    if (sub && sub->ghost2) {   // ghost-adjacent list of a sharded plan: ghost_trace is the trace array here, the ghost buffer rides in the volume arguments
+      if (!plan->d_ghost_trace) D4EST_HIP_ABORT("direct face kernel: the ghost-aware form needs the plan's ghost trace buffer");
+      vol.ghost_buf = plan->d_ghost_trace;
+      vmode |= 32;
+    }
   }
 #define D4EST_HIP_DIRECT_GO(N_, NQ_, FUSE_, VOL_)                                                                             \
   hipLaunchKernelGGL((faces_direct_kernel<N_, NQ_, true, FUSE_, VOL_>), dim3(n_wg), dim3(64 * kDirectWPB), 0,     \
                      plan->stream, u, ghost_trace, Au, dh->d_sides, dh->d_ghost_off, dh->d_ops, plan->d_face_geom, plan->d_bndry,            \
-                     robin_c, robin_r, n, dh->ns0, dh->ns_stride, chunk, cfv, vol, dh->d_list)
+                     robin_c, robin_r, n, dh->ns0, dh->ns_stride, chunk, cfv, vol, elem_list)
 #define X(N_, NQ_)                                                                 \
   if (!done && dh->N == N_ && dh->NQ == NQ_) {                                     \
     if constexpr (N_ == NQ_) {                                                     \
@@ -797,6 +819,8 @@ static void launch_direct_core(d4est_hip_plan* plan, DirectHost* dh, const Bucke
       if (vmode == 9) { if (cf) D4EST_HIP_DIRECT_GO(N_, NQ_, true, 9); else D4EST_HIP_DIRECT_GO(N_, NQ_, false, 9); done = true; } \
       if (vmode == 17) { if (cf) D4EST_HIP_DIRECT_GO(N_, NQ_, true, 17); else D4EST_HIP_DIRECT_GO(N_, NQ_, false, 17); done = true; } \
       if (vmode == 25) { if (cf) D4EST_HIP_DIRECT_GO(N_, NQ_, true, 25); else D4EST_HIP_DIRECT_GO(N_, NQ_, false, 25); done = true; } \
+      if (vmode == 49) { if (cf) D4EST_HIP_DIRECT_GO(N_, NQ_, true, 49); else D4EST_HIP_DIRECT_GO(N_, NQ_, false, 49); done = true; } \
+      if (vmode == 57) { if (cf) D4EST_HIP_DIRECT_GO(N_, NQ_, true, 57); else D4EST_HIP_DIRECT_GO(N_, NQ_, false, 57); done = true; } \
       if (vmode == 2) { if (cf) D4EST_HIP_DIRECT_GO(N_, NQ_, true, 2); else D4EST_HIP_DIRECT_GO(N_, NQ_, false, 2); done = true; } \
       if (vmode == 5) { if (cf) D4EST_HIP_DIRECT_GO(N_, NQ_, true, 5); else D4EST_HIP_DIRECT_GO(N_, NQ_, false, 5); done = true; } \
       if (vmode == 6) { if (cf) D4EST_HIP_DIRECT_GO(N_, NQ_, true, 6); else D4EST_HIP_DIRECT_GO(N_, NQ_, false, 6); done = true; } \
@@ -841,8 +865,12 @@ void launch_direct_faces(d4est_hip_plan* plan, const double* u, const double* gh
 // ---------------------------------------------------------------------------
 struct HybridHost {
   std::vector<DirectHost*> dh;        // per plan bucket (nullptr: no clean elements there)
-  std::vector<int*> d_clean;          // per plan bucket: its clean elements
-  std::vector<int> n_clean;
+  std::vector<int*> d_clean;          // per plan bucket: its clean elements (sharded plans: those WITHOUT a ghost side -- they need no
+  std::vector<int> n_clean;           // exchanged data and run while the trace blocks travel)
+  std::vector<int*> d_clean_g;        // per plan bucket: its clean elements with a ghost side (launched after the exchange has completed)
+  std::vector<int> n_clean_g;
+  int n_clean_ghost = 0;
+  bool sharded = false;               // the plan has ghost sides: every element whose trace block is sent is in the ring
   DirectSide* d_sides = nullptr;      // shared by the buckets' tables (the element's nodal offset in sides[6 e].pad)
   DirectGhostOff* d_ghost_off = nullptr;
   int* d_qs_by_elem = nullptr;
@@ -851,7 +879,7 @@ struct HybridHost {
   std::vector<int> h_dirty, h_ring;   // host copies (the face set-up splits them by kernel family, hybrid_host_lists)
   int *d_ns_dirty = nullptr, *d_qs_dirty = nullptr;   // bucket-ordered lists of the dirty elements (the volume kernels' view)
   std::vector<int> dirty_off, dirty_cnt;
-  char path[96] = "";
+  char path[160] = "";
   double* d_u2 = nullptr;             // second iterate vector of the fused Chebyshev update (hybrid_second_vector)
   bool hang = false;                  // hanging-aware form: the clean kernels read record traces and export small sides' blocks
   // the clean buckets' launches are short, latency-structured kernels (one wavefront / workgroup per element, a few hundred elements
@@ -869,6 +897,7 @@ void hybrid_destroy(d4est_hip_plan* plan) {
   for (DirectHost* d : hh->dh)
     if (d) { (void)hipFree(d->d_ops); delete d; }
   for (int* p : hh->d_clean) (void)hipFree(p);
+  for (int* p : hh->d_clean_g) (void)hipFree(p);
   for (hipStream_t st : hh->side) (void)hipStreamDestroy(st);
   for (hipEvent_t ev : hh->done) (void)hipEventDestroy(ev);
   if (hh->fork) (void)hipEventDestroy(hh->fork);
@@ -896,10 +925,13 @@ void hybrid_setup(d4est_hip_plan* plan, const std::vector<char>& clean, const st
   HybridHost* hh = new HybridHost;
   const size_t nb = plan->buckets.size();
   hh->dh.assign(nb, nullptr); hh->d_clean.assign(nb, nullptr); hh->n_clean.assign(nb, 0);
+  hh->d_clean_g.assign(nb, nullptr); hh->n_clean_g.assign(nb, 0);
   hh->dirty_off.assign(nb, 0); hh->dirty_cnt.assign(nb, 0);
+  hh->sharded = plan->n_ghost > 0;
   // side table of every element (only clean elements are worked on, everybody is read as a neighbour)
   std::vector<DirectSide> sd(6 * (size_t)ne);
   std::vector<DirectGhostOff> goff(6 * (size_t)ne, 0);
+  std::vector<char> ghost_adj(ne, 0);   // clean elements with a ghost-aware side
   for (int e = 0; e < ne; ++e)
     for (int f = 0; f < 6; ++f) {
       const size_t s = 6 * (size_t)e + f;
@@ -913,9 +945,17 @@ void hybrid_setup(d4est_hip_plan* plan, const std::vector<char>& clean, const st
       d.pad = (f == 0) ? plan->nodal_stride[e] : 0;
       if (ov && clean[e] && (*ov)[s].kind >= 0) {
         const HybridSideOverride& o = (*ov)[s];
-        d.kcf = o.kind | ((plan->side_reorder[s] & 7) << 2);
-        if (o.kind == 2) { d.nbr_ns = o.export_off; d.geom = o.geom; goff[s] = o.goff; }
-        hh->hang = true;
+        if (o.kind == 4) {
+          // ghost-aware side: kind 2 to the kernel.  An element list without trace-array sides gets the ghost buffer as ghost_qtrace (the
+          // plain instances, which ignore the flag); beside such sides the flag selects it (VOL & 32)
+          d.kcf = 2 | ((plan->side_reorder[s] & 7) << 2) | DIRECT_KCF_GHOST;
+          d.nbr_ns = -1; d.geom = o.geom; goff[s] = o.goff;
+          ghost_adj[e] = 1;
+        } else {
+          d.kcf = o.kind | ((plan->side_reorder[s] & 7) << 2);
+          if (o.kind == 2) { d.nbr_ns = o.export_off; d.geom = o.geom; goff[s] = o.goff; }
+          hh->hang = true;
+        }
       }
       sd[s] = d;
     }
@@ -926,16 +966,17 @@ void hybrid_setup(d4est_hip_plan* plan, const std::vector<char>& clean, const st
   std::vector<int> dirty, ns_dirty, qs_dirty;
   for (size_t b = 0; b < nb; ++b) {
     const Bucket& bk = plan->buckets[b];
-    std::vector<int> cl;
+    std::vector<int> cl, cl_g;   // (cl_g: beside a ghost side -- a launch of their own, after the exchange)
     hh->dirty_off[b] = (int)ns_dirty.size();
     for (int i = 0; i < bk.n_elem; ++i) {
       const int e = plan->elem_ids[bk.elem_offset + i];
-      if (clean[e]) cl.push_back(e);
+      if (clean[e]) (ghost_adj[e] ? cl_g : cl).push_back(e);
       else { ns_dirty.push_back(plan->nodal_stride[e]); qs_dirty.push_back(plan->quad_stride[e]); }
     }
     hh->dirty_cnt[b] = (int)ns_dirty.size() - hh->dirty_off[b];
-    if (cl.empty()) continue;
+    if (cl.empty() && cl_g.empty()) continue;
     std::sort(cl.begin(), cl.end());   // element (Morton) order: neighbours' u close in the caches
+    std::sort(cl_g.begin(), cl_g.end());
     DirectHost* dh = new DirectHost;
     const int N = bk.N, NQ = bk.NQ;
     dh->N = N; dh->NQ = NQ; dh->ns0 = 0; dh->ns_stride = -1;
@@ -963,6 +1004,11 @@ void hybrid_setup(d4est_hip_plan* plan, const std::vector<char>& clean, const st
     dh->d_ghost_off = hh->d_ghost_off;
     hh->d_clean[b] = hy_upload(cl);
     hh->n_clean[b] = (int)cl.size();
+    if (!cl_g.empty()) {
+      hh->d_clean_g[b] = hy_upload(cl_g);
+      hh->n_clean_g[b] = (int)cl_g.size();
+      hh->n_clean_ghost += (int)cl_g.size();
+    }
     dh->d_list = hh->d_clean[b];
     dh->n_list = hh->n_clean[b];
     // every element of the plan, in order, at affine offsets (a locally refined mesh of one degree in the hanging-aware form): the
@@ -979,7 +1025,7 @@ void hybrid_setup(d4est_hip_plan* plan, const std::vector<char>& clean, const st
       }
     }
     hh->dh[b] = dh;
-    hh->n_clean_total += (int)cl.size();
+    hh->n_clean_total += (int)cl.size() + (int)cl_g.size();
   }
   // dirty elements in element order, and the ring: the dirty elements plus every local element across one of their sides (whose traces the
   // dirty flux reads; hanging neighbours through side_nbr4)
@@ -996,6 +1042,18 @@ void hybrid_setup(d4est_hip_plan* plan, const std::vector<char>& clean, const st
           if (plan->side_nbr4[4 * s + k] >= 0) in_ring[plan->side_nbr4[4 * s + k]] = 1;
     }
   }
+  // sharded plan: ... and every element whose trace block is sent to a peer, clean or not -- the exchange packs the blocks of the sides
+  // with a ghost neighbour straight from the trace array, and a clean kernel never writes a block that another kernel of the same apply
+  // (or the pack) reads: the ring's trace kernel does, before exchange `begin`
+  if (hh->sharded)
+    for (int e = 0; e < ne; ++e)
+      for (int f = 0; f < 6 && !in_ring[e]; ++f) {
+        const size_t s = 6 * (size_t)e + f;
+        if (plan->side_nbr[s] <= -2) in_ring[e] = 1;
+        if (!plan->side_nbr4.empty())
+          for (int k = 0; k < 4; ++k)
+            if (plan->side_nbr4[4 * s + k] <= -2) in_ring[e] = 1;
+      }
   std::vector<int> ring;
   for (int e = 0; e < ne; ++e)
     if (in_ring[e]) ring.push_back(e);
@@ -1006,7 +1064,11 @@ void hybrid_setup(d4est_hip_plan* plan, const std::vector<char>& clean, const st
   hh->d_qs_dirty = hy_upload(qs_dirty);
   char tag[32] = "";
   if (hh->hang) std::snprintf(tag, sizeof(tag), " (%s)", form);
-  std::snprintf(hh->path, sizeof(hh->path), "hybrid%s: direct+volume on %d clean elements, two-phase on %d", tag, hh->n_clean_total, hh->n_dirty);
+  if (hh->sharded)
+    std::snprintf(hh->path, sizeof(hh->path), "hybrid%s: direct+volume on %d clean elements (%d beside ghost sides), two-phase on %d", tag,
+                  hh->n_clean_total, hh->n_clean_ghost, hh->n_dirty);
+  else
+    std::snprintf(hh->path, sizeof(hh->path), "hybrid%s: direct+volume on %d clean elements, two-phase on %d", tag, hh->n_clean_total, hh->n_dirty);
   plan->hybrid = hh;
 }
 
@@ -1050,7 +1112,9 @@ void hybrid_lists(const d4est_hip_plan* plan, const int** dirty, int* n_dirty, c
 }
 
 // the clean elements: one whole-operator launch per degree bucket (u in, A u out), every bucket on its own stream between a fork event
-// on the plan's stream (phase 0, before the dirty path is queued there) and the join (phase 1, after it)
+// on the plan's stream (phase 0, before the dirty path is queued there) and the join (phase 1, after it).  On a sharded plan (and with one
+// bucket) there is no fork: phase 0 does nothing and phase 1 launches the buckets one after another on the plan's stream -- on a shard only
+// their elements WITHOUT a ghost side (launch_hybrid_clean_ghost has the others)
 void launch_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, const double* robin_c, const double* robin_r,
                          int phase, const DirectFuse* cf) {
   HybridHost* hh = hybrid_of(plan);
@@ -1058,7 +1122,8 @@ void launch_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* gh
   static const bool serial = std::getenv("D4EST_HIP_HYBRID_SERIAL") != nullptr;
   int n_launch = 0;
   for (DirectHost* d : hh->dh) n_launch += d != nullptr;
-  const bool forked = !serial && n_launch > 1;
+  // (a shard: never forked -- everything stays on the plan's stream, in the order apply_operator sets around the exchange hooks)
+  const bool forked = !serial && !hh->sharded && n_launch > 1;
   if (!forked) {   // one bucket: nothing to overlap
     if (phase == 0) return;
     for (size_t b = 0; b < hh->dh.size(); ++b)
@@ -1092,6 +1157,22 @@ void launch_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* gh
   }
   for (int i = 0; i < n_launch; ++i) HIP_CHECK(hipStreamWaitEvent(main, hh->done[i], 0));
 }
+// sharded plans: the clean elements WITH a ghost side, bucket by bucket on the plan's stream -- the caller has the exchange completed there
+// (hook phase 1 returned), so the ghost trace buffer is whole; no side streams: the launches are short and nothing is left to overlap.
+// Each launch reads the plan's ghost buffer for its ghost sides and, where the plan has hanging- or mixed-aware sides, the trace array for those.
+void launch_hybrid_clean_ghost(d4est_hip_plan* plan, const double* u, double* Au, const double* robin_c, const double* robin_r, const DirectFuse* cf) {
+  HybridHost* hh = hybrid_of(plan);
+  if (hh->n_clean_ghost == 0) return;
+  if (cf && !hybrid_can_fuse_update(plan)) D4EST_HIP_ABORT("hybrid operator: a fused update was requested on a plan that cannot carry it");
+  if (!plan->d_ghost_trace) D4EST_HIP_ABORT("hybrid operator: the plan's ghost trace buffer does not exist");
+  for (size_t b = 0; b < hh->dh.size(); ++b) {
+    DirectHost* dh = hh->dh[b];
+    if (!dh || hh->n_clean_g[b] == 0) continue;
+    const DirectSubList sub{hh->d_clean_g[b], hh->n_clean_g[b], dh->hang};
+    launch_direct_core(plan, dh, plan->buckets[b], true, hh->d_qs_by_elem, u, dh->hang ? plan->d_trace : plan->d_ghost_trace, Au, cf, robin_c, robin_r, 1, &sub);
+  }
+}
+bool hybrid_sharded(const d4est_hip_plan* plan) { return hybrid_of(plan)->sharded; }
 // the dirty elements' volume term
 void launch_hybrid_dirty_stiffness(d4est_hip_plan* plan, const double* u, double* Au) {
   HybridHost* hh = hybrid_of(plan);

@@ -2637,13 +2637,23 @@ void faces_setup(d4est_hip_plan* plan) {
   }
   // ---- the hybrid operator (d4est_hip_direct.hip): on mixed-degree / locally refined plans the CLEAN elements -- deg_quad = deg with a
   // one-kernel instance, all six sides conforming against a local element of the same degree or the boundary -- take the trace-free
-  // whole-operator kernels of their degree bucket; one rank, plans whose two-phase kernels have list forms
+  // whole-operator kernels of their degree bucket; plans whose two-phase kernels have list forms.  One rank -- or, tuning value 2, a shard:
+  // ghost-aware form below (a uniform-degree shard, which has the direct tables too, then takes this path instead)
   hybrid_destroy(plan);
   (void)hipFree(fh.d_ring_small); (void)hipFree(fh.d_ring_big); (void)hipFree(fh.d_dirty_small); (void)hipFree(fh.d_dirty_big);
   fh.d_ring_small = fh.d_ring_big = fh.d_dirty_small = fh.d_dirty_big = nullptr;
   fh.n_ring_small = fh.n_ring_big = fh.n_dirty_small = fh.n_dirty_big = 0;
   fh.hy_ring = fh.hy_dirty = fh.hy_dirty_any = nullptr;
-  if (!plan->direct && ne > 0 && plan->n_ghost == 0 && plan->tuning[D4EST_HIP_TUNE_HYBRID] != 0 && plan->tuning[D4EST_HIP_TUNE_GHOST_ALIAS] <= 0 &&
+  // ghost-aware form (tuning value 2 on a plan with ghost sides; D4EST_HIP_HYBRID_NO_GHOST=1 switches it off): a conforming side against a
+  // ghost element of the same degree does not make a (one-wavefront, N <= 8) element dirty -- the kernel reads the (+) block from the ghost
+  // trace buffer (kind 4 -> kind 2 + DIRECT_KCF_GHOST).  The sender's trace kernel wrote that block at the mortar nodes in the sender's own
+  // face order; the READING kernel re-orients it with the side's side_reorder code, as the two-phase flux kernel and the uniform direct
+  // kernel do with a ghost block.  Race freedom by
+  // construction: such an element is in the ring, so the trace kernel -- never a clean kernel -- writes the block the exchange packs, and
+  // its own launch is queued on the plan's stream only after exchange phase 1 has returned there (apply_operator).  A ghost neighbour of
+  // another degree, a hanging face cut by the shard boundary and every ghost side of a p >= 8 element leave the element dirty.
+  const bool hy_ghost = plan->n_ghost > 0 && plan->tuning[D4EST_HIP_TUNE_HYBRID] == 2 && !std::getenv("D4EST_HIP_HYBRID_NO_GHOST");
+  if ((hy_ghost || (!plan->direct && plan->n_ghost == 0)) && ne > 0 && plan->tuning[D4EST_HIP_TUNE_HYBRID] != 0 && plan->tuning[D4EST_HIP_TUNE_GHOST_ALIAS] <= 0 &&
       plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0 && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 1 && (hp ? (fh.hp_split || (fh.hp_max_N <= 16 && fh.hp_max_NQ <= 16)) : (fast || (fh.max_N <= 16 && fh.max_NQ <= 16)))) {
     std::vector<char> bucket_ok(plan->buckets.size(), 0), clean(ne, 0);
     std::vector<int> bucket_of(ne, -1);
@@ -2659,7 +2669,7 @@ void faces_setup(d4est_hip_plan* plan) {
     // neighbour itself stays dirty: ITS side sees a mortar above its own degree).  D4EST_HIP_HYBRID_NO_MIXED=1 switches it off
     const bool mixed_aware = (!hp || fh.hp_split) && !std::getenv("D4EST_HIP_HYBRID_NO_MIXED") && plan->local_trace_doubles < (1LL << 31);
     std::vector<HybridSideOverride> ov;
-    if (hang_aware || mixed_aware) ov.assign(ns, HybridSideOverride{-1, 0, 0, 0});
+    if (hang_aware || mixed_aware || hy_ghost) ov.assign(ns, HybridSideOverride{-1, 0, 0, 0});
     bool any_ov = false, any_hang_ov = false, any_mixed_ov = false;
     for (size_t b = 0; b < plan->buckets.size(); ++b) {
       const Bucket& bk = plan->buckets[b];
@@ -2674,6 +2684,11 @@ void faces_setup(d4est_hip_plan* plan) {
         const size_t s_ = 6 * (size_t)e + f;
         if (hp && plan->side_hang[s_] != 0) {
           if (!hang_aware || plan->buckets[bucket_of[e]].N > 8) { ok = false; break; }
+          // (a hanging face cut by the shard boundary: the two-phase kernels)
+          bool cut = plan->side_nbr[s_] <= -2;
+          if (plan->side_hang[s_] == 1 && !plan->side_nbr4.empty())
+            for (int k = 0; k < 4; ++k) cut = cut || plan->side_nbr4[4 * s_ + k] <= -2;
+          if (cut) { ok = false; break; }
           const SideDesc& d = sd[s_];
           if (d.kind == 3) { ov[s_] = HybridSideOverride{3, 0, 0, 0}; continue; }   // (the element is on the record kernels' list)
           if (d.kind == 1 && plan->side_hang[s_] == 2 && d.NQ == plan->buckets[bucket_of[e]].NQ && deg_p_of[s_] == plan->deg[e]) {
@@ -2685,7 +2700,18 @@ void faces_setup(d4est_hip_plan* plan) {
         }
         const int nbr = plan->side_nbr[s_];
         if (nbr == -1) continue;                                   // domain boundary
-        if (nbr < 0) { ok = false; break; }                        // (ghost: not on one-rank plans)
+        if (nbr < 0) {                                             // ghost: the ghost-aware form, or dirty
+          const int g = -(nbr + 2);
+          const Bucket& bk = plan->buckets[bucket_of[e]];
+          if (hy_ghost && bk.N <= 8 && g < plan->n_ghost && plan->ghost_deg[g] == plan->deg[e] && plan->ghost_deg_quad[g] == plan->deg_quad[e] &&
+              deg_mq_of[s_] == plan->deg_quad[e] && sd[s_].kind == 2 && sd[s_].NQ == bk.NQ && plan->ghost_trace_offset[s_] >= 0 &&
+              plan->ghost_trace_offset[s_] + 4LL * bk.NQ * bk.NQ <= plan->ghost_trace_doubles) {
+            ov[s_] = HybridSideOverride{4, plan->ghost_trace_offset[s_], -1, plan->side_mortar_stride[s_]};
+            continue;
+          }
+          ok = false;
+          break;
+        }
         const size_t sp = 6 * (size_t)nbr + plan->side_nbr_face[s_];
         if (mixed_aware && plan->buckets[bucket_of[e]].N <= 8 && plan->deg[nbr] < plan->deg[e] && plan->deg_quad[nbr] <= plan->deg_quad[e] &&
             deg_mq_of[s_] == plan->deg_quad[e] && !(hp && plan->side_hang[sp] != 0) && sd[s_].kind == 1 && sd[s_].NQ == plan->buckets[bucket_of[e]].NQ) {
@@ -2699,11 +2725,12 @@ void faces_setup(d4est_hip_plan* plan) {
       }
       clean[e] = ok;
       n_clean += ok;
-      if (ok && (hang_aware || mixed_aware))
+      if (ok && (hang_aware || mixed_aware || hy_ghost))
         for (int f = 0; f < 6; ++f) {
           const size_t s_ = 6 * (size_t)e + f;
           if (ov[s_].kind < 0) continue;
           any_ov = true;
+          if (ov[s_].kind == 4) continue;   // (ghost-aware: not part of the form's label)
           if (hp && plan->side_hang[s_] != 0) any_hang_ov = true;
           else any_mixed_ov = true;
         }
@@ -3583,6 +3610,11 @@ void launch_flux_direct(d4est_hip_plan* plan, const double* u, const double* gho
 void launch_flux_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, int phase, const DirectFuse* cf) {
   FaceHost& fh = g_face_host[plan];
   launch_hybrid_clean(plan, u, ghost_trace, Au, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, phase, cf);
+}
+
+void launch_flux_hybrid_clean_ghost(d4est_hip_plan* plan, const double* u, double* Au, const DirectFuse* cf) {
+  FaceHost& fh = g_face_host[plan];
+  launch_hybrid_clean_ghost(plan, u, Au, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, cf);
 }
 
 void launch_flux_units(d4est_hip_plan* plan, const double* trace, const double* ghost_trace, double* Au, const ChebyFuse* cf) {

@@ -317,6 +317,8 @@ bool hybrid_pair_built(int N, int NQ);
 // hanging-aware form (locally refined plans under the hp split): what a clean element's hanging side is to the direct kernel --
 // kind 3: served by the mortar-record kernels (no contribution); kind 2: a small side, (+) block at goff in the plan's trace array, own
 // block exported to export_off, combined factors at geom; kind < 0: an ordinary side
+// ghost-aware form (sharded plans, tuning key 14 = 2): kind 4 = a conforming side against a ghost element of the same degree -- (+) block at
+// goff in the plan's GHOST trace buffer, no export, combined factors at geom
 struct HybridSideOverride { int kind; long long goff; int export_off; int geom; };
 void hybrid_setup(d4est_hip_plan* plan, const std::vector<char>& clean, const std::vector<const double*>& C, const std::vector<const double*>& CD,
                   const std::vector<const double*>& E, const std::vector<HybridSideOverride>* ov = nullptr, const char* form = "hanging-aware");
@@ -336,7 +338,12 @@ bool faces_have_units(d4est_hip_plan* plan);
 bool faces_hp(d4est_hip_plan* plan);         // the plan has hanging faces (mortar records)
 bool faces_hp_split(d4est_hip_plan* plan);   // the plan has record kernels beside the conforming ones (launch_traces / launch_flux take `parts`)   // hp split with the unit record kernels (the form that can carry the update)
 void launch_hybrid_dirty_stiffness(d4est_hip_plan* plan, const double* u, double* Au);
-void launch_flux_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, int phase, const DirectFuse* cf = nullptr);   // (faces.hip: supplies the Robin arrays; phase 0 fork + launches, 1 join)
+// sharded plans: the plan has ghost sides (launch order around the exchange hooks: apply_operator); the clean elements beside a ghost side
+// run after exchange phase 1, on the plan's stream (launch_flux_hybrid_clean_ghost: faces.hip, supplies the Robin arrays)
+bool hybrid_sharded(const d4est_hip_plan* plan);
+void launch_hybrid_clean_ghost(d4est_hip_plan* plan, const double* u, double* Au, const double* robin_c, const double* robin_r, const DirectFuse* cf);
+void launch_flux_hybrid_clean_ghost(d4est_hip_plan* plan, const double* u, double* Au, const DirectFuse* cf = nullptr);
+void launch_flux_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, int phase, const DirectFuse* cf = nullptr);   // (faces.hip: supplies the Robin arrays; phase 0 fork + launches, 1 join; one bucket or a sharded plan: no fork, phase 1 launches on the plan's stream)
 void faces_destroy(d4est_hip_plan* plan);
 // the estimator's view of the plan's mortars (d4est_hip_faces.hip builds it from its side descriptors / mortar records): one entry per
 // conforming or boundary side, per sub-mortar of a big hanging side, per small hanging side; the entries of an element consecutive

@@ -163,6 +163,47 @@ void apply_operator(d4est_hip_plan* plan, const double* u, double* Au, const Che
     hybrid_lists(plan, &dirty, &n_dirty, &ring, &n_ring);
     if (cf && !hybrid_can_fuse_update(plan))
       D4EST_HIP_ABORT("apply_operator: the hybrid operator of this plan does not carry a fused update");
+    if (hybrid_sharded(plan)) {
+      // a shard (tuning key 14 = 2, ghost-aware form).  Every launch on the plan's stream -- the clean buckets too, one after another: no
+      // side streams and no cross-stream events on this path (launch_hybrid_clean does not fork on a sharded plan) -- around the exchange hooks:
+      //   1. the trace kernels of the ring (the dirty elements, their neighbours, and every element whose block is sent) and the record traces
+      //   2. exchange phase 0 (pack + post)
+      //   3. the clean elements WITHOUT a ghost side, and the dirty elements' volume term: they overlap the exchange
+      //   4. exchange phase 1 (complete + unpack into the ghost trace buffer)
+      //   5. the clean elements WITH a ghost side (they read that buffer)
+      //   6. the dirty flux kernels, then the record flux kernel
+      // No clean kernel writes a trace block that the pack or another kernel of this apply reads (the ring's trace kernel does), and the
+      // ghost buffer is read only by launches queued after phase 1 has returned.  Every element's A u -- and a fused update -- comes from
+      // exactly one launch, as on one rank.
+      const bool hp = faces_hp(plan), hang = hybrid_hanging(plan), rec = hp && faces_hp_split(plan);
+      DirectFuse df;
+      ChebyFuse cu;
+      const DirectFuse* dfp = nullptr;
+      if (cf) {
+        if (!cf->u_out || cf->u_out == u) D4EST_HIP_ABORT("apply_operator: the hybrid operator needs a second vector for the fused update");
+        df.rhs = cf->rhs; df.p = cf->p; df.u_out = cf->u_out; df.r = cf->r; df.alpha = cf->alpha; df.beta = cf->beta;
+        df.skip_Au_store = cf->skip_Au_store ? 1 : 0;
+        dfp = &df;
+        cu = *cf;
+        cu.u = const_cast<double*>(u);
+      }
+      const double* gt = hang ? plan->d_trace : plan->d_ghost_trace;   // (hanging- / mixed-aware sides read the trace array)
+      if (rec) launch_traces(plan, u, plan->d_trace, false, ring, n_ring, n_ring > 0 ? 3 : 2);
+      else if (n_ring > 0) launch_traces(plan, u, plan->d_trace, false, ring, n_ring);
+      if (has_ghost) plan->exchange_fn(plan->comm_ctx, 0, plan->d_trace, plan->d_ghost_trace);
+      launch_flux_hybrid_clean(plan, u, gt, Au, 1, dfp);   // (a shard: bucket after bucket on the plan's stream, no side streams, no events)
+      if (n_dirty > 0) launch_hybrid_dirty_stiffness(plan, u, Au);
+      if (has_ghost) plan->exchange_fn(plan->comm_ctx, 1, plan->d_trace, plan->d_ghost_trace);
+      launch_flux_hybrid_clean_ghost(plan, u, Au, dfp);
+      if (cf && hp) {   // (hybrid_can_fuse_update: hanging-aware form, no dirty elements, unit record kernels)
+        launch_flux_units(plan, plan->d_trace, plan->d_ghost_trace, Au, &cu);
+        return;
+      }
+      if (n_dirty > 0) launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, cf ? &cu : nullptr, dirty, n_dirty, (rec && hang) ? 1 : 3);
+      if (rec && hang) launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, nullptr, dirty, n_dirty, 2);
+      if (!cf && lhs_term) add_lhs_mass_term(plan, u, Au);
+      return;
+    }
     if (cf && !faces_hp(plan)) {
       // conforming mixed-degree plan: the update in every clean bucket's kernel and in the flux kernels of the dirty list (each element's
       // A u is final in exactly one of them); all of them read u and write the new iterate to cf->u_out
