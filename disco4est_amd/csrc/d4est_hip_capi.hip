@@ -882,7 +882,7 @@ void d4est_hip_apply_aij(d4est_hip_plan_t* plan, const double* u_dev, const doub
   if (d4est_hip::direct_active(plan)) {   // the caller's ghost traces, the local ones from u inside the kernel
     const bool whole = d4est_hip::direct_fused_ok(plan);
     if (!whole) d4est_hip::launch_stiffness(plan, u_dev, Au_dev);
-    d4est_hip::launch_flux_direct(plan, u_dev, ghost_trace_dev, Au_dev, nullptr, whole ? 1 : 0);
+    d4est_hip::launch_direct_faces(plan, u_dev, ghost_trace_dev, Au_dev, nullptr, whole ? 1 : 0);
     return;
   }
   d4est_hip::launch_stiffness(plan, u_dev, Au_dev);

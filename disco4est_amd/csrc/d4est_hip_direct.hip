@@ -846,10 +846,11 @@ static void launch_direct_core(d4est_hip_plan* plan, DirectHost* dh, const Bucke
   HIP_CHECK(hipGetLastError());
 }
 
-void launch_direct_faces(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, const DirectFuse* cf,
-                         const double* robin_c, const double* robin_r, int vol_term) {
+void launch_direct_faces(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, const DirectFuse* cf, int vol_term) {
   DirectHost* dh = host_of(plan);
   if (!dh) D4EST_HIP_ABORT("direct face kernel: the plan has no direct tables");
+  const double *robin_c, *robin_r;
+  faces_robin(plan, &robin_c, &robin_r);
   launch_direct_core(plan, dh, plan->buckets[0], false, nullptr, u, ghost_trace, Au, cf, robin_c, robin_r, vol_term);
 }
 
@@ -1115,9 +1116,10 @@ void hybrid_lists(const d4est_hip_plan* plan, const int** dirty, int* n_dirty, c
 // on the plan's stream (phase 0, before the dirty path is queued there) and the join (phase 1, after it).  On a sharded plan (and with one
 // bucket) there is no fork: phase 0 does nothing and phase 1 launches the buckets one after another on the plan's stream -- on a shard only
 // their elements WITHOUT a ghost side (launch_hybrid_clean_ghost has the others)
-void launch_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, const double* robin_c, const double* robin_r,
-                         int phase, const DirectFuse* cf) {
+void launch_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, int phase, const DirectFuse* cf) {
   HybridHost* hh = hybrid_of(plan);
+  const double *robin_c, *robin_r;
+  faces_robin(plan, &robin_c, &robin_r);
   if (cf && !hybrid_can_fuse_update(plan)) D4EST_HIP_ABORT("hybrid operator: a fused update was requested on a plan that cannot carry it");
   static const bool serial = std::getenv("D4EST_HIP_HYBRID_SERIAL") != nullptr;
   int n_launch = 0;
@@ -1141,8 +1143,7 @@ void launch_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* gh
         hh->side.push_back(st); hh->done.push_back(ev);
       }
     }
-    if (plan->d_lhs_coeff == nullptr) {}   // (the zeroth-order term is added after the join, on the plan's stream)
-    HIP_CHECK(hipEventRecord(hh->fork, main));
+    HIP_CHECK(hipEventRecord(hh->fork, main));   // (the zeroth-order term is added after the join, on the plan's stream)
     int i = 0;
     for (size_t b = 0; b < hh->dh.size(); ++b) {
       if (!hh->dh[b]) continue;
@@ -1160,9 +1161,11 @@ void launch_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* gh
 // sharded plans: the clean elements WITH a ghost side, bucket by bucket on the plan's stream -- the caller has the exchange completed there
 // (hook phase 1 returned), so the ghost trace buffer is whole; no side streams: the launches are short and nothing is left to overlap.
 // Each launch reads the plan's ghost buffer for its ghost sides and, where the plan has hanging- or mixed-aware sides, the trace array for those.
-void launch_hybrid_clean_ghost(d4est_hip_plan* plan, const double* u, double* Au, const double* robin_c, const double* robin_r, const DirectFuse* cf) {
+void launch_hybrid_clean_ghost(d4est_hip_plan* plan, const double* u, double* Au, const DirectFuse* cf) {
   HybridHost* hh = hybrid_of(plan);
   if (hh->n_clean_ghost == 0) return;
+  const double *robin_c, *robin_r;
+  faces_robin(plan, &robin_c, &robin_r);
   if (cf && !hybrid_can_fuse_update(plan)) D4EST_HIP_ABORT("hybrid operator: a fused update was requested on a plan that cannot carry it");
   if (!plan->d_ghost_trace) D4EST_HIP_ABORT("hybrid operator: the plan's ghost trace buffer does not exist");
   for (size_t b = 0; b < hh->dh.size(); ++b) {

@@ -3329,292 +3329,310 @@ static void debug_occupancy_once() {
 
 static size_t generic_lds_bytes(const d4est_hip_plan* plan) { return (size_t)plan->max_face_lds_doubles * sizeof(double); }
 
+// ---- which kernels serve a plan.  The one place that decides it: launch_traces, launch_flux, flux_can_fuse_update and the list rules
+// below all read it.  Computed per call from the set-up's findings and the tuning keys as they are NOW (keys are flipped on live plans).
+enum class FaceFamily {
+  HpSplitFast,    // hanging faces, hp split: conforming sides through the p <= 7 kernels, hanging sides through the record kernels
+  HpSplitTiled,   // ... conforming sides through the tiled 16 x 16 kernels (or both conforming families on lists)
+  HpTiled,        // hanging faces, no split: the tiled record kernels for every side
+  HpGeneric,      // hanging faces, any degree
+  ConfFastMfma,   // conforming, every N, NQ <= 8: trace_mfma_kernel + flux_wave_kernel
+  ConfFastWave,   // ... tuning key 3 = 1: trace_wave_kernel + flux_wave_kernel
+  FamilySplit,    // conforming mixed-degree with degrees above 7: p <= 7 kernels and tiled kernels, each on its list
+  Tiled,          // conforming, N, NQ <= 16: trace_mfma16_kernel + flux_mfma16_kernel
+  Generic,
+};
+static FaceFamily face_family(const d4est_hip_plan* plan, const FaceHost& fh) {
+  const int fast_key = plan->tuning[D4EST_HIP_TUNE_FLUX_FAST];
+  if (fh.hp) {
+    if (fh.hp_split) return fh.hp_split_fast ? FaceFamily::HpSplitFast : FaceFamily::HpSplitTiled;   // (decided at set-up)
+    return (fast_key != 0 && fh.hp_max_N <= 16 && fh.hp_max_NQ <= 16) ? FaceFamily::HpTiled : FaceFamily::HpGeneric;
+  }
+  if (fast_key == 0) return FaceFamily::Generic;
+  if (plan->face_fast) return fast_key != 1 ? FaceFamily::ConfFastMfma : FaceFamily::ConfFastWave;
+  if (fh.family_split) return FaceFamily::FamilySplit;   // (set-up takes it only where the tiled kernels apply: N, NQ <= 16)
+  return (fh.max_N <= 16 && fh.max_NQ <= 16) ? FaceFamily::Tiled : FaceFamily::Generic;
+}
+static bool family_hp_split(FaceFamily f) { return f == FaceFamily::HpSplitFast || f == FaceFamily::HpSplitTiled; }
+// the trace kernels with an element-list form (the other families compute every element's traces) ...
+static bool trace_takes_list(FaceFamily f) { return f != FaceFamily::HpGeneric && f != FaceFamily::ConfFastWave && f != FaceFamily::Generic; }
+// ... and the flux kernels with one (the hybrid operator is not set up on the others)
+static bool flux_takes_list(FaceFamily f) { return f != FaceFamily::HpGeneric && f != FaceFamily::Generic; }
+// the flux kernels whose epilogue can carry the Chebyshev update
+static bool flux_family_fuses(FaceFamily f) {
+  return f == FaceFamily::ConfFastMfma || f == FaceFamily::ConfFastWave || f == FaceFamily::FamilySplit || f == FaceFamily::Tiled;
+}
+
+// the two conforming families' lists of one launch: the whole plan's, or the hybrid operator's ring (traces) / dirty (flux) list split
+// the same way; a list without a split of its own goes through the tiled kernels whole
+struct FamilyLists {
+  bool on;
+  const int *small, *big;
+  int n_small, n_big;
+};
+static FamilyLists family_lists(const FaceHost& fh, const int* elist, bool ring) {
+  const int* hy = ring ? fh.hy_ring : fh.hy_dirty;
+  const int* hy_small = ring ? fh.d_ring_small : fh.d_dirty_small;
+  FamilyLists l;
+  l.on = fh.family_split && (!elist || (elist == hy && hy_small));
+  l.small = elist ? hy_small : fh.d_fam_small;
+  l.big = elist ? (ring ? fh.d_ring_big : fh.d_dirty_big) : fh.d_fam_big;
+  l.n_small = elist ? (ring ? fh.n_ring_small : fh.n_dirty_small) : fh.n_fam_small;
+  l.n_big = elist ? (ring ? fh.n_ring_big : fh.n_dirty_big) : fh.n_fam_big;
+  return l;
+}
+
+// ---- one launcher per kernel: it owns the grid, the block, the LDS size and the plan's arguments; the callers pass what varies
+static int face_cus(const d4est_hip_plan* plan) { return plan->n_cus > 0 ? plan->n_cus : 256; }
+// persistent grid: `resident` workgroups at most, every one with the same number of rounds over the n elements
+static int persistent_grid(int n, int resident) {
+  const int rounds = (n + resident - 1) / resident;
+  return (n + rounds - 1) / rounds;
+}
+// XCD-aware element order (chunk = n / 8 elements per XCD) on whole-plan launches only: 0 with an element list, the family lists included
+static int xcd_chunk(const int* elist, int n, int grid) {
+  static const bool no_remap = std::getenv("D4EST_HIP_NO_XCD_REMAP") != nullptr;
+  return (!elist && n % 8 == 0 && grid % 8 == 0 && !no_remap) ? n / 8 : 0;
+}
+template <typename K>
+static void allow_lds(K kern, size_t lds) {
+  if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+}
+static const double* robin_c_of(const FaceHost& fh) { return fh.robin ? fh.d_robin_c : nullptr; }
+static const double* robin_r_of(const FaceHost& fh) { return fh.robin ? fh.d_robin_r : nullptr; }
+
+void faces_robin(d4est_hip_plan* plan, const double** robin_c, const double** robin_r) {
+  const FaceHost& fh = g_face_host[plan];
+  *robin_c = robin_c_of(fh);
+  *robin_r = robin_r_of(fh);
+}
+
+// p <= 7, 3 waves.  Inherited: 8 resident workgroups per CU (47 VGPRs, 11.5 KB LDS) where the flux kernels take face_wg_per_cu()
+static void run_trace_mfma(d4est_hip_plan* plan, const double* u, double* trace, int n, const int* elist, int wg_per_cu = 8) {
+  hipLaunchKernelGGL(trace_mfma_kernel, dim3(persistent_grid(n, wg_per_cu * face_cus(plan))), dim3(192), 0, plan->stream, u, trace,
+                     (const SideDesc*)plan->d_side_desc, (const ElemDesc*)plan->d_elem_desc, plan->d_face_ops, n, elist);
+}
+// p <= 7, 6 waves, no list form
+static void run_trace_wave(d4est_hip_plan* plan, const FaceHost& fh, const double* u, double* trace, int n, int wg_per_cu) {
+  hipLaunchKernelGGL(trace_wave_kernel, dim3(persistent_grid(n, wg_per_cu * face_cus(plan))), dim3(384), 0, plan->stream, u, trace,
+                     (const SideDesc*)plan->d_side_desc, (const ElemDesc*)plan->d_elem_desc, plan->d_face_ops, n, fh.uni);
+}
+// p = 8 .. 15: tiled MFMA trace kernel (descriptors with unpadded N x N derivative matrices).  Only local elements are copied to LDS:
+// the copy of u is sized by the largest LOCAL degree (cached at set-up: no per-launch walk over the elements)
+static void run_trace_mfma16(d4est_hip_plan* plan, const FaceHost& fh, const double* u, double* trace, int n, const int* elist) {
+  const size_t lds = (size_t)(fh.max_local_N * 272 + 3 * 2 * 16 * 34) * sizeof(double);
+  allow_lds(trace_mfma16_kernel, lds);
+  const int per_cu = (int)std::min<size_t>(8, (160 * 1024) / lds);
+  hipLaunchKernelGGL(trace_mfma16_kernel, dim3(std::min(n, per_cu * face_cus(plan))), dim3(192), lds, plan->stream, u, trace,
+                     (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, n, fh.max_local_N, elist);
+}
+// both conforming families on their lists; false: this launch's list has no split of its own (the caller sends it through the tiled kernel)
+static bool run_trace_families(d4est_hip_plan* plan, const FaceHost& fh, const double* u, double* trace, const int* elist) {
+  const FamilyLists l = family_lists(fh, elist, /*ring=*/true);
+  if (!l.on) return false;
+  if (l.n_small > 0) run_trace_mfma(plan, u, trace, l.n_small, l.small);
+  if (l.n_big > 0) run_trace_mfma16(plan, fh, u, trace, l.n_big, l.big);
+  return true;
+}
+// the hanging sides of the hp split, one unit (side with live records) per workgroup round
+static void run_trace_unit(d4est_hip_plan* plan, const FaceHost& fh, const double* u, double* trace) {
+  const int uj = fh.hp_max_N | 1, uk = (fh.hp_max_N * uj) | 1;
+  const size_t lds = (size_t)(((fh.hp_max_N * uk + 1) & ~1) + 4 * 16 * 34) * sizeof(double);
+  const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
+  hipLaunchKernelGGL(trace_unit_kernel, dim3(std::min(fh.n_units, per_cu * face_cus(plan))), dim3(256), lds, plan->stream, u, trace, fh.d_rec,
+                     fh.d_units, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, fh.n_units, fh.hp_max_N);
+}
+// tiled record kernel, 4 workgroups per CU.  hang_only = 1: the hanging sides of the listed elements (hp split), 0: every side
+static void run_trace_hp_mfma16(d4est_hip_plan* plan, const FaceHost& fh, const double* u, double* trace, int n, const int* elist, int hang_only) {
+  const size_t lds = (size_t)(fh.hp_max_N * 272 + 3 * 2 * 16 * 34) * sizeof(double);
+  allow_lds(trace_hp_mfma16_kernel, lds);
+  hipLaunchKernelGGL(trace_hp_mfma16_kernel, dim3(std::min(n, 4 * face_cus(plan))), dim3(192), lds, plan->stream, u, trace, fh.d_rec,
+                     fh.d_side_first, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, n, fh.hp_max_N, elist, hang_only);
+}
+static void run_trace_hp_generic(d4est_hip_plan* plan, const FaceHost& fh, const double* u, double* trace, int n) {
+  const size_t lds = fh.hp_lds_doubles * sizeof(double);
+  allow_lds(trace_hp_kernel, lds);
+  hipLaunchKernelGGL(trace_hp_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, u, trace, fh.d_rec, fh.d_elem_first,
+                     (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, n, fh.hp_fld_stride);
+}
+static void run_trace_generic(d4est_hip_plan* plan, const FaceHost& fh, const double* u, double* trace, int n) {
+  const size_t lds = generic_lds_bytes(plan);
+  allow_lds(trace_generic_kernel, lds);
+  hipLaunchKernelGGL(trace_generic_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, u, trace, (const SideDesc*)plan->d_side_desc,
+                     (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, n, fh.fld_stride);
+}
+
 void launch_traces(d4est_hip_plan* plan, const double* u, double* trace, bool ghost, const int* elist, int n_list, int parts) {
   FaceHost& fh = g_face_host[plan];
   if (ghost) {
     if (fh.hp) D4EST_HIP_ABORT("compute_ghost_traces: plans with hanging faces take their ghost traces from the trace exchange (d4est_hip_plan_*_sub offsets), not from whole ghost elements");
     if (fh.n_ghost_sides == 0) return;
     const size_t lds = generic_lds_bytes(plan);
-    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ghost_trace_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    allow_lds(ghost_trace_kernel, lds);
     hipLaunchKernelGGL(ghost_trace_kernel, dim3(std::min(fh.n_ghost_sides, 16384)), dim3(256), lds, plan->stream, u, trace,
                        fh.d_ghost_sides, plan->d_face_ops, fh.n_ghost_sides, fh.fld_stride);
     HIP_CHECK(hipGetLastError());
     return;
   }
-  // elist: only these elements' traces are needed (the tiled MFMA kernels take the list; the other families compute every element)
-  const bool listed = elist && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0 &&
-                      ((fh.hp && (fh.hp_split || (fh.hp_max_N <= 16 && fh.hp_max_NQ <= 16))) ||
-                       (!fh.hp && ((plan->face_fast && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 1) || (!plan->face_fast && fh.max_N <= 16 && fh.max_NQ <= 16))));
-  if (!listed) elist = nullptr;
-  const int n = listed ? n_list : plan->n_elements;
-  // the two conforming families' lists of this launch: the whole plan's, or the hybrid operator's ring list split the same way
-  const bool fam = fh.family_split && (!elist || (elist == fh.hy_ring && fh.d_ring_small));
-  const int* fam_small = elist ? fh.d_ring_small : fh.d_fam_small;
-  const int* fam_big = elist ? fh.d_ring_big : fh.d_fam_big;
-  const int n_fam_small = elist ? fh.n_ring_small : fh.n_fam_small, n_fam_big = elist ? fh.n_ring_big : fh.n_fam_big;
-  if (parts != 3 && !(fh.hp && fh.hp_split)) D4EST_HIP_ABORT("launch_traces: parts = %d on a plan without the hp split", parts);
-  if (n == 0 && !(fh.hp && fh.hp_split && (parts & 2))) return;
-  if (fh.hp && fh.hp_split) {
-    // hp split: every conforming side from the fast conforming kernel, then the hanging sides of the elements that have one (the
-    // record kernel overwrites the blocks the first kernel filled for those sides)
-    const int cus = plan->n_cus > 0 ? plan->n_cus : 256;
-    if (n > 0 && (parts & 1) && fh.hp_split_fast) {
-      const int resident = 8 * cus;
-      const int rounds = (n + resident - 1) / resident;
-      const int grid = (n + rounds - 1) / rounds;
-      hipLaunchKernelGGL(trace_mfma_kernel, dim3(grid), dim3(192), 0, plan->stream, u, trace, (const SideDesc*)plan->d_side_desc,
-                         (const ElemDesc*)plan->d_elem_desc, plan->d_face_ops, n, elist);
-    } else if (n > 0 && (parts & 1)) {
-      // degrees above 7: the conforming sides through the tiled kernels -- both conforming families on their lists where the plan has them
-      const int max_local_n = fh.max_local_N;
-      const size_t lds = (size_t)(max_local_n * 272 + 3 * 2 * 16 * 34) * sizeof(double);
-      if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trace_mfma16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      const int per_cu = (int)std::min<size_t>(8, (160 * 1024) / lds);
-      if (fam) {
-        if (n_fam_small > 0) {
-          const int ns_ = n_fam_small, resident = 8 * cus, rounds = (ns_ + resident - 1) / resident, grid = (ns_ + rounds - 1) / rounds;
-          hipLaunchKernelGGL(trace_mfma_kernel, dim3(grid), dim3(192), 0, plan->stream, u, trace, (const SideDesc*)plan->d_side_desc,
-                             (const ElemDesc*)plan->d_elem_desc, plan->d_face_ops, ns_, fam_small);
-        }
-        if (n_fam_big > 0)
-          hipLaunchKernelGGL(trace_mfma16_kernel, dim3(std::min(n_fam_big, per_cu * cus)), dim3(192), lds, plan->stream, u, trace,
-                             (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, n_fam_big, max_local_n,
-                             fam_big);
-      } else {
-        hipLaunchKernelGGL(trace_mfma16_kernel, dim3(std::min(n, per_cu * cus)), dim3(192), lds, plan->stream, u, trace,
-                           (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, n, max_local_n, elist);
+  const FaceFamily fam = face_family(plan, fh);
+  // elist: only these elements' traces are needed (inherited: an hp-split plan whose key 3 was set to 0 afterwards computes every element)
+  if (!(trace_takes_list(fam) && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0)) elist = nullptr;
+  const int n = elist ? n_list : plan->n_elements;
+  if (parts != 3 && !family_hp_split(fam)) D4EST_HIP_ABORT("launch_traces: parts = %d on a plan without the hp split", parts);
+  if (n == 0 && !(family_hp_split(fam) && (parts & 2))) return;
+  switch (fam) {
+    case FaceFamily::HpSplitFast:
+    case FaceFamily::HpSplitTiled:
+      // every conforming side from the conforming kernels, then the hanging sides of the elements that have one (the record kernel
+      // overwrites the blocks the first kernel filled for those sides)
+      if (n > 0 && (parts & 1)) {
+        if (fam == FaceFamily::HpSplitFast) run_trace_mfma(plan, u, trace, n, elist);
+        else if (!run_trace_families(plan, fh, u, trace, elist)) run_trace_mfma16(plan, fh, u, trace, n, elist);
       }
+      if ((parts & 2) && fh.n_units > 0) run_trace_unit(plan, fh, u, trace);
+      else if ((parts & 2) && fh.n_hang_elems > 0) run_trace_hp_mfma16(plan, fh, u, trace, fh.n_hang_elems, fh.d_hang_elems, 1);
+      break;
+    case FaceFamily::HpTiled: run_trace_hp_mfma16(plan, fh, u, trace, n, elist, 0); break;
+    case FaceFamily::HpGeneric: run_trace_hp_generic(plan, fh, u, trace, n); break;
+    case FaceFamily::ConfFastMfma:
+    case FaceFamily::ConfFastWave: {
+      // resident workgroups per CU: 8 of the 3-wave MFMA kernel, 4 of the 6-wave kernel.  Inherited: D4EST_HIP_FACE_WG_PER_CU overrides
+      // the trace grid on this family only
+      static const bool wg_override = std::getenv("D4EST_HIP_FACE_WG_PER_CU") != nullptr;   // environment knobs are read once
+      const bool mfma = fam == FaceFamily::ConfFastMfma;
+      const int wg_per_cu = wg_override ? face_wg_per_cu() : (mfma ? 8 : 4);
+      debug_occupancy_once();
+      if (mfma) run_trace_mfma(plan, u, trace, n, elist, wg_per_cu);
+      else run_trace_wave(plan, fh, u, trace, n, wg_per_cu);
+      break;
     }
-    if (fh.n_units > 0 && (parts & 2)) {
-      const int uj = fh.hp_max_N | 1, uk = (fh.hp_max_N * uj) | 1;
-      const size_t lds = (size_t)(((fh.hp_max_N * uk + 1) & ~1) + 4 * 16 * 34) * sizeof(double);
-      const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
-      hipLaunchKernelGGL(trace_unit_kernel, dim3(std::min(fh.n_units, per_cu * cus)), dim3(256), lds, plan->stream, u, trace, fh.d_rec, fh.d_units,
-                         (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, fh.n_units, fh.hp_max_N);
-    } else if (fh.n_hang_elems > 0 && (parts & 2)) {
-      const size_t lds = (size_t)(fh.hp_max_N * 272 + 3 * 2 * 16 * 34) * sizeof(double);
-      if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trace_hp_mfma16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(trace_hp_mfma16_kernel, dim3(std::min(fh.n_hang_elems, 4 * cus)), dim3(192), lds, plan->stream, u, trace, fh.d_rec,
-                         fh.d_side_first, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, fh.n_hang_elems, fh.hp_max_N,
-                         (const int*)fh.d_hang_elems, 1);
-    }
-  } else if (fh.hp && fh.hp_max_N <= 16 && fh.hp_max_NQ <= 16 && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0) {
-    const size_t lds = (size_t)(fh.hp_max_N * 272 + 3 * 2 * 16 * 34) * sizeof(double);
-    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trace_hp_mfma16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(trace_hp_mfma16_kernel, dim3(std::min(n, 4 * (plan->n_cus > 0 ? plan->n_cus : 256))), dim3(192), lds, plan->stream, u, trace,
-                       fh.d_rec, fh.d_side_first, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, n, fh.hp_max_N, elist, 0);
-  } else if (fh.hp) {
-    const size_t lds = fh.hp_lds_doubles * sizeof(double);
-    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trace_hp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(trace_hp_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, u, trace, fh.d_rec, fh.d_elem_first,
-                       (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, n, fh.hp_fld_stride);
-  } else if (plan->face_fast && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0) {
-    const int cus = plan->n_cus > 0 ? plan->n_cus : 256;
-    const bool mfma = plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 1;
-    // resident workgroups per CU: 8 of the 3-wave MFMA kernel (47 VGPRs, 11.5 KB LDS), 4 of the 6-wave kernel
-    static const bool wg_override = std::getenv("D4EST_HIP_FACE_WG_PER_CU") != nullptr;   // environment knobs are read once
-    const int resident = (wg_override ? face_wg_per_cu() : (mfma ? 8 : 4)) * cus;
-    const int rounds = (n + resident - 1) / resident;
-    const int grid = (n + rounds - 1) / rounds;
-    debug_occupancy_once();
-    if (mfma)   // auto: MFMA form of the two interpolation passes
-      hipLaunchKernelGGL(trace_mfma_kernel, dim3(grid), dim3(192), 0, plan->stream, u, trace, (const SideDesc*)plan->d_side_desc,
-                         (const ElemDesc*)plan->d_elem_desc, plan->d_face_ops, n, elist);
-    else
-      hipLaunchKernelGGL(trace_wave_kernel, dim3(grid), dim3(384), 0, plan->stream, u, trace, (const SideDesc*)plan->d_side_desc,
-                         (const ElemDesc*)plan->d_elem_desc, plan->d_face_ops, n, fh.uni);
-  } else if (fam && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0) {
-    const int cus = plan->n_cus > 0 ? plan->n_cus : 256;
-    if (n_fam_small > 0) {
-      const int ns_ = n_fam_small, resident = 8 * cus, rounds = (ns_ + resident - 1) / resident, grid = (ns_ + rounds - 1) / rounds;
-      hipLaunchKernelGGL(trace_mfma_kernel, dim3(grid), dim3(192), 0, plan->stream, u, trace, (const SideDesc*)plan->d_side_desc,
-                         (const ElemDesc*)plan->d_elem_desc, plan->d_face_ops, ns_, fam_small);
-    }
-    const int max_local_n = fh.max_local_N;
-    const size_t lds = (size_t)(max_local_n * 272 + 3 * 2 * 16 * 34) * sizeof(double);
-    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trace_mfma16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int per_cu = (int)std::min<size_t>(8, (160 * 1024) / lds);
-    if (n_fam_big > 0)
-      hipLaunchKernelGGL(trace_mfma16_kernel, dim3(std::min(n_fam_big, per_cu * cus)), dim3(192), lds, plan->stream, u, trace,
-                         (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, n_fam_big, max_local_n,
-                         fam_big);
-  } else if (fh.max_N <= 16 && fh.max_NQ <= 16 && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0) {
-    // p = 8 .. 15: tiled MFMA trace kernel (descriptors with unpadded N x N derivative matrices)
-    // only local elements are copied to LDS: size the copy of u by the largest LOCAL degree
-    const int max_local_n = fh.max_local_N;   // (cached at set-up: no per-launch walk over the elements)
-    const size_t lds = (size_t)(max_local_n * 272 + 3 * 2 * 16 * 34) * sizeof(double);
-    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trace_mfma16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int per_cu = (int)std::min<size_t>(8, (160 * 1024) / lds);
-    hipLaunchKernelGGL(trace_mfma16_kernel, dim3(std::min(n, per_cu * (plan->n_cus > 0 ? plan->n_cus : 256))), dim3(192), lds, plan->stream, u, trace,
-                       (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, n, max_local_n, elist);
-  } else {
-    const size_t lds = generic_lds_bytes(plan);
-    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trace_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(trace_generic_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, u, trace,
-                       (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, n,
-                       fh.fld_stride);
+    case FaceFamily::FamilySplit:
+      if (run_trace_families(plan, fh, u, trace, elist)) break;
+      if (fh.max_N > 16 || fh.max_NQ > 16) D4EST_HIP_ABORT("launch_traces: family split on a plan beyond the tiled kernels (N, NQ <= 16)");
+      [[fallthrough]];
+    case FaceFamily::Tiled: run_trace_mfma16(plan, fh, u, trace, n, elist); break;
+    case FaceFamily::Generic: run_trace_generic(plan, fh, u, trace, n); break;
   }
   HIP_CHECK(hipGetLastError());
 }
 
 // true when launch_flux runs the kernel that can carry the Chebyshev update in its epilogue
-bool flux_can_fuse_update(d4est_hip_plan* plan) {
-  FaceHost& fh = g_face_host[plan];
-  return plan->has_faces && plan->n_elements > 0 && !fh.hp && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0 && !hybrid_active(plan) &&
-         (plan->face_fast || (fh.max_N <= 16 && fh.max_NQ <= 16));
+static bool flux_can_fuse(d4est_hip_plan* plan, FaceFamily fam) {
+  return plan->has_faces && plan->n_elements > 0 && !hybrid_active(plan) && flux_family_fuses(fam);
+}
+bool flux_can_fuse_update(d4est_hip_plan* plan) { return flux_can_fuse(plan, face_family(plan, g_face_host[plan])); }
+
+// p <= 7, 6 waves, persistent grid of face_wg_per_cu() workgroups per CU.  INPLACE = false: a Schwarz subdomain plan (see the kernel)
+template <bool FUSE, bool INPLACE>
+static void run_flux_wave(d4est_hip_plan* plan, const FaceHost& fh, const double* trace, const double* ghost_trace, double* Au, int n,
+                          const int* elist, const ChebyFuse& cf) {
+  const int grid = persistent_grid(n, face_wg_per_cu() * face_cus(plan));
+  hipLaunchKernelGGL((flux_wave_kernel<FUSE, INPLACE>), dim3(grid), dim3(384), 0, plan->stream, trace, ghost_trace, Au,
+                     (const SideDesc*)plan->d_side_desc, (const ElemDesc*)plan->d_elem_desc, plan->d_face_ops, plan->d_face_geom, plan->d_bndry,
+                     robin_c_of(fh), robin_r_of(fh), n, xcd_chunk(elist, n, grid), cf, elist);
+}
+static void flux_wave(d4est_hip_plan* plan, const FaceHost& fh, const double* trace, const double* ghost_trace, double* Au, int n,
+                      const int* elist, const ChebyFuse* cf, bool inplace = true) {
+  if (cf && !inplace) run_flux_wave<true, false>(plan, fh, trace, ghost_trace, Au, n, elist, *cf);
+  else if (cf) run_flux_wave<true, true>(plan, fh, trace, ghost_trace, Au, n, elist, *cf);
+  else if (!inplace) run_flux_wave<false, false>(plan, fh, trace, ghost_trace, Au, n, elist, ChebyFuse{});
+  else run_flux_wave<false, true>(plan, fh, trace, ghost_trace, Au, n, elist, ChebyFuse{});
+}
+// p = 8 .. 15, 8 workgroups per CU.  Inherited: the XCD-aware order only where the conforming tiled family calls it (xcd), not under the hp split
+template <bool FUSE>
+static void run_flux_mfma16(d4est_hip_plan* plan, const FaceHost& fh, const double* trace, const double* ghost_trace, double* Au, int n,
+                            const int* elist, const ChebyFuse& cf, bool xcd) {
+  const int grid = std::min(n, 8 * face_cus(plan));
+  hipLaunchKernelGGL(flux_mfma16_kernel<FUSE>, dim3(grid), dim3(192), 0, plan->stream, trace, ghost_trace, Au, (const SideDesc*)plan->d_side_desc,
+                     (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, plan->d_face_geom, plan->d_bndry, robin_c_of(fh), robin_r_of(fh), n,
+                     xcd ? xcd_chunk(elist, n, grid) : 0, cf, elist);
+}
+static void flux_mfma16(d4est_hip_plan* plan, const FaceHost& fh, const double* trace, const double* ghost_trace, double* Au, int n,
+                        const int* elist, const ChebyFuse* cf, bool xcd) {
+  if (cf) run_flux_mfma16<true>(plan, fh, trace, ghost_trace, Au, n, elist, *cf, xcd);
+  else run_flux_mfma16<false>(plan, fh, trace, ghost_trace, Au, n, elist, ChebyFuse{}, xcd);
+}
+// (cf: the Chebyshev update in both families' epilogues -- every element is on exactly one of the two lists)
+static bool flux_families(d4est_hip_plan* plan, const FaceHost& fh, const double* trace, const double* ghost_trace, double* Au,
+                          const int* elist, const ChebyFuse* cf) {
+  const FamilyLists l = family_lists(fh, elist, /*ring=*/false);
+  if (!l.on) return false;
+  if (l.n_small > 0) flux_wave(plan, fh, trace, ghost_trace, Au, l.n_small, l.small, cf);
+  if (l.n_big > 0) flux_mfma16(plan, fh, trace, ghost_trace, Au, l.n_big, l.big, cf, false);
+  return true;
+}
+// the hanging sides of the hp split, by units: 8 workgroups per CU of the N <= 8 instance, 2 of the N <= 16 one
+template <bool FUSE>
+static void run_flux_unit(d4est_hip_plan* plan, const FaceHost& fh, const double* trace, const double* ghost_trace, double* Au, const ChebyFuse& cf) {
+  auto go = [&](auto kern, int per_cu) {
+    hipLaunchKernelGGL(kern, dim3(std::min(fh.n_hang_elems, per_cu * face_cus(plan))), dim3(256), 0, plan->stream, trace, ghost_trace, Au, fh.d_rec,
+                       fh.d_units, fh.d_unit_first, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, plan->d_face_geom,
+                       plan->d_bndry, robin_c_of(fh), robin_r_of(fh), fh.n_hang_elems, cf);
+  };
+  if (fh.hp_max_N <= 8) go(flux_unit_kernel<FUSE, 8>, 8);
+  else go(flux_unit_kernel<FUSE, 16>, 2);
+}
+// tiled record kernel, 8 workgroups per CU; hang_only as in run_trace_hp_mfma16
+static void run_flux_hp_mfma16(d4est_hip_plan* plan, const FaceHost& fh, const double* trace, const double* ghost_trace, double* Au, int n,
+                               const int* elist, int hang_only) {
+  hipLaunchKernelGGL(flux_hp_mfma16_kernel, dim3(std::min(n, 8 * face_cus(plan))), dim3(192), 0, plan->stream, trace, ghost_trace, Au, fh.d_rec,
+                     fh.d_side_first, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, plan->d_face_geom, plan->d_bndry,
+                     robin_c_of(fh), robin_r_of(fh), n, elist, hang_only);
+}
+static void run_flux_hp_generic(d4est_hip_plan* plan, const FaceHost& fh, const double* trace, const double* ghost_trace, double* Au, int n) {
+  const size_t lds = fh.hp_lds_doubles * sizeof(double);
+  allow_lds(flux_hp_kernel, lds);
+  hipLaunchKernelGGL(flux_hp_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, trace, ghost_trace, Au, fh.d_rec, fh.d_elem_first,
+                     (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, plan->d_face_geom, plan->d_bndry, robin_c_of(fh),
+                     robin_r_of(fh), n, fh.hp_fld_stride);
+}
+static void run_flux_generic(d4est_hip_plan* plan, const FaceHost& fh, const double* trace, const double* ghost_trace, double* Au, int n) {
+  const size_t lds = generic_lds_bytes(plan);
+  allow_lds(flux_generic_kernel, lds);
+  hipLaunchKernelGGL(flux_generic_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, trace, ghost_trace, Au,
+                     (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, plan->d_face_geom, plan->d_bndry,
+                     robin_c_of(fh), robin_r_of(fh), n, fh.fld_stride);
 }
 
 void launch_flux(d4est_hip_plan* plan, const double* trace, const double* ghost_trace, double* Au, const ChebyFuse* cf, const int* elist,
                  int n_list, int parts) {
   FaceHost& fh = g_face_host[plan];
-  if (cf && !(flux_can_fuse_update(plan) || (elist && hybrid_active(plan) && !fh.hp))) D4EST_HIP_ABORT("launch_flux: fused update requested on a plan whose flux kernel cannot carry it");
+  const FaceFamily fam = face_family(plan, fh);
+  if (cf && !(flux_can_fuse(plan, fam) || (elist && hybrid_active(plan) && !fh.hp))) D4EST_HIP_ABORT("launch_flux: fused update requested on a plan whose flux kernel cannot carry it");
   if (!plan->has_faces || !plan->has_face_geometry) D4EST_HIP_ABORT("apply flux: plan_set_faces / plan_set_mortar_geometry were not called");
   if (plan->n_elements == 0) return;
   if (fh.n_ghost_sides > 0 && !ghost_trace) D4EST_HIP_ABORT("apply flux: plan has %d ghost sides but no ghost trace buffer was given", fh.n_ghost_sides);
   const int n = elist ? n_list : plan->n_elements;
-  if (parts != 3 && !(fh.hp && fh.hp_split)) D4EST_HIP_ABORT("launch_flux: parts = %d on a plan without the hp split", parts);
-  if (n == 0 && !(fh.hp && fh.hp_split && (parts & 2))) return;
+  if (parts != 3 && !family_hp_split(fam)) D4EST_HIP_ABORT("launch_flux: parts = %d on a plan without the hp split", parts);
+  if (n == 0 && !(family_hp_split(fam) && (parts & 2))) return;
   // (a fused update on a list: the hybrid operator's dirty elements only -- cf->u_out set, see apply_operator)
   if (elist && cf && !(elist == fh.hy_dirty_any && cf->u_out)) D4EST_HIP_ABORT("launch_flux: a fused update cannot ride on this element list");
-  // the two conforming families' lists of this launch: the whole plan's, or the hybrid operator's dirty list split the same way
-  const bool fam = fh.family_split && (!elist || (elist == fh.hy_dirty && fh.d_dirty_small));
-  const int* fam_small = elist ? fh.d_dirty_small : fh.d_fam_small;
-  const int* fam_big = elist ? fh.d_dirty_big : fh.d_fam_big;
-  const int n_fam_small = elist ? fh.n_dirty_small : fh.n_fam_small, n_fam_big = elist ? fh.n_dirty_big : fh.n_fam_big;
-  if (fh.hp && fh.hp_split) {
-    // hp split (see launch_traces): the conforming sides' terms from the fast kernel, then the hanging sides' from the record kernel
-    const int cus = plan->n_cus > 0 ? plan->n_cus : 256;
-    if (n > 0 && (parts & 1) && fh.hp_split_fast) {
-      const int resident = face_wg_per_cu() * cus;
-      const int rounds = (n + resident - 1) / resident;
-      const int grid = (n + rounds - 1) / rounds;
-      static const bool no_remap_s = std::getenv("D4EST_HIP_NO_XCD_REMAP") != nullptr;
-      const int chunk_s = (!elist && n % 8 == 0 && grid % 8 == 0 && !no_remap_s) ? n / 8 : 0;   // XCD-aware element order, as on conforming plans
-      hipLaunchKernelGGL((flux_wave_kernel<false, true>), dim3(grid), dim3(384), 0, plan->stream, trace, ghost_trace, Au,
-                         (const SideDesc*)plan->d_side_desc, (const ElemDesc*)plan->d_elem_desc, plan->d_face_ops, plan->d_face_geom,
-                         plan->d_bndry, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, n, chunk_s, ChebyFuse{}, elist);
-    } else if (n > 0 && (parts & 1)) {
-      if (fam) {
-        if (n_fam_small > 0) {
-          const int ns_ = n_fam_small, resident = face_wg_per_cu() * cus, rounds = (ns_ + resident - 1) / resident, grid = (ns_ + rounds - 1) / rounds;
-          hipLaunchKernelGGL((flux_wave_kernel<false, true>), dim3(grid), dim3(384), 0, plan->stream, trace, ghost_trace, Au,
-                             (const SideDesc*)plan->d_side_desc, (const ElemDesc*)plan->d_elem_desc, plan->d_face_ops, plan->d_face_geom, plan->d_bndry,
-                             fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, ns_, 0, ChebyFuse{}, fam_small);
-        }
-        if (n_fam_big > 0)
-          hipLaunchKernelGGL(flux_mfma16_kernel<false>, dim3(std::min(n_fam_big, 8 * cus)), dim3(192), 0, plan->stream, trace, ghost_trace, Au,
-                             (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, plan->d_face_geom, plan->d_bndry,
-                             fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, n_fam_big, 0, ChebyFuse{}, fam_big);
-      } else {
-        hipLaunchKernelGGL(flux_mfma16_kernel<false>, dim3(std::min(n, 8 * cus)), dim3(192), 0, plan->stream, trace, ghost_trace, Au,
-                           (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, plan->d_face_geom, plan->d_bndry,
-                           fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, n, 0, ChebyFuse{}, elist);
+  if (elist && !flux_takes_list(fam)) D4EST_HIP_ABORT("launch_flux: no list form of this plan's flux kernels (the hybrid operator is not set up for such plans)");
+  switch (fam) {
+    case FaceFamily::HpSplitFast:
+    case FaceFamily::HpSplitTiled:
+      // (see launch_traces) the conforming sides' terms from the conforming kernels, then the hanging sides' from the record kernel
+      if (n > 0 && (parts & 1)) {
+        if (fam == FaceFamily::HpSplitFast) flux_wave(plan, fh, trace, ghost_trace, Au, n, elist, nullptr);
+        else if (!flux_families(plan, fh, trace, ghost_trace, Au, elist, nullptr)) flux_mfma16(plan, fh, trace, ghost_trace, Au, n, elist, nullptr, false);
       }
-    }
-    if (fh.n_units > 0 && (parts & 2))
-    {
-      auto go = [&](auto kern, int per_cu) {
-        hipLaunchKernelGGL(kern, dim3(std::min(fh.n_hang_elems, per_cu * cus)), dim3(256), 0, plan->stream, trace, ghost_trace, Au, fh.d_rec,
-                           fh.d_units, fh.d_unit_first, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, plan->d_face_geom,
-                           plan->d_bndry, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, fh.n_hang_elems, ChebyFuse{});
-      };
-      if (fh.hp_max_N <= 8) go(flux_unit_kernel<false, 8>, 8);
-      else go(flux_unit_kernel<false, 16>, 2);
-    }
-    else if (fh.n_hang_elems > 0 && (parts & 2))
-      hipLaunchKernelGGL(flux_hp_mfma16_kernel, dim3(std::min(fh.n_hang_elems, 8 * cus)), dim3(192), 0, plan->stream, trace, ghost_trace, Au,
-                         fh.d_rec, fh.d_side_first, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, plan->d_face_geom,
-                         plan->d_bndry, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, fh.n_hang_elems,
-                         (const int*)fh.d_hang_elems, 1);
-  } else if (elist && ((fh.hp && !(fh.hp_max_N <= 16 && fh.hp_max_NQ <= 16 && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0)) ||
-                       (!fh.hp && !(plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0 && (plan->face_fast || (fh.max_N <= 16 && fh.max_NQ <= 16)))))) {
-    D4EST_HIP_ABORT("launch_flux: no list form of this plan's flux kernels (the hybrid operator is not set up for such plans)");
-  } else if (fh.hp && fh.hp_max_N <= 16 && fh.hp_max_NQ <= 16 && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0) {
-    hipLaunchKernelGGL(flux_hp_mfma16_kernel, dim3(std::min(n, 8 * (plan->n_cus > 0 ? plan->n_cus : 256))), dim3(192), 0, plan->stream, trace, ghost_trace, Au,
-                       fh.d_rec, fh.d_side_first, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, plan->d_face_geom,
-                       plan->d_bndry, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, n, elist, 0);
-  } else if (fh.hp) {
-    const size_t lds = fh.hp_lds_doubles * sizeof(double);
-    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(flux_hp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(flux_hp_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, trace, ghost_trace, Au, fh.d_rec, fh.d_elem_first,
-                       (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, plan->d_face_geom, plan->d_bndry,
-                       fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, n, fh.hp_fld_stride);
-  } else if (plan->face_fast && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0) {
-    // persistent grid: 3 workgroups per CU are resident (LDS), each loops over elements
-    const int cus = plan->n_cus > 0 ? plan->n_cus : 256;
-    const int resident = face_wg_per_cu() * cus;
-    const int rounds = (n + resident - 1) / resident;
-    const int grid = (n + rounds - 1) / rounds;
-    static const bool no_remap = std::getenv("D4EST_HIP_NO_XCD_REMAP") != nullptr;
-    const int chunk = (!elist && n % 8 == 0 && grid % 8 == 0 && !no_remap) ? n / 8 : 0;
-    const bool subdomain_plan = plan->tuning[D4EST_HIP_TUNE_GHOST_ALIAS] > 0;   // see flux_wave_kernel: INPLACE
-#define D4EST_HIP_LAUNCH_FLUX_WAVE(FUSE_, INPLACE_, CF_)                                                                                 \
-  hipLaunchKernelGGL((flux_wave_kernel<FUSE_, INPLACE_>), dim3(grid), dim3(384), 0, plan->stream, trace, ghost_trace, Au,               \
-                     (const SideDesc*)plan->d_side_desc, (const ElemDesc*)plan->d_elem_desc, plan->d_face_ops, plan->d_face_geom,        \
-                     plan->d_bndry, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, n, chunk, CF_, elist)
-    if (cf && subdomain_plan) D4EST_HIP_LAUNCH_FLUX_WAVE(true, false, *cf);
-    else if (cf) D4EST_HIP_LAUNCH_FLUX_WAVE(true, true, *cf);
-    else if (subdomain_plan) D4EST_HIP_LAUNCH_FLUX_WAVE(false, false, ChebyFuse{});
-    else D4EST_HIP_LAUNCH_FLUX_WAVE(false, true, ChebyFuse{});
-#undef D4EST_HIP_LAUNCH_FLUX_WAVE
-  } else if (fam && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0) {
-    // (cf: the Chebyshev update in both families' epilogues -- every element is on exactly one of the two lists)
-    const int cus = plan->n_cus > 0 ? plan->n_cus : 256;
-    const ChebyFuse cfv = cf ? *cf : ChebyFuse{};
-    if (n_fam_small > 0) {
-      const int ns_ = n_fam_small, resident = face_wg_per_cu() * cus, rounds = (ns_ + resident - 1) / resident, grid = (ns_ + rounds - 1) / rounds;
-      auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(384), 0, plan->stream, trace, ghost_trace, Au,
-                           (const SideDesc*)plan->d_side_desc, (const ElemDesc*)plan->d_elem_desc, plan->d_face_ops, plan->d_face_geom, plan->d_bndry,
-                           fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, ns_, 0, cfv, fam_small);
-      };
-      if (cf) go(flux_wave_kernel<true, true>); else go(flux_wave_kernel<false, true>);
-    }
-    if (n_fam_big > 0) {
-      auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(std::min(n_fam_big, 8 * cus)), dim3(192), 0, plan->stream, trace, ghost_trace, Au,
-                           (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, plan->d_face_geom, plan->d_bndry,
-                           fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, n_fam_big, 0, cfv, fam_big);
-      };
-      if (cf) go(flux_mfma16_kernel<true>); else go(flux_mfma16_kernel<false>);
-    }
-  } else if (fh.max_N <= 16 && fh.max_NQ <= 16 && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0) {
-    const int grid16 = std::min(n, 8 * (plan->n_cus > 0 ? plan->n_cus : 256));
-    static const bool no_remap16 = std::getenv("D4EST_HIP_NO_XCD_REMAP") != nullptr;
-    const int chunk16 = (!elist && n % 8 == 0 && grid16 % 8 == 0 && !no_remap16) ? n / 8 : 0;
-    if (cf)
-      hipLaunchKernelGGL(flux_mfma16_kernel<true>, dim3(grid16), dim3(192), 0, plan->stream, trace,
-                         ghost_trace, Au, (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops,
-                         plan->d_face_geom, plan->d_bndry, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, n, chunk16, *cf, elist);
-    else
-      hipLaunchKernelGGL(flux_mfma16_kernel<false>, dim3(grid16), dim3(192), 0, plan->stream, trace,
-                         ghost_trace, Au, (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops,
-                         plan->d_face_geom, plan->d_bndry, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, n, chunk16,
-                         ChebyFuse{}, elist);
-  } else {
-    const size_t lds = generic_lds_bytes(plan);
-    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(flux_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(flux_generic_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, trace, ghost_trace, Au,
-                       (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops,
-                       plan->d_face_geom, plan->d_bndry, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, n,
-                       fh.fld_stride);
+      if ((parts & 2) && fh.n_units > 0) run_flux_unit<false>(plan, fh, trace, ghost_trace, Au, ChebyFuse{});
+      else if ((parts & 2) && fh.n_hang_elems > 0) run_flux_hp_mfma16(plan, fh, trace, ghost_trace, Au, fh.n_hang_elems, fh.d_hang_elems, 1);
+      break;
+    case FaceFamily::HpTiled: run_flux_hp_mfma16(plan, fh, trace, ghost_trace, Au, n, elist, 0); break;
+    case FaceFamily::HpGeneric: run_flux_hp_generic(plan, fh, trace, ghost_trace, Au, n); break;
+    case FaceFamily::ConfFastMfma:
+    case FaceFamily::ConfFastWave:
+      flux_wave(plan, fh, trace, ghost_trace, Au, n, elist, cf, /*inplace=*/plan->tuning[D4EST_HIP_TUNE_GHOST_ALIAS] <= 0);
+      break;
+    case FaceFamily::FamilySplit:
+      if (flux_families(plan, fh, trace, ghost_trace, Au, elist, cf)) break;
+      if (fh.max_N > 16 || fh.max_NQ > 16) D4EST_HIP_ABORT("launch_flux: family split on a plan beyond the tiled kernels (N, NQ <= 16)");
+      [[fallthrough]];
+    case FaceFamily::Tiled: flux_mfma16(plan, fh, trace, ghost_trace, Au, n, elist, cf, true); break;
+    case FaceFamily::Generic: run_flux_generic(plan, fh, trace, ghost_trace, Au, n); break;
   }
   HIP_CHECK(hipGetLastError());
-}
-
-void launch_flux_direct(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, const DirectFuse* cf, int vol_term) {
-  FaceHost& fh = g_face_host[plan];
-  launch_direct_faces(plan, u, ghost_trace, Au, cf, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, vol_term);
-}
-
-void launch_flux_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, int phase, const DirectFuse* cf) {
-  FaceHost& fh = g_face_host[plan];
-  launch_hybrid_clean(plan, u, ghost_trace, Au, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, phase, cf);
-}
-
-void launch_flux_hybrid_clean_ghost(d4est_hip_plan* plan, const double* u, double* Au, const DirectFuse* cf) {
-  FaceHost& fh = g_face_host[plan];
-  launch_hybrid_clean_ghost(plan, u, Au, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, cf);
 }
 
 void launch_flux_units(d4est_hip_plan* plan, const double* trace, const double* ghost_trace, double* Au, const ChebyFuse* cf) {
@@ -3624,14 +3642,7 @@ void launch_flux_units(d4est_hip_plan* plan, const double* trace, const double* 
   if (fh.n_hang_elems == 0) return;
   if (fh.n_units == 0) D4EST_HIP_ABORT("launch_flux_units: a fused update needs the unit form of the record kernels");
   if (!cf->u_out || cf->u_out == cf->u) D4EST_HIP_ABORT("launch_flux_units: the fused update needs a second vector");
-  const int cus = plan->n_cus > 0 ? plan->n_cus : 256;
-  auto go = [&](auto kern, int per_cu) {
-    hipLaunchKernelGGL(kern, dim3(std::min(fh.n_hang_elems, per_cu * cus)), dim3(256), 0, plan->stream, trace, ghost_trace, Au, fh.d_rec,
-                       fh.d_units, fh.d_unit_first, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, plan->d_face_geom,
-                       plan->d_bndry, fh.robin ? fh.d_robin_c : nullptr, fh.robin ? fh.d_robin_r : nullptr, fh.n_hang_elems, *cf);
-  };
-  if (fh.hp_max_N <= 8) go(flux_unit_kernel<true, 8>, 8);
-  else go(flux_unit_kernel<true, 16>, 2);
+  run_flux_unit<true>(plan, fh, trace, ghost_trace, Au, *cf);
   HIP_CHECK(hipGetLastError());
 }
 bool faces_hp(d4est_hip_plan* plan) { return g_face_host[plan].hp; }
@@ -3715,17 +3726,8 @@ void launch_traces_all(d4est_hip_plan* plan, const double* u, double* trace) {
   FaceHost& fh = g_face_host[plan];
   const int n = plan->n_elements;
   if (n == 0) return;
-  if (fh.hp) {
-    const size_t lds = fh.hp_lds_doubles * sizeof(double);
-    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trace_hp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(trace_hp_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, u, trace, fh.d_rec, fh.d_elem_first,
-                       (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, n, fh.hp_fld_stride);
-  } else {
-    const size_t lds = generic_lds_bytes(plan);
-    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trace_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(trace_generic_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, u, trace,
-                       (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, n, fh.fld_stride);
-  }
+  if (fh.hp) run_trace_hp_generic(plan, fh, u, trace, n);
+  else run_trace_generic(plan, fh, u, trace, n);
   HIP_CHECK(hipGetLastError());
 }
 

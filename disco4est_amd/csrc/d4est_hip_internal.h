@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -267,6 +268,8 @@ void faces_set_robin(d4est_hip_plan* plan, const double* coeff_quad, const doubl
 // on as faces_set_robin does -- the caller fills the boundary sides' entries on the plan's stream; both abort with `who` without sj
 const double* faces_sj(d4est_hip_plan* plan, const char* who);
 void faces_robin_arrays(d4est_hip_plan* plan, const char* who, double** robin_c, double** robin_r);
+// the plan's Robin arrays as the kernels take them: both nullptr while the boundary sides are Dirichlet
+void faces_robin(d4est_hip_plan* plan, const double** robin_c, const double** robin_r);
 void launch_traces(d4est_hip_plan* plan, const double* u, double* trace, bool ghost, const int* elist = nullptr, int n_list = 0, int parts = 3 /* see launch_flux */);
 // Chebyshev update carried by the flux kernel's epilogue (flux_wave_kernel<true>): r = alpha (rhs - Au), p = r + beta p, u += p
 struct ChebyFuse {
@@ -302,11 +305,9 @@ bool direct_fused_ok(const d4est_hip_plan* plan);   // the volume term can ride 
 // the elements with at least one ghost (+) side / with none (device lists; multi-rank plans: boundary traces feed the exchange,
 // the interior elements' operator kernel runs while it is in flight)
 void direct_ghost_split(d4est_hip_plan* plan, const int** bnd_list, int* n_bnd, const int** int_list, int* n_int);
-void launch_direct_faces(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, const DirectFuse* cf,
-                         const double* robin_c, const double* robin_r, int vol_term);
-// the same through the plan's face data (Robin arrays): vol_term = 0: Au += face terms of u; 1: Au = (volume + face terms) of u
-void launch_flux_direct(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, const DirectFuse* cf = nullptr,
-                        int vol_term = 0);
+// vol_term = 0: Au += face terms of u; 1: Au = (volume + face terms) of u; 2: ... with the zeroth-order term in the volume stage
+void launch_direct_faces(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, const DirectFuse* cf = nullptr,
+                         int vol_term = 0);
 // elist / n_list: only these elements' face terms (the hybrid operator's dirty elements); the hanging-side record kernels keep their own list
 // parts (locally refined plans under the hp split): 1 the conforming kernel only, 2 the record kernel only, 3 both
 void launch_flux(d4est_hip_plan* plan, const double* trace, const double* ghost_trace, double* Au, const ChebyFuse* cf = nullptr,
@@ -322,28 +323,26 @@ bool hybrid_pair_built(int N, int NQ);
 struct HybridSideOverride { int kind; long long goff; int export_off; int geom; };
 void hybrid_setup(d4est_hip_plan* plan, const std::vector<char>& clean, const std::vector<const double*>& C, const std::vector<const double*>& CD,
                   const std::vector<const double*>& E, const std::vector<HybridSideOverride>* ov = nullptr, const char* form = "hanging-aware");
-bool hybrid_hanging(const d4est_hip_plan* plan);
-void hybrid_host_lists(const d4est_hip_plan* plan, const std::vector<int>** dirty, const std::vector<int>** ring);   // host copies of hybrid_lists   // the clean kernels read / write the trace array: record traces before, record flux after them
+bool hybrid_hanging(const d4est_hip_plan* plan);   // the clean kernels read / write the trace array: record traces before, record flux after them
+void hybrid_host_lists(const d4est_hip_plan* plan, const std::vector<int>** dirty, const std::vector<int>** ring);   // host copies of hybrid_lists
 void hybrid_destroy(d4est_hip_plan* plan);
 bool hybrid_active(const d4est_hip_plan* plan);
 const char* hybrid_path(const d4est_hip_plan* plan);
 void hybrid_lists(const d4est_hip_plan* plan, const int** dirty, int* n_dirty, const int** ring, int* n_ring);
-void launch_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, const double* robin_c, const double* robin_r,
-                         int phase, const DirectFuse* cf = nullptr);
+// phase 0 fork + launches, 1 join; one bucket or a sharded plan: no fork, phase 1 launches on the plan's stream
+void launch_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, int phase, const DirectFuse* cf = nullptr);
 bool hybrid_can_fuse_update(const d4est_hip_plan* plan);   // the Chebyshev update can ride in the hybrid operator's kernels (hanging-aware form, all clean)
 double* hybrid_second_vector(d4est_hip_plan* plan);
 // the record flux kernel of an hp-split plan alone, optionally with the Chebyshev update of the elements it serves in its epilogue
 void launch_flux_units(d4est_hip_plan* plan, const double* trace, const double* ghost_trace, double* Au, const ChebyFuse* cf);
-bool faces_have_units(d4est_hip_plan* plan);
+bool faces_have_units(d4est_hip_plan* plan);   // hp split with the unit record kernels (the form that can carry the update)
 bool faces_hp(d4est_hip_plan* plan);         // the plan has hanging faces (mortar records)
-bool faces_hp_split(d4est_hip_plan* plan);   // the plan has record kernels beside the conforming ones (launch_traces / launch_flux take `parts`)   // hp split with the unit record kernels (the form that can carry the update)
+bool faces_hp_split(d4est_hip_plan* plan);   // the plan has record kernels beside the conforming ones (launch_traces / launch_flux take `parts`)
 void launch_hybrid_dirty_stiffness(d4est_hip_plan* plan, const double* u, double* Au);
 // sharded plans: the plan has ghost sides (launch order around the exchange hooks: apply_operator); the clean elements beside a ghost side
-// run after exchange phase 1, on the plan's stream (launch_flux_hybrid_clean_ghost: faces.hip, supplies the Robin arrays)
+// run after exchange phase 1, on the plan's stream (launch_hybrid_clean_ghost)
 bool hybrid_sharded(const d4est_hip_plan* plan);
-void launch_hybrid_clean_ghost(d4est_hip_plan* plan, const double* u, double* Au, const double* robin_c, const double* robin_r, const DirectFuse* cf);
-void launch_flux_hybrid_clean_ghost(d4est_hip_plan* plan, const double* u, double* Au, const DirectFuse* cf = nullptr);
-void launch_flux_hybrid_clean(d4est_hip_plan* plan, const double* u, const double* ghost_trace, double* Au, int phase, const DirectFuse* cf = nullptr);   // (faces.hip: supplies the Robin arrays; phase 0 fork + launches, 1 join; one bucket or a sharded plan: no fork, phase 1 launches on the plan's stream)
+void launch_hybrid_clean_ghost(d4est_hip_plan* plan, const double* u, double* Au, const DirectFuse* cf = nullptr);
 void faces_destroy(d4est_hip_plan* plan);
 // the estimator's view of the plan's mortars (d4est_hip_faces.hip builds it from its side descriptors / mortar records): one entry per
 // conforming or boundary side, per sub-mortar of a big hanging side, per small hanging side; the entries of an element consecutive
@@ -408,6 +407,9 @@ void norms_masked_sum(d4est_hip_plan* plan, const double* elem, const int* skip,
 // traces, volume term, (exchange), flux; lhs_term: also the optional zeroth-order term of plan_set_lhs_coefficient
 void apply_operator(d4est_hip_plan* plan, const double* u, double* Au, const ChebyFuse* cf = nullptr, bool lhs_term = true);
 void launch_residual(d4est_hip_plan* plan, int n, const double* rhs, const double* Au, double* r);   // r = rhs - Au
+// grid of the 256-thread grid-stride vector kernels: one thread per entry up to 4096 workgroups
+inline int grid_for(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096)); }
+void launch_add(d4est_hip_plan* plan, int n, const double* x, double* y);   // y += x (d4est_linalg_vec_axpy 1.0), on the plan's stream
 void launch_residual_inplace(d4est_hip_plan* plan, int n, const double* rhs, double* r);              // r = rhs - r
 void launch_residual_inplace_sub(d4est_hip_plan* plan, int n, const double* a, double* r);            // r = r - a
 void ensure_solver_workspace(d4est_hip_plan* plan);

@@ -111,10 +111,6 @@ void lhs_chain_destroy(d4est_hip_plan* plan) {
   plan->lhs_chain = nullptr;
 }
 
-__global__ __launch_bounds__(256) void mg_add_kernel(int n, const double* __restrict__ x, double* __restrict__ y) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) y[i] = __dadd_rn(y[i], x[i]);
-}
-
 void add_lhs_chain_term(d4est_hip_plan* plan, const double* u, double* Au) {
   LhsChain* ch = chain_of(plan);
   if (!ch || plan->local_nodes == 0) return;
@@ -140,9 +136,7 @@ void add_lhs_chain_term(d4est_hip_plan* plan, const double* u, double* Au) {
   for (int i = k - 1; i >= 1; --i) d4est_hip_transfer_restrict(ch->t[i], ch->y[i], ch->y[i - 1]);
   if (!plan->d_work_m) HIP_CHECK(hipMalloc(&plan->d_work_m, (size_t)plan->local_nodes * sizeof(double)));
   d4est_hip_transfer_restrict(ch->t[0], ch->y[0], plan->d_work_m);
-  const int n = plan->local_nodes;
-  hipLaunchKernelGGL(mg_add_kernel, dim3(std::max(1, std::min((n + 255) / 256, 4096))), dim3(256), 0, st, n, plan->d_work_m, Au);
-  HIP_CHECK(hipGetLastError());
+  launch_add(plan, plan->local_nodes, plan->d_work_m, Au);   // (st is the plan's stream)
   for (int i = 0; i < k; ++i) ch->t[i]->stream = saved[i];
   fine->stream = fine_saved;
 }

@@ -121,11 +121,6 @@ struct ChebySmoother : Smoother {
   }
 };
 
-__global__ __launch_bounds__(256) void mg_add_kernel(long long n, const double* __restrict__ x, double* __restrict__ u) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    u[i] = __dadd_rn(u[i], x[i]);   // d4est_linalg_vec_axpy(1.0, x, u)
-}
-
 const char* check_message(int code) {
   switch (code) {
     case 0: return "ok";
@@ -180,9 +175,8 @@ void vcycle(d4est_hip_multigrid* mg, double* u, const double* rhs, double* Au, i
     } else {
       double* rf = mg->rres + mg->off[level + 1];
       d4est_hip_transfer_prolong(mg->transfers[level], mg->lvl(mg->err, level), rf);
-      const long long n = mg->nodes[level + 1];
-      if (n > 0) hipLaunchKernelGGL(mg_add_kernel, dim3((unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096))), dim3(256), 0, st, n, rf, fine_u);
-      HIP_CHECK(hipGetLastError());
+      // u_{level+1} += rres_{level+1}, on the top plan's stream like the rest of the cycle (a level's node count is its plan's: an int)
+      launch_add(mg->plans[top], mg->plans[level + 1]->local_nodes, rf, fine_u);
     }
     mg->smoother->upv_pre_smooth(vcycle_index);                                                  // :1261
     double* r = mg->rres + mg->off[level + 1];

@@ -238,14 +238,10 @@ __global__ __launch_bounds__(256) void nonlin_pointwise_kernel(long long n, doub
   }
 }
 
-__global__ __launch_bounds__(256) void nonlin_add_kernel(int n, const double* __restrict__ x, double* __restrict__ y) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) y[i] = y[i] + x[i];
-}
 __global__ __launch_bounds__(256) void nonlin_negate_kernel(int n, double* __restrict__ x) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) x[i] = -1. * x[i];
 }
 
-static int grid_for(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096)); }
 
 // the (deg + 1, deg_quad + 1) pairs with a compiled kernel: those of D4EST_HIP_FAST_PAIRS and D4EST_HIP_BIG_PAIRS, the coverage of
 // d4est_hip_apply_galerkin_integral's one-kernel path (d4est_hip_volume.hip)
@@ -433,7 +429,7 @@ void d4est_hip_apply_nonlinear_term(d4est_hip_plan_t* plan, const double* u_dev,
   } else {
     if (!plan->d_work_m) HIP_CHECK(hipMalloc(&plan->d_work_m, (size_t)n * sizeof(double)));
     d4est_hip::launch_mass_like(plan, 1, h->d_uq, plan->d_work_m);
-    hipLaunchKernelGGL(d4est_hip::nonlin_add_kernel, dim3(d4est_hip::grid_for(n)), dim3(256), 0, plan->stream, n, plan->d_work_m, out_dev);
+    d4est_hip::launch_add(plan, n, plan->d_work_m, out_dev);
   }
   HIP_CHECK(hipGetLastError());
 }
@@ -519,8 +515,7 @@ int d4est_hip_newton_solve(d4est_hip_plan_t* plan, double* u_dev, const double* 
     d4est_hip_plan_linearise(plan, u_dev);
     if (on_linearise) on_linearise(cb_ctx, u_dev);
     (void)d4est_hip::fcg_solve(plan, h->d_step, h->d_f, h->d_Au, krylov_imax, krylov_atol, krylov_rtol, pc, pc_ctx, nullptr);   // :248-263
-    if (n > 0) hipLaunchKernelGGL(d4est_hip::nonlin_add_kernel, dim3(g), dim3(256), 0, plan->stream, n, h->d_step, u_dev);   // :266, the full step
-    HIP_CHECK(hipGetLastError());
+    d4est_hip::launch_add(plan, n, h->d_step, u_dev);   // :266, the full step
     fnrm = residual_norm();                                                  // :269-305
     ++itc;
     if (fnrm_history_host) fnrm_history_host[itc] = fnrm;

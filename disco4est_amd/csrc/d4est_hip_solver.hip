@@ -121,11 +121,6 @@ void launch_copy_blocks(hipStream_t stream, int n_blocks, const double* src, con
   HIP_CHECK(hipGetLastError());
 }
 
-static int grid_for(int n) {
-  int g = (n + 255) / 256;
-  return std::max(1, std::min(g, 4096));
-}
-
 void ensure_solver_workspace(d4est_hip_plan* plan) {
   const size_t n = std::max<size_t>((size_t)plan->local_nodes, 1);
   if (!plan->d_work_p) HIP_CHECK(hipMalloc(&plan->d_work_p, n * sizeof(double)));
@@ -143,185 +138,196 @@ void launch_dot(d4est_hip_plan* plan, int n, const double* x, const double* y, d
   HIP_CHECK(hipGetLastError());
 }
 
-// Au = A u with the plan's communication hooks (or without ghosts).
-// Fork-join on two streams: the trace kernel (and, through the hooks, the ghost exchange) runs on the plan's side
-// stream while the volume kernel runs on the main stream -- they only share the read-only u -- and the flux kernel
-// joins them.  At config 2 both kernels are latency-structured (~28 us each), so running them side by side hides one.
-void apply_operator(d4est_hip_plan* plan, const double* u, double* Au, const ChebyFuse* cf, bool lhs_term) {
-  if (!plan->has_faces) D4EST_HIP_ABORT("smoother: the plan has no faces (plan_set_faces)");
-  ensure_solver_workspace(plan);
+void launch_add(d4est_hip_plan* plan, int n, const double* x, double* y) {
+  if (n > 0) hipLaunchKernelGGL(add_kernel, dim3(grid_for(n)), dim3(256), 0, plan->stream, n, x, y);
+  HIP_CHECK(hipGetLastError());
+}
+
+// the Chebyshev update as the one-kernel paths take it: they read the neighbours' u, so the new iterate goes to a second vector
+// (`who` names the kernel family in the abort)
+static DirectFuse direct_fuse_of(const ChebyFuse& cf, const double* u, const char* who) {
+  if (!cf.u_out || cf.u_out == u) D4EST_HIP_ABORT("apply_operator: %s needs a second vector for the fused update", who);
+  DirectFuse df;
+  df.rhs = cf.rhs; df.p = cf.p; df.u_out = cf.u_out; df.r = cf.r; df.alpha = cf.alpha; df.beta = cf.beta;
+  df.skip_Au_store = cf.skip_Au_store ? 1 : 0;
+  return df;
+}
+// ... and as the two-phase flux kernels beside them take it: the iterate they read is this apply's u
+static ChebyFuse cheby_fuse_on(const ChebyFuse& cf, const double* u) {
+  ChebyFuse cu = cf;
+  cu.u = const_cast<double*>(u);
+  return cu;
+}
+
+// a shard (tuning key 14 = 2, ghost-aware form).  Every launch on the plan's stream -- the clean buckets too, one after another: no
+// side streams and no cross-stream events on this path (launch_hybrid_clean does not fork on a sharded plan) -- around the exchange hooks:
+//   1. the trace kernels of the ring (the dirty elements, their neighbours, and every element whose block is sent) and the record traces
+//   2. exchange phase 0 (pack + post)
+//   3. the clean elements WITHOUT a ghost side, and the dirty elements' volume term: they overlap the exchange
+//   4. exchange phase 1 (complete + unpack into the ghost trace buffer)
+//   5. the clean elements WITH a ghost side (they read that buffer)
+//   6. the dirty flux kernels, then the record flux kernel
+// No clean kernel writes a trace block that the pack or another kernel of this apply reads (the ring's trace kernel does), and the
+// ghost buffer is read only by launches queued after phase 1 has returned.  Every element's A u -- and a fused update -- comes from
+// exactly one launch, as on one rank.
+static void apply_hybrid_sharded(d4est_hip_plan* plan, const double* u, double* Au, const ChebyFuse* cf, bool lhs_term) {
+  const int *dirty, *ring;
+  int n_dirty, n_ring;
+  hybrid_lists(plan, &dirty, &n_dirty, &ring, &n_ring);
   const bool has_ghost = plan->ghost_trace_doubles > 0;
-  if (has_ghost && !plan->exchange_fn) D4EST_HIP_ABORT("apply_lhs: plan has ghost sides but no exchange callback (plan_set_comm)");
-  // measured: the two cross-stream event waits cost more than the overlap buys (config 2: 119 -> 129 us; 512 elements:
-  // 16 -> 44 us), so the fork is opt-in (tuning value 1) and the default is one stream
-  if (hybrid_active(plan)) {
-    // mixed-degree / locally refined plan (d4est_hip_direct.hip, "the hybrid operator"): the clean elements' A u from the one-kernel path of
-    // their degree bucket, the dirty elements' from traces (dirty elements + their neighbours) + volume + flux on lists.  Disjoint
-    // rows, so the order of the launches is free; the small dirty-path kernels go first.
-    const int *dirty, *ring;
-    int n_dirty, n_ring;
-    hybrid_lists(plan, &dirty, &n_dirty, &ring, &n_ring);
-    if (cf && !hybrid_can_fuse_update(plan))
-      D4EST_HIP_ABORT("apply_operator: the hybrid operator of this plan does not carry a fused update");
-    if (hybrid_sharded(plan)) {
-      // a shard (tuning key 14 = 2, ghost-aware form).  Every launch on the plan's stream -- the clean buckets too, one after another: no
-      // side streams and no cross-stream events on this path (launch_hybrid_clean does not fork on a sharded plan) -- around the exchange hooks:
-      //   1. the trace kernels of the ring (the dirty elements, their neighbours, and every element whose block is sent) and the record traces
-      //   2. exchange phase 0 (pack + post)
-      //   3. the clean elements WITHOUT a ghost side, and the dirty elements' volume term: they overlap the exchange
-      //   4. exchange phase 1 (complete + unpack into the ghost trace buffer)
-      //   5. the clean elements WITH a ghost side (they read that buffer)
-      //   6. the dirty flux kernels, then the record flux kernel
-      // No clean kernel writes a trace block that the pack or another kernel of this apply reads (the ring's trace kernel does), and the
-      // ghost buffer is read only by launches queued after phase 1 has returned.  Every element's A u -- and a fused update -- comes from
-      // exactly one launch, as on one rank.
-      const bool hp = faces_hp(plan), hang = hybrid_hanging(plan), rec = hp && faces_hp_split(plan);
-      DirectFuse df;
-      ChebyFuse cu;
-      const DirectFuse* dfp = nullptr;
-      if (cf) {
-        if (!cf->u_out || cf->u_out == u) D4EST_HIP_ABORT("apply_operator: the hybrid operator needs a second vector for the fused update");
-        df.rhs = cf->rhs; df.p = cf->p; df.u_out = cf->u_out; df.r = cf->r; df.alpha = cf->alpha; df.beta = cf->beta;
-        df.skip_Au_store = cf->skip_Au_store ? 1 : 0;
-        dfp = &df;
-        cu = *cf;
-        cu.u = const_cast<double*>(u);
-      }
-      const double* gt = hang ? plan->d_trace : plan->d_ghost_trace;   // (hanging- / mixed-aware sides read the trace array)
-      if (rec) launch_traces(plan, u, plan->d_trace, false, ring, n_ring, n_ring > 0 ? 3 : 2);
-      else if (n_ring > 0) launch_traces(plan, u, plan->d_trace, false, ring, n_ring);
-      if (has_ghost) plan->exchange_fn(plan->comm_ctx, 0, plan->d_trace, plan->d_ghost_trace);
-      launch_flux_hybrid_clean(plan, u, gt, Au, 1, dfp);   // (a shard: bucket after bucket on the plan's stream, no side streams, no events)
-      if (n_dirty > 0) launch_hybrid_dirty_stiffness(plan, u, Au);
-      if (has_ghost) plan->exchange_fn(plan->comm_ctx, 1, plan->d_trace, plan->d_ghost_trace);
-      launch_flux_hybrid_clean_ghost(plan, u, Au, dfp);
-      if (cf && hp) {   // (hybrid_can_fuse_update: hanging-aware form, no dirty elements, unit record kernels)
-        launch_flux_units(plan, plan->d_trace, plan->d_ghost_trace, Au, &cu);
-        return;
-      }
-      if (n_dirty > 0) launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, cf ? &cu : nullptr, dirty, n_dirty, (rec && hang) ? 1 : 3);
-      if (rec && hang) launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, nullptr, dirty, n_dirty, 2);
-      if (!cf && lhs_term) add_lhs_mass_term(plan, u, Au);
-      return;
-    }
-    if (cf && !faces_hp(plan)) {
-      // conforming mixed-degree plan: the update in every clean bucket's kernel and in the flux kernels of the dirty list (each element's
-      // A u is final in exactly one of them); all of them read u and write the new iterate to cf->u_out
-      if (!cf->u_out || cf->u_out == u) D4EST_HIP_ABORT("apply_operator: the hybrid operator needs a second vector for the fused update");
-      DirectFuse df;
-      df.rhs = cf->rhs; df.p = cf->p; df.u_out = cf->u_out; df.r = cf->r; df.alpha = cf->alpha; df.beta = cf->beta;
-      df.skip_Au_store = cf->skip_Au_store ? 1 : 0;
-      const double* gt = hybrid_hanging(plan) ? plan->d_trace : plan->d_ghost_trace;   // (mixed-aware sides read the trace array)
-      if (n_dirty > 0) launch_traces(plan, u, plan->d_trace, false, ring, n_ring);
-      launch_flux_hybrid_clean(plan, u, gt, Au, 0, &df);
-      if (n_dirty > 0) {
-        launch_hybrid_dirty_stiffness(plan, u, Au);
-        ChebyFuse cu = *cf;
-        cu.u = const_cast<double*>(u);
-        launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, &cu, dirty, n_dirty);
-      }
-      launch_flux_hybrid_clean(plan, u, gt, Au, 1, &df);
-      return;
-    }
-    if (hybrid_hanging(plan) && cf) {
-      // the Chebyshev update in the kernels' epilogues: the operator kernel updates every element it finishes, the record flux kernel
-      // the elements with a record side (disjoint sets; both read u and write the new iterate to cf->u_out)
-      if (!cf->u_out || cf->u_out == u) D4EST_HIP_ABORT("apply_operator: the hybrid operator needs a second vector for the fused update");
-      DirectFuse df;
-      df.rhs = cf->rhs; df.p = cf->p; df.u_out = cf->u_out; df.r = cf->r; df.alpha = cf->alpha; df.beta = cf->beta;
-      df.skip_Au_store = cf->skip_Au_store ? 1 : 0;
-      launch_traces(plan, u, plan->d_trace, false, ring, n_ring, 2);
-      launch_flux_hybrid_clean(plan, u, plan->d_trace, Au, 1, &df);
-      ChebyFuse cu = *cf;
-      cu.u = const_cast<double*>(u);
-      launch_flux_units(plan, plan->d_trace, plan->d_ghost_trace, Au, &cu);
-      return;
-    }
-    if (hybrid_hanging(plan)) {
-      // hanging-aware form (a locally refined plan under the hp split): elements with hanging sides are clean too.  The record trace
-      // kernel goes first (the clean kernel reads the big elements' sub-mortar blocks for its small sides), the record flux kernel last
-      // (it adds the big sides' terms to rows the clean kernel writes, from small-side blocks that kernel exports).
-      // (mixed-aware form on a plan without hanging faces: no record kernels, the two-phase kernels whole)
-      const bool rec = faces_hp_split(plan);
-      if (rec) launch_traces(plan, u, plan->d_trace, false, ring, n_ring, n_dirty > 0 ? 3 : 2);
-      else if (n_dirty > 0) launch_traces(plan, u, plan->d_trace, false, ring, n_ring);
-      launch_flux_hybrid_clean(plan, u, plan->d_trace, Au, 0);
-      if (n_dirty > 0) {
-        launch_hybrid_dirty_stiffness(plan, u, Au);
-        launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, nullptr, dirty, n_dirty, rec ? 1 : 3);
-      }
-      launch_flux_hybrid_clean(plan, u, plan->d_trace, Au, 1);
-      if (rec) launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, nullptr, dirty, n_dirty, 2);
-      if (lhs_term) add_lhs_mass_term(plan, u, Au);
-      return;
-    }
-    launch_flux_hybrid_clean(plan, u, plan->d_ghost_trace, Au, 0);   // the clean buckets, each on its own stream beside ...
-    if (n_dirty > 0) {                                                // ... the dirty path on the plan's stream
-      launch_traces(plan, u, plan->d_trace, false, ring, n_ring);
+  const bool hp = faces_hp(plan), hang = hybrid_hanging(plan), rec = hp && faces_hp_split(plan);
+  DirectFuse df;
+  ChebyFuse cu;
+  if (cf) {
+    df = direct_fuse_of(*cf, u, "the hybrid operator");
+    cu = cheby_fuse_on(*cf, u);
+  }
+  const DirectFuse* dfp = cf ? &df : nullptr;
+  const double* gt = hang ? plan->d_trace : plan->d_ghost_trace;   // (hanging- / mixed-aware sides read the trace array)
+  if (rec) launch_traces(plan, u, plan->d_trace, false, ring, n_ring, n_ring > 0 ? 3 : 2);
+  else if (n_ring > 0) launch_traces(plan, u, plan->d_trace, false, ring, n_ring);
+  if (has_ghost) plan->exchange_fn(plan->comm_ctx, 0, plan->d_trace, plan->d_ghost_trace);
+  launch_hybrid_clean(plan, u, gt, Au, 1, dfp);   // (a shard: bucket after bucket on the plan's stream, no side streams, no events)
+  if (n_dirty > 0) launch_hybrid_dirty_stiffness(plan, u, Au);
+  if (has_ghost) plan->exchange_fn(plan->comm_ctx, 1, plan->d_trace, plan->d_ghost_trace);
+  launch_hybrid_clean_ghost(plan, u, Au, dfp);
+  if (cf && hp) {   // (hybrid_can_fuse_update: hanging-aware form, no dirty elements, unit record kernels)
+    launch_flux_units(plan, plan->d_trace, plan->d_ghost_trace, Au, &cu);
+    return;
+  }
+  if (n_dirty > 0) launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, cf ? &cu : nullptr, dirty, n_dirty, (rec && hang) ? 1 : 3);
+  if (rec && hang) launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, nullptr, dirty, n_dirty, 2);
+  if (!cf && lhs_term) add_lhs_mass_term(plan, u, Au);
+}
+
+// mixed-degree / locally refined plan (d4est_hip_direct.hip, "the hybrid operator"): the clean elements' A u from the one-kernel path of
+// their degree bucket, the dirty elements' from traces (dirty elements + their neighbours) + volume + flux on lists.  Disjoint
+// rows, so the order of the launches is free; the small dirty-path kernels go first.  Four forms on one rank; each is its list of launches
+// (the plain form forks the clean buckets BEFORE the ring traces, the hanging forms after them: side streams, deliberate).
+static void apply_hybrid(d4est_hip_plan* plan, const double* u, double* Au, const ChebyFuse* cf, bool lhs_term) {
+  if (cf && !hybrid_can_fuse_update(plan))
+    D4EST_HIP_ABORT("apply_operator: the hybrid operator of this plan does not carry a fused update");
+  if (hybrid_sharded(plan)) {
+    apply_hybrid_sharded(plan, u, Au, cf, lhs_term);
+    return;
+  }
+  const int *dirty, *ring;
+  int n_dirty, n_ring;
+  hybrid_lists(plan, &dirty, &n_dirty, &ring, &n_ring);
+  const bool hang = hybrid_hanging(plan);
+  if (cf && !faces_hp(plan)) {
+    // conforming mixed-degree plan: the update in every clean bucket's kernel and in the flux kernels of the dirty list (each element's
+    // A u is final in exactly one of them); all of them read u and write the new iterate to cf->u_out
+    const DirectFuse df = direct_fuse_of(*cf, u, "the hybrid operator");
+    const double* gt = hang ? plan->d_trace : plan->d_ghost_trace;   // (mixed-aware sides read the trace array)
+    if (n_dirty > 0) launch_traces(plan, u, plan->d_trace, false, ring, n_ring);
+    launch_hybrid_clean(plan, u, gt, Au, 0, &df);
+    if (n_dirty > 0) {
       launch_hybrid_dirty_stiffness(plan, u, Au);
-      launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, nullptr, dirty, n_dirty);
+      const ChebyFuse cu = cheby_fuse_on(*cf, u);
+      launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, &cu, dirty, n_dirty);
     }
-    launch_flux_hybrid_clean(plan, u, plan->d_ghost_trace, Au, 1);   // join
+    launch_hybrid_clean(plan, u, gt, Au, 1, &df);
+    return;
+  }
+  if (hang && cf) {
+    // the Chebyshev update in the kernels' epilogues: the operator kernel updates every element it finishes, the record flux kernel
+    // the elements with a record side (disjoint sets; both read u and write the new iterate to cf->u_out)
+    const DirectFuse df = direct_fuse_of(*cf, u, "the hybrid operator");
+    launch_traces(plan, u, plan->d_trace, false, ring, n_ring, 2);
+    launch_hybrid_clean(plan, u, plan->d_trace, Au, 1, &df);
+    const ChebyFuse cu = cheby_fuse_on(*cf, u);
+    launch_flux_units(plan, plan->d_trace, plan->d_ghost_trace, Au, &cu);
+    return;
+  }
+  if (hang) {
+    // hanging-aware form (a locally refined plan under the hp split): elements with hanging sides are clean too.  The record trace
+    // kernel goes first (the clean kernel reads the big elements' sub-mortar blocks for its small sides), the record flux kernel last
+    // (it adds the big sides' terms to rows the clean kernel writes, from small-side blocks that kernel exports).
+    // (mixed-aware form on a plan without hanging faces: no record kernels, the two-phase kernels whole)
+    const bool rec = faces_hp_split(plan);
+    if (rec) launch_traces(plan, u, plan->d_trace, false, ring, n_ring, n_dirty > 0 ? 3 : 2);
+    else if (n_dirty > 0) launch_traces(plan, u, plan->d_trace, false, ring, n_ring);
+    launch_hybrid_clean(plan, u, plan->d_trace, Au, 0);
+    if (n_dirty > 0) {
+      launch_hybrid_dirty_stiffness(plan, u, Au);
+      launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, nullptr, dirty, n_dirty, rec ? 1 : 3);
+    }
+    launch_hybrid_clean(plan, u, plan->d_trace, Au, 1);
+    if (rec) launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, nullptr, dirty, n_dirty, 2);
     if (lhs_term) add_lhs_mass_term(plan, u, Au);
     return;
   }
-  if (direct_active(plan)) {
-    // one-kernel face terms (d4est_hip_direct.hip): both sides' traces come from u inside the kernel; with ghost sides the trace
-    // kernel still runs, to feed the exchange
-    const bool mass = lhs_term && plan->d_lhs_coeff;
-    // a zeroth-order term held as dense element blocks or as a Galerkin chain (coarse multigrid levels) is not part of the fused
-    // kernels' volume stage: volume kernel, the term, then the face kernel
-    const bool fused = direct_fused_ok(plan) && !(lhs_term && lhs_extra_term(plan));
-    auto run = [&](int vterm) {
-      if (cf) {
-        DirectFuse df;
-        df.rhs = cf->rhs; df.p = cf->p; df.u_out = cf->u_out; df.r = cf->r; df.alpha = cf->alpha; df.beta = cf->beta;
-        df.skip_Au_store = (vterm != 0 && cf->skip_Au_store) ? 1 : 0;
-        if (!df.u_out || df.u_out == u) D4EST_HIP_ABORT("apply_operator: the direct face kernel needs a second vector for the fused update");
-        launch_flux_direct(plan, u, plan->d_ghost_trace, Au, &df, vterm);
-      } else {
-        launch_flux_direct(plan, u, plan->d_ghost_trace, Au, nullptr, vterm);
-      }
-    };
-    if (has_ghost && fused && !direct_has_element_list(plan)) {
-      // Several ranks, whole operator in the kernel.  Only the elements with a ghost (+) side need exchanged data -- the reference,
-      // too, packs just its mirror elements (src/Mesh/d4est_ghost_data.c:143-256): the trace kernel runs over THOSE elements to feed
-      // the exchange, the operator kernel over the interior elements runs while the blocks travel, and a second, short launch over
-      // the boundary elements follows the unpack.  Every element still gets its A u (and its fused update) from exactly one launch.
-      const int *bl, *il;
-      int nb, ni;
-      direct_ghost_split(plan, &bl, &nb, &il, &ni);
-      launch_traces(plan, u, plan->d_trace, false, bl, nb);
-      plan->exchange_fn(plan->comm_ctx, 0, plan->d_trace, plan->d_ghost_trace);
-      const int vterm = mass ? 2 : 1;
-      if (ni > 0) {
-        direct_set_element_list(plan, il, ni);
-        run(vterm);
-      }
-      plan->exchange_fn(plan->comm_ctx, 1, plan->d_trace, plan->d_ghost_trace);
-      direct_set_element_list(plan, bl, nb);
-      run(vterm);
-      direct_set_element_list(plan, nullptr, 0);
+  launch_hybrid_clean(plan, u, plan->d_ghost_trace, Au, 0);   // the clean buckets, each on its own stream beside ...
+  if (n_dirty > 0) {                                           // ... the dirty path on the plan's stream
+    launch_traces(plan, u, plan->d_trace, false, ring, n_ring);
+    launch_hybrid_dirty_stiffness(plan, u, Au);
+    launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, nullptr, dirty, n_dirty);
+  }
+  launch_hybrid_clean(plan, u, plan->d_ghost_trace, Au, 1);   // join
+  if (lhs_term) add_lhs_mass_term(plan, u, Au);
+}
+
+// one-kernel face terms (d4est_hip_direct.hip): both sides' traces come from u inside the kernel; with ghost sides the trace
+// kernel still runs, to feed the exchange
+static void apply_direct(d4est_hip_plan* plan, const double* u, double* Au, const ChebyFuse* cf, bool lhs_term) {
+  const bool has_ghost = plan->ghost_trace_doubles > 0;
+  const bool mass = lhs_term && plan->d_lhs_coeff;
+  // a zeroth-order term held as dense element blocks or as a Galerkin chain (coarse multigrid levels) is not part of the fused
+  // kernels' volume stage: volume kernel, the term, then the face kernel
+  const bool fused = direct_fused_ok(plan) && !(lhs_term && lhs_extra_term(plan));
+  auto run = [&](int vterm) {
+    if (!cf) {
+      launch_direct_faces(plan, u, plan->d_ghost_trace, Au, nullptr, vterm);
       return;
     }
-    // one-kernel face terms (d4est_hip_direct.hip): both sides' traces come from u inside the kernel; with ghost sides the trace
-    // kernel still runs, to feed the exchange
-    if (has_ghost) {
-      launch_traces(plan, u, plan->d_trace, false);
-      plan->exchange_fn(plan->comm_ctx, 0, plan->d_trace, plan->d_ghost_trace);
+    DirectFuse df = direct_fuse_of(*cf, u, "the direct face kernel");
+    df.skip_Au_store = (vterm != 0 && cf->skip_Au_store) ? 1 : 0;   // (only the whole-operator form consumes A u in registers)
+    launch_direct_faces(plan, u, plan->d_ghost_trace, Au, &df, vterm);
+  };
+  if (has_ghost && fused && !direct_has_element_list(plan)) {
+    // Several ranks, whole operator in the kernel.  Only the elements with a ghost (+) side need exchanged data -- the reference,
+    // too, packs just its mirror elements (src/Mesh/d4est_ghost_data.c:143-256): the trace kernel runs over THOSE elements to feed
+    // the exchange, the operator kernel over the interior elements runs while the blocks travel, and a second, short launch over
+    // the boundary elements follows the unpack.  Every element still gets its A u (and its fused update) from exactly one launch.
+    const int *bl, *il;
+    int nb, ni;
+    direct_ghost_split(plan, &bl, &nb, &il, &ni);
+    launch_traces(plan, u, plan->d_trace, false, bl, nb);
+    plan->exchange_fn(plan->comm_ctx, 0, plan->d_trace, plan->d_ghost_trace);
+    const int vterm = mass ? 2 : 1;
+    if (ni > 0) {
+      direct_set_element_list(plan, il, ni);
+      run(vterm);
     }
-    // the volume term rides in the same kernel (u in, A u out) unless an exchange is to overlap it; the zeroth-order term of
-    // plan_set_lhs_coefficient then sits in that kernel's volume stage (vol_term 2)
-    const bool whole = !has_ghost && fused;
-    const int vterm = whole ? (mass ? 2 : 1) : 0;
-    if (!whole) {
-      launch_stiffness(plan, u, Au);
-      if (lhs_term) add_lhs_mass_term(plan, u, Au);
-    }
-    if (has_ghost) plan->exchange_fn(plan->comm_ctx, 1, plan->d_trace, plan->d_ghost_trace);
+    plan->exchange_fn(plan->comm_ctx, 1, plan->d_trace, plan->d_ghost_trace);
+    direct_set_element_list(plan, bl, nb);
     run(vterm);
+    direct_set_element_list(plan, nullptr, 0);
     return;
   }
+  if (has_ghost) {
+    launch_traces(plan, u, plan->d_trace, false);
+    plan->exchange_fn(plan->comm_ctx, 0, plan->d_trace, plan->d_ghost_trace);
+  }
+  // the volume term rides in the same kernel (u in, A u out) unless an exchange is to overlap it; the zeroth-order term of
+  // plan_set_lhs_coefficient then sits in that kernel's volume stage (vol_term 2)
+  const bool whole = !has_ghost && fused;
+  const int vterm = whole ? (mass ? 2 : 1) : 0;
+  if (!whole) {
+    launch_stiffness(plan, u, Au);
+    if (lhs_term) add_lhs_mass_term(plan, u, Au);
+  }
+  if (has_ghost) plan->exchange_fn(plan->comm_ctx, 1, plan->d_trace, plan->d_ghost_trace);
+  run(vterm);
+}
+
+// traces, volume, flux.  With ghost sides the exchange callbacks enqueue on the plan's (single) stream: traces, post, volume, complete,
+// flux.  Opt-in fork (tuning key 5 = 1, one rank): the trace kernel runs on the plan's side stream while the volume kernel runs on the
+// main stream -- they only share the read-only u -- and the flux kernel joins them.  Measured: the two cross-stream event waits cost more
+// than the overlap buys (config 2: 119 -> 129 us; 512 elements: 16 -> 44 us), so the default is one stream
+static void apply_two_phase(d4est_hip_plan* plan, const double* u, double* Au, const ChebyFuse* cf, bool lhs_term) {
+  const bool has_ghost = plan->ghost_trace_doubles > 0;
   const bool fork = plan->tuning[D4EST_HIP_TUNE_OVERLAP_TRACES] > 0 && !has_ghost;
   if (fork) {
     if (!plan->side_stream) {
@@ -342,13 +348,22 @@ void apply_operator(d4est_hip_plan* plan, const double* u, double* Au, const Che
     launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, cf);
     return;
   }
-  // with ghost sides the exchange callbacks enqueue on the plan's (single) stream: traces, post, volume, complete, flux
   launch_traces(plan, u, plan->d_trace, false);
   if (has_ghost) plan->exchange_fn(plan->comm_ctx, 0, plan->d_trace, plan->d_ghost_trace);
   launch_stiffness(plan, u, Au);  // overlaps the exchange: the volume term needs no ghost data
   if (lhs_term) add_lhs_mass_term(plan, u, Au);  // before the flux kernel, so an update fused into its epilogue sees the whole A u
   if (has_ghost) plan->exchange_fn(plan->comm_ctx, 1, plan->d_trace, plan->d_ghost_trace);
   launch_flux(plan, plan->d_trace, plan->d_ghost_trace, Au, cf);
+}
+
+// Au = A u with the plan's communication hooks (or without ghosts): one of three schedules
+void apply_operator(d4est_hip_plan* plan, const double* u, double* Au, const ChebyFuse* cf, bool lhs_term) {
+  if (!plan->has_faces) D4EST_HIP_ABORT("smoother: the plan has no faces (plan_set_faces)");
+  ensure_solver_workspace(plan);
+  if (plan->ghost_trace_doubles > 0 && !plan->exchange_fn) D4EST_HIP_ABORT("apply_lhs: plan has ghost sides but no exchange callback (plan_set_comm)");
+  if (hybrid_active(plan)) apply_hybrid(plan, u, Au, cf, lhs_term);
+  else if (direct_active(plan)) apply_direct(plan, u, Au, cf, lhs_term);
+  else apply_two_phase(plan, u, Au, cf, lhs_term);
 }
 
 // the zeroth-order term of a linearised nonlinear problem (d4est_quadrature_apply_fofufofvlilj per element, added with axpy 1.0:
@@ -361,8 +376,7 @@ void add_lhs_mass_term(d4est_hip_plan* plan, const double* u, double* Au) {
   const int n = plan->local_nodes;
   if (!plan->d_work_m) HIP_CHECK(hipMalloc(&plan->d_work_m, (size_t)n * sizeof(double)));
   launch_mass_like(plan, 3, u, plan->d_work_m, plan->d_lhs_c, 0);
-  hipLaunchKernelGGL(add_kernel, dim3(grid_for(n)), dim3(256), 0, plan->stream, n, plan->d_work_m, Au);
-  HIP_CHECK(hipGetLastError());
+  launch_add(plan, n, plan->d_work_m, Au);
 }
 
 // w J c at the quadrature nodes of the elements of one (deg, deg_quad) bucket (elements that alias each other's quadrature block -- the

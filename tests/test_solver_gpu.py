@@ -47,6 +47,40 @@ def test_cheby_iterate_parity(gpu, hiplib, oracle, level, deg, curved):
     assert np.linalg.norm(r_ref) < np.linalg.norm(r0)
 
 
+@pytest.mark.parametrize("deg", [2, 7])
+def test_forked_two_phase_schedule(gpu, hiplib, oracle, deg):
+    """tuning key 5 = 1: the trace kernel on the plan's side stream beside the volume kernel, the flux kernel joins them.  The same
+    kernels on the same data as the one-stream schedule: apply_lhs and cheby_iterate are held to the oracle at this file's tolerances
+    (1e-12; 1e-11 / 1e-10) and are bit-equal to the unforked default plan."""
+    import torch
+    from disco4est_amd import Plan, mesh as M
+    m, plan = _setup(1, deg, M.SineMap(0.05), gpu, oracle)
+    J, rst = m.geometry(M.SineMap(0.05)); sides = m.build_sides(M.SineMap(0.05))
+    forked = Plan(m.deg, m.deg_quad, m.nodal_stride, m.quad_stride, 0)
+    forked.set_tuning(5, 1)
+    forked.set_geometry(J, rst)
+    forked.set_faces(sides, 10.0, 0)
+    assert plan.face_path() == "two-phase" and forked.face_path() == "two-phase"   # (8 elements: the schedule the fork belongs to)
+    u0 = M.splitmix64_uniform(11, m.local_nodes)
+    rhs = M.splitmix64_uniform(12, m.local_nodes) - 0.5
+    lmax, _ = oracle.cg_eigs(np.zeros(m.local_nodes), rhs, 10)
+    u_ref, r_ref = oracle.cheby_iterate(u0, rhs, 4, lmax / 30.0, lmax, 1)
+    Au_ref = oracle.apply_aij(m, *oracle._op_keep[1:], u0)
+    got = {}
+    for name, p in (("default", plan), ("forked", forked)):
+        du = _t(u0, gpu); dAu = torch.full_like(du, float("nan")); dr = torch.full_like(du, float("nan"))
+        p.apply_lhs(du, dAu)
+        Au = dAu.cpu().numpy()
+        p.cheby_iterate(du, _t(rhs, gpu), dAu, dr, 4, lmax / 30.0, lmax, 1)
+        got[name] = (Au, du.cpu().numpy(), dr.cpu().numpy())
+    Au, u, r = got["forked"]
+    assert _rel(Au, Au_ref) <= 1e-12
+    assert _rel(u, u_ref) <= 1e-11 and _rel(r, r_ref) <= 1e-10
+    for a, b in zip(got["forked"], got["default"]):
+        assert np.array_equal(a, b)
+    plan.destroy(); forked.destroy()
+
+
 def test_smoother_on_hanging_mesh(gpu, hiplib, oracle):
     """Chebyshev iteration and cg_eigs on a locally refined, mixed-p mesh (hanging 1 <-> 4 mortars in the operator)."""
     import torch
