@@ -7,8 +7,8 @@ torch CUDA tensors (torch is used for device memory and streams only) and the
 synthetic-mesh helpers.  There is NO CPU fallback: if the library is missing or
 fails to load, importing :mod:`disco4est_amd.capi` raises.
 """
-from .capi import Plan, Transfer, Amr, Probe, Multigrid, multigrid_check, load_library, table, TABLE  # noqa: F401
+from .capi import Plan, Transfer, Amr, Probe, Multigrid, PcCheby, PcSchwarz, multigrid_check, load_library, table, TABLE  # noqa: F401
 from . import mesh  # noqa: F401
 from .schwarz import Schwarz, SchwarzMetadata  # noqa: F401
 
-__all__ = ["Plan", "Transfer", "Amr", "Probe", "Multigrid", "multigrid_check", "Schwarz", "SchwarzMetadata", "load_library", "table", "TABLE", "mesh"]
+__all__ = ["Plan", "Transfer", "Amr", "Probe", "Multigrid", "PcCheby", "PcSchwarz", "multigrid_check", "Schwarz", "SchwarzMetadata", "load_library", "table", "TABLE", "mesh"]

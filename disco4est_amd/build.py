@@ -31,6 +31,7 @@ SOURCES = [
     "d4est_hip_norms.hip",
     "d4est_hip_krylov.hip",
     "d4est_hip_multigrid.hip",
+    "d4est_hip_pc.hip",
     "d4est_hip_amr.hip",
     "d4est_hip_sizes.hip",
     "d4est_hip_hessian.hip",

@@ -161,6 +161,17 @@ SIGNATURES = {
     "d4est_hip_multigrid_set_pc": (None, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double]),
     "d4est_hip_multigrid_pc_apply": (None, [_vp, _vp, _vp]),
     "d4est_hip_multigrid_get_info": (None, [_vp, _c_double_p, _c_int_p, _c_int_p]),
+    "d4est_hip_multigrid_set_smoother_schwarz": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double]),
+    "d4est_hip_multigrid_smooth_level": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "d4est_hip_multigrid_set_bottom_solver_reuse_smoother": (None, [_vp]),
+    "d4est_hip_pc_cheby_create": (_vp, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "d4est_hip_pc_cheby_destroy": (None, [_vp]),
+    "d4est_hip_pc_cheby_apply": (None, [_vp, _vp, _vp]),
+    "d4est_hip_pc_cheby_eig": (ctypes.c_double, [_vp, _c_int_p]),
+    "d4est_hip_pc_cheby_reset_eig": (None, [_vp]),
+    "d4est_hip_pc_schwarz_create": (_vp, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double]),
+    "d4est_hip_pc_schwarz_destroy": (None, [_vp]),
+    "d4est_hip_pc_schwarz_apply": (None, [_vp, _vp, _vp]),
     "d4est_hip_copy_blocks": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "d4est_hip_plan_trace_offset": (ctypes.c_longlong, [_vp, ctypes.c_int]),
     "d4est_hip_plan_side_blocks": (ctypes.c_int, [_vp, ctypes.c_int]),
@@ -1416,6 +1427,38 @@ class Multigrid:
             int(cheby_eigs_reuse_fromdownvcycle), int(cheby_eigs_reuse_fromlastvcycle), int(cheby_use_new_cg_eigs),
             int(cheby_use_zero_guess_for_eigs))
 
+    def set_smoother_schwarz(self, schwarz_list, iterations, subdomain_iter=None, subdomain_atol=None, subdomain_rtol=None):
+        """the [mg_smoother_schwarz] smoother: schwarz_list[l] is the schwarz.Schwarz object of plans[l] (entry 0 may be None unless the
+        reuse_smoother bottom solver is used).  The subdomain CG options are the Schwarz objects' own (they must agree, as in the
+        reference where one input section serves every level) unless passed explicitly.  Returns the C code: 0 accepted; 1 a missing
+        entry on a level >= 1; 2 node counts; 3 streams; 4 a plan with ghost sides; 5 options <= 0"""
+        sl = list(schwarz_list)
+        if len(sl) != self.n_levels:
+            raise ValueError("set_smoother_schwarz: %d entries for %d levels" % (len(sl), self.n_levels))
+        given = [z for z in sl if z is not None]
+        opts = []
+        for name, val in (("subdomain_iter", subdomain_iter), ("subdomain_atol", subdomain_atol), ("subdomain_rtol", subdomain_rtol)):
+            if val is None:
+                vals = {getattr(z, name) for z in given}
+                if len(vals) > 1:
+                    raise ValueError("set_smoother_schwarz: the Schwarz objects disagree on %s; pass it explicitly" % name)
+                val = vals.pop() if vals else 0
+            opts.append(val)
+        self._schwarz = sl                                   # kept alive: the object only borrows the handles
+        ha = (ctypes.c_void_p * self.n_levels)(*[(z.handle if z is not None else None) for z in sl])
+        return self.lib.d4est_hip_multigrid_set_smoother_schwarz(self.handle, ha, int(iterations), int(opts[0]), float(opts[1]), float(opts[2]))
+
+    def set_bottom_solver_reuse_smoother(self):
+        """[mg_bottom_solver_reuse_smoother]: the bottom solve is the current smoother on level 0"""
+        self.lib.d4est_hip_multigrid_set_bottom_solver_reuse_smoother(self.handle)
+
+    def smooth_level(self, level, u, rhs, Au, r):
+        """one call of the current smoother on `level`, as the V-cycle makes it: r = rhs - A u of the final iterate on exit"""
+        n = self.plans[level].local_nodes
+        for t in (u, rhs, Au, r):
+            assert t.numel() == n
+        self.lib.d4est_hip_multigrid_smooth_level(self.handle, int(level), _ptr(u), _ptr(rhs), _ptr(Au), _ptr(r))
+
     def set_bottom_solver_cg(self, bottom_imax, bottom_atol, bottom_rtol):
         self.lib.d4est_hip_multigrid_set_bottom_solver_cg(self.handle, int(bottom_imax), float(bottom_atol), float(bottom_rtol))
 
@@ -1467,6 +1510,90 @@ class Multigrid:
     def destroy(self):
         if self.handle:
             self.lib.d4est_hip_multigrid_destroy(self.handle)
+            self.handle = None
+            self.pc_ctx = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class PcCheby:
+    """d4est_krylov_pc_cheby on the device (d4est_hip_pc_cheby_*), the [d4est_krylov_pc_cheby] keys.  Passed as `pc` to Plan.fcg_solve /
+    Plan.newton_solve like a Multigrid: `pc_fn` / `pc_ctx` are the C function pointer and the object, no Python in the loop."""
+
+    def __init__(self, plan, cheby_imax, cheby_eigs_cg_imax, cheby_eigs_lmax_lmin_ratio, cheby_eigs_max_multiplier=1.0, cheby_reuse_eig=0,
+                 cheby_use_new_cg_eigs=0, cheby_use_zero_guess_for_eigs=0):
+        self.lib = load_library()
+        self.handle = None
+        if int(cheby_imax) < 0 or int(cheby_eigs_cg_imax) < 1 or not float(cheby_eigs_lmax_lmin_ratio) > 0.0:   # (the C entry would abort)
+            raise ValueError("PcCheby: cheby_imax < 0, cheby_eigs_cg_imax < 1 or a ratio that is not positive")
+        self.plan = plan                                     # kept alive: the object only borrows it
+        self.local_nodes = plan.local_nodes
+        self.handle = self.lib.d4est_hip_pc_cheby_create(plan.handle, int(cheby_imax), int(cheby_eigs_cg_imax), float(cheby_eigs_lmax_lmin_ratio),
+                                                         float(cheby_eigs_max_multiplier), int(cheby_reuse_eig), int(cheby_use_new_cg_eigs),
+                                                         int(cheby_use_zero_guess_for_eigs))
+        self.pc_fn = ctypes.cast(self.lib.d4est_hip_pc_cheby_apply, ctypes.c_void_p).value
+        self.pc_ctx = self.handle
+
+    def apply(self, r, z):
+        """z = B r"""
+        assert r.numel() == self.local_nodes and z.numel() == self.local_nodes
+        self.lib.d4est_hip_pc_cheby_apply(self.handle, _ptr(r), _ptr(z))
+
+    def eig(self):
+        """(the bound held, after the multiplier; -1 = none, cg_eigs runs so far)"""
+        runs = ctypes.c_int(0)
+        e = self.lib.d4est_hip_pc_cheby_eig(self.handle, ctypes.byref(runs))
+        return e, runs.value
+
+    def reset_eig(self):
+        self.lib.d4est_hip_pc_cheby_reset_eig(self.handle)
+
+    def destroy(self):
+        if self.handle:
+            self.lib.d4est_hip_pc_cheby_destroy(self.handle)
+            self.handle = None
+            self.pc_ctx = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class PcSchwarz:
+    """d4est_krylov_pc_schwarz on the device (d4est_hip_pc_schwarz_*): z = 0, then `iterations` times { residual = r - A z;
+    schwarz_iterate(z, residual) }.  schwarz: a schwarz.Schwarz object of the mesh whose plan is mesh_plan; the subdomain CG options are
+    the object's own unless passed.  Passed as `pc` to Plan.fcg_solve / Plan.newton_solve like a Multigrid."""
+
+    def __init__(self, schwarz, mesh_plan, iterations=1, subdomain_iter=None, subdomain_atol=None, subdomain_rtol=None):
+        self.lib = load_library()
+        self.handle = None
+        it = schwarz.subdomain_iter if subdomain_iter is None else subdomain_iter
+        atol = schwarz.subdomain_atol if subdomain_atol is None else subdomain_atol
+        rtol = schwarz.subdomain_rtol if subdomain_rtol is None else subdomain_rtol
+        if mesh_plan.local_nodes != schwarz.local_nodes:      # (the C entry would abort)
+            raise ValueError("PcSchwarz: the plan has %d nodes, the smoother's mesh %d" % (mesh_plan.local_nodes, schwarz.local_nodes))
+        if int(iterations) < 0 or int(it) <= 0 or not float(atol) > 0 or not float(rtol) > 0:
+            raise ValueError("PcSchwarz: some options are <= 0")
+        self.schwarz, self.plan = schwarz, mesh_plan         # kept alive: the object only borrows them
+        self.local_nodes = mesh_plan.local_nodes
+        self.handle = self.lib.d4est_hip_pc_schwarz_create(schwarz.handle, mesh_plan.handle, int(iterations), int(it), float(atol), float(rtol))
+        self.pc_fn = ctypes.cast(self.lib.d4est_hip_pc_schwarz_apply, ctypes.c_void_p).value
+        self.pc_ctx = self.handle
+
+    def apply(self, r, z):
+        """z = B r"""
+        assert r.numel() == self.local_nodes and z.numel() == self.local_nodes
+        self.lib.d4est_hip_pc_schwarz_apply(self.handle, _ptr(r), _ptr(z))
+
+    def destroy(self):
+        if self.handle:
+            self.lib.d4est_hip_pc_schwarz_destroy(self.handle)
             self.handle = None
             self.pc_ctx = None
 

@@ -1,12 +1,13 @@
 // The hp-multigrid V-cycle on the device: d4est_solver_multigrid_vcycle / d4est_solver_multigrid_solve
 // (src/Solver/d4est_solver_multigrid.c:751-1348, :1420-1506), the Chebyshev smoother driver with its eigenvalue-reuse rules
-// (src/Solver/d4est_solver_multigrid_smoother_cheby.c:222-376), the CG and Chebyshev bottom solvers
-// (d4est_solver_multigrid_bottom_solver_cg.c:48-198, d4est_solver_multigrid_bottom_solver_cheby.c:59-113) and the preconditioner
-// d4est_krylov_pc_multigrid_apply (src/Solver/d4est_krylov_pc_multigrid.c:40-77).
+// (src/Solver/d4est_solver_multigrid_smoother_cheby.c:222-376), the Schwarz smoother (d4est_solver_multigrid_smoother_schwarz.c:89-204),
+// the CG, Chebyshev and reuse_smoother bottom solvers (d4est_solver_multigrid_bottom_solver_cg.c:48-198,
+// d4est_solver_multigrid_bottom_solver_cheby.c:59-113, d4est_solver_multigrid_bottom_solver_reuse_smoother.c:20-39) and the
+// preconditioner d4est_krylov_pc_multigrid_apply (src/Solver/d4est_krylov_pc_multigrid.c:40-77).
 //
 // The object ties together pieces that exist: every level's operator is a plan (apply_lhs with whatever zeroth-order term and
-// communication hooks the caller set on it), the smoother is cheby_iterate / cg_eigs, the bottom CG is cg_solve, the grid transfers are
-// transfer objects.  Levels are numbered as in the reference: 0 = bottom (coarsest) ... n_levels - 1 = top (finest); transfers[l]
+// communication hooks the caller set on it), the smoother is cheby_iterate / cg_eigs or the caller's Schwarz handles (one per level,
+// d4est_hip_schwarz.hip: schwarz_smoother_run), the bottom CG is cg_solve, the grid transfers are transfer objects.  Levels are numbered as in the reference: 0 = bottom (coarsest) ... n_levels - 1 = top (finest); transfers[l]
 // connects level l (coarse) and l + 1 (fine).  The workspace is one arena per vector kind, laid out like the reference's Ae_at0,
 // err_at0, res_at0, rres_at0 (:797-800): the top level first (stride_to_fine_data = 0), then every coarser level; Ae, err and res exist
 // only below the top (the top uses the caller's Au, u, rhs), rres on every level.  Allocated once, at create.
@@ -21,11 +22,12 @@
 //     are the same bit for bit; environment D4EST_HIP_MG_UNFUSED_CORRECTION=1 (read at create) runs prolong + add as two kernels;
 //   - vcycle_r2 = rres_top . rres_top (:1330-1332) through the plan's fixed-order two-stage reduction (no atomics).
 // The host reads r2 once per cycle (the stop rule of :1467-1494); that is the only synchronisation the object adds to those its parts
-// make (cg_eigs reads its Lanczos coefficients, cg_solve its stop flag).
+// make (cg_eigs reads its Lanczos coefficients, cg_solve its stop flag, a Schwarz iterate its "still iterating" counter before the
+// first and then every 8th subdomain sweep).
 //
-// Not here: the Schwarz smoother slot (d4est_hip_schwarz_smooth has the contract of Smoother::smooth -- r = rhs - A u on exit -- and goes
-// behind that interface), the reuse_smoother and PETSc bottom solvers, the reference-named compat entry points (they need
-// d4est_solver_multigrid_t's layout and a mutating p4est), hierarchies coarsened across ranks (every level's hooks are simply used).
+// Not here: the Schwarz smoother on plans with ghost sides (the whole-element exchanges around an iterate are the host's), the PETSc
+// bottom solver, the reference-named compat entry points (they need d4est_solver_multigrid_t's layout and a mutating p4est),
+// hierarchies coarsened across ranks (every level's hooks are simply used).
 // Coarse operators are whatever the caller set on plans[l]; homogeneous boundary data on every level is the caller's contract, as in the
 // reference, where build_rhs_with_strong_bc moved g into rhs.  The object never switches D4EST_HIP_TUNE_GRAPH on: the plans are the
 // caller's (a caller may set key 9 on launch-bound coarse plans).
@@ -48,6 +50,8 @@ struct Smoother {
   virtual void upv_pre_smooth(int vcycle_index) = 0;  // mg_state == UPV_PRE_SMOOTH
   // smooth A u = rhs on `level`; r = rhs - A u of the final iterate on exit
   virtual void smooth(int level, double* u, const double* rhs, double* Au, double* r) = 0;
+  virtual double eig(int level) const = 0;            // the spectral bound last used on `level`, -1: none (or a smoother without one)
+  virtual bool covers_level0() const = 0;             // the smoother can run on level 0 (the reuse_smoother bottom solver)
 };
 
 }  // namespace
@@ -68,7 +72,7 @@ struct d4est_hip_multigrid {
   double* r2_host = nullptr;   // pinned
   bool fused_correction = true;
   d4est_hip::Smoother* smoother = nullptr;
-  // bottom solver: 0 none, 1 CG, 2 Chebyshev
+  // bottom solver: 0 none, 1 CG, 2 Chebyshev, 3 reuse_smoother
   int bottom_kind = 0;
   int bottom_imax = 0;
   double bottom_atol = 0.0, bottom_rtol = 0.0;
@@ -119,6 +123,30 @@ struct ChebySmoother : Smoother {
     const double lmax = eigs[level], lmin = eigs[level] / ratio;   // :355-357
     cheby_iterate(plan, u, rhs, Au, r, cheby_imax, lmin, lmax, 1);  // :364-375
   }
+  double eig(int level) const override { return eigs[level]; }
+  // level 0 takes its bound like any other level: eigs_compute is what PRE_V left (the update callback knows no bottom state,
+  // :234-257), so the first cycle always computes eigs[0] before a later one can reuse it
+  bool covers_level0() const override { return true; }
+};
+
+// d4est_solver_multigrid_smoother_schwarz (src/Solver/d4est_solver_multigrid_smoother_schwarz.c:89-204)
+struct SchwarzSmoother : Smoother {
+  d4est_hip_multigrid* mg;
+  std::vector<d4est_hip_schwarz*> schwarz_on_level;   // the caller's handles (:221, :240-242)
+  int iterations, subdomain_iter;
+  double subdomain_atol, subdomain_rtol;
+
+  // d4est_solver_multigrid_smoother_schwarz_update (:296-365) keeps debug counters and builds the level's Schwarz data at
+  // DOWNV_POST_BALANCE; the data are the caller's here, so nothing is left for PRE_V and UPV_PRE_SMOOTH: no eigenvalue state
+  void pre_v(int) override {}
+  void upv_pre_smooth(int) override {}
+  void smooth(int level, double* u, const double* rhs, double* /*Au: the reference's smoother leaves vecs->Au alone, :112-113*/,
+              double* r) override {
+    // :110-152 iterations x { r = rhs - A u; schwarz_iterate(u, r) }, :154-196 r = rhs - A u
+    schwarz_smoother_run(schwarz_on_level[level], mg->plans[level], u, rhs, r, iterations, subdomain_iter, subdomain_atol, subdomain_rtol);
+  }
+  double eig(int) const override { return -1.0; }
+  bool covers_level0() const override { return schwarz_on_level[0] != nullptr; }
 };
 
 const char* check_message(int code) {
@@ -133,7 +161,7 @@ const char* check_message(int code) {
 
 void require_ready(d4est_hip_multigrid* mg, const char* who) {
   if (!mg) D4EST_HIP_ABORT("%s: NULL multigrid object", who);
-  if (!mg->smoother || mg->bottom_kind == 0) D4EST_HIP_ABORT("%s: the object is not ready (set a smoother and a bottom solver first)", who);
+  if (!d4est_hip_multigrid_ready(mg)) D4EST_HIP_ABORT("%s: the object is not ready (set a smoother and a bottom solver first)", who);
 }
 
 // the bottom solver on (err_0, res_0, Ae_0); rres_0 is its residual vector
@@ -143,6 +171,10 @@ void bottom_solve(d4est_hip_multigrid* mg) {
   if (mg->bottom_kind == 1) {
     // d4est_solver_multigrid_bottom_solver_cg.c:48-198 is the recurrence of d4est_solver_cg_solve, statement for statement
     mg->last_bottom_iterations = cg_solve(plan, u, rhs, Au, mg->bottom_imax, mg->bottom_atol, mg->bottom_rtol, nullptr);
+  } else if (mg->bottom_kind == 3) {
+    // d4est_solver_multigrid_bottom_solver_reuse_smoother.c:30-37: smoother->smooth(p4est, vecs, fcns, r, 0)
+    mg->smoother->smooth(0, u, rhs, Au, r);
+    mg->last_bottom_iterations = 0;   // (the smoother reports no count)
   } else {
     // d4est_solver_multigrid_bottom_solver_cheby.c:73-112: cg_eigs from the current iterate on every call, the multiplier, the iteration
     mg->bcheby_eig = cg_eigs(plan, u, rhs, Au, mg->bcheby_eigs_cg_imax, mg->bcheby_use_new, nullptr);
@@ -311,6 +343,38 @@ int d4est_hip_multigrid_set_smoother_cheby(d4est_hip_multigrid_t* mg, int cheby_
   return 0;
 }
 
+int d4est_hip_multigrid_set_smoother_schwarz(d4est_hip_multigrid_t* mg, d4est_hip_schwarz_t* const* schwarz_on_level, int smoother_iterations,
+                                             int subdomain_iter, double subdomain_atol, double subdomain_rtol) {
+  if (!mg) D4EST_HIP_ABORT("multigrid_set_smoother_schwarz: NULL multigrid object");
+  delete mg->smoother;
+  mg->smoother = nullptr;
+  if (!schwarz_on_level) return 1;
+  for (int l = 1; l < mg->n_levels; ++l)
+    if (!schwarz_on_level[l]) return 1;                 // (level 0 may be NULL: only the reuse_smoother bottom solver smooths there)
+  for (int l = 0; l < mg->n_levels; ++l) {
+    if (!schwarz_on_level[l]) continue;
+    // 2: node counts, 3: streams, 4: ghost sides -- schwarz_iterate is a one-rank entry, the whole-element exchanges are the host's
+    const int code = d4est_hip::schwarz_smoother_check(schwarz_on_level[l], mg->plans[l]);
+    if (code != 0) return code;
+  }
+  // "some subdomain solver options are <= 0" (d4est_solver_schwarz_subdomain_solver_cg.c:86-92); a negative iteration count runs nothing
+  if (subdomain_iter <= 0 || !(subdomain_atol > 0) || !(subdomain_rtol > 0) || smoother_iterations < 0) return 5;
+  d4est_hip::SchwarzSmoother* s = new d4est_hip::SchwarzSmoother();
+  s->mg = mg;
+  s->schwarz_on_level.assign(schwarz_on_level, schwarz_on_level + mg->n_levels);
+  s->iterations = smoother_iterations;
+  s->subdomain_iter = subdomain_iter;
+  s->subdomain_atol = subdomain_atol;
+  s->subdomain_rtol = subdomain_rtol;
+  mg->smoother = s;
+  return 0;
+}
+
+void d4est_hip_multigrid_set_bottom_solver_reuse_smoother(d4est_hip_multigrid_t* mg) {
+  if (!mg) D4EST_HIP_ABORT("multigrid_set_bottom_solver_reuse_smoother: NULL multigrid object");
+  mg->bottom_kind = 3;   // d4est_solver_multigrid_bottom_solver_reuse_smoother_init (:5-18): no parameters of its own
+}
+
 void d4est_hip_multigrid_set_bottom_solver_cg(d4est_hip_multigrid_t* mg, int bottom_imax, double bottom_atol, double bottom_rtol) {
   if (!mg) D4EST_HIP_ABORT("multigrid_set_bottom_solver_cg: NULL multigrid object");
   if (bottom_imax < 0) D4EST_HIP_ABORT("multigrid_set_bottom_solver_cg: bottom_imax = %d", bottom_imax);
@@ -341,7 +405,20 @@ void d4est_hip_multigrid_set_pc(d4est_hip_multigrid_t* mg, int vcycle_imax, doub
   mg->pc_rtol = vcycle_rtol;
 }
 
-int d4est_hip_multigrid_ready(const d4est_hip_multigrid_t* mg) { return (mg && mg->smoother && mg->bottom_kind != 0) ? 1 : 0; }
+int d4est_hip_multigrid_ready(const d4est_hip_multigrid_t* mg) {
+  if (!mg || !mg->smoother || mg->bottom_kind == 0) return 0;
+  if (mg->bottom_kind == 3 && !mg->smoother->covers_level0()) return 0;   // reuse_smoother needs the smoother on level 0
+  return 1;
+}
+
+void d4est_hip_multigrid_smooth_level(d4est_hip_multigrid_t* mg, int level, double* u_dev, const double* rhs_dev, double* Au_dev,
+                                      double* r_dev) {
+  if (!mg || !mg->smoother) D4EST_HIP_ABORT("multigrid_smooth_level: no smoother is set");
+  if (level < 0 || level >= mg->n_levels || (level == 0 && !mg->smoother->covers_level0()))
+    D4EST_HIP_ABORT("multigrid_smooth_level: the smoother does not cover level %d", level);
+  if (!u_dev || !rhs_dev || !Au_dev || !r_dev) D4EST_HIP_ABORT("multigrid_smooth_level: NULL vector");
+  mg->smoother->smooth(level, u_dev, rhs_dev, Au_dev, r_dev);
+}
 
 void d4est_hip_multigrid_vcycle(d4est_hip_multigrid_t* mg, double* u_dev, const double* rhs_dev, double* Au_dev, int vcycle_index) {
   d4est_hip::require_ready(mg, "multigrid_vcycle");
@@ -376,8 +453,7 @@ void d4est_hip_multigrid_pc_apply(void* ctx, const double* r_dev, double* z_dev)
 void d4est_hip_multigrid_get_info(const d4est_hip_multigrid_t* mg, double* eigs_host, int* vcycles, int* bottom_iterations) {
   if (!mg) D4EST_HIP_ABORT("multigrid_get_info: NULL multigrid object");
   if (eigs_host) {
-    const d4est_hip::ChebySmoother* s = static_cast<const d4est_hip::ChebySmoother*>(mg->smoother);
-    for (int l = 0; l < mg->n_levels; ++l) eigs_host[l] = s ? s->eigs[l] : -1.0;
+    for (int l = 0; l < mg->n_levels; ++l) eigs_host[l] = mg->smoother ? mg->smoother->eig(l) : -1.0;
     if (mg->bottom_kind == 2) eigs_host[0] = mg->bcheby_eig;   // level 0 is never smoothed: the bottom Chebyshev solver's bound
   }
   if (vcycles) *vcycles = mg->last_vcycles;

@@ -72,6 +72,10 @@ struct d4est_hip_schwarz {
   int n_keep = 0;
   int* d_cond_off = nullptr;         // per condensed copy: field offsets of its inputs (own restricted nodes first, then the neighbours')
   long long cond_block_doubles = 0;
+  // D4EST_HIP_SCHWARZ_FUSED_RESIDUAL=1 (read at create): the smoother loop (schwarz_smoother_run, schwarz_pc_run) forms rhs - A u
+  // inside the CG start instead of writing it to a mesh vector first -- same numbers.  Off by default: on the level-4, p = 7 cycle
+  // it measured no faster than the two-kernel sequence; D4EST_HIP_SCHWARZ_UNFUSED_RESIDUAL=1 forces it off.
+  bool fused_residual = false;
 };
 
 namespace d4est_hip {
@@ -129,9 +133,14 @@ __global__ __launch_bounds__(256) void schwarz_mask_kernel(const VirtDesc* __res
   }
 }
 
-// CG start of every subdomain: du = 0, r = d = restricted residual (A du = 0 exactly), delta_0, the break tolerance
+// CG start of every subdomain: du = 0, r = d = restricted residual (A du = 0 exactly), delta_0, the break tolerance.
+// FUSED: r_mesh is the right-hand side and Au_mesh is A u; the residual rhs - A u is formed node by node as it is restricted (the one
+// rounded operation of residual_inplace_kernel, d4est_linalg_vec_xpby(rhs, -1., r) of d4est_solver_multigrid_smoother_schwarz.c:128),
+// so the mesh vector r is never written and not read back up to 27 times.  !FUSED: r_mesh is the residual, Au_mesh is not read.
+template <bool FUSED>
 __global__ __launch_bounds__(256) void schwarz_cg_init_kernel(const VirtDesc* __restrict__ vd, const int* __restrict__ sub_first,
-                                                              const double* __restrict__ r_mesh, double* __restrict__ du,
+                                                              const double* __restrict__ r_mesh, const double* __restrict__ Au_mesh,
+                                                              double* __restrict__ du,
                                                               double* __restrict__ r, double* __restrict__ d,
                                                               double* __restrict__ delta, double* __restrict__ tol, int* __restrict__ active,
                                                               int* __restrict__ final_iter, int* __restrict__ n_active, int iter,
@@ -144,7 +153,9 @@ __global__ __launch_bounds__(256) void schwarz_cg_init_kernel(const VirtDesc* __
     const int n3 = q.N * q.N * q.N;
     for (int n = threadIdx.x; n < n3; n += blockDim.x) {
       int i, j, k;
-      const double val = in_overlap(q, n, i, j, k) ? r_mesh[q.src + n] : 0.0;
+      double val = 0.0;
+      if (in_overlap(q, n, i, j, k))
+        val = FUSED ? __dadd_rn(r_mesh[q.src + n], __dmul_rn(-1.0, Au_mesh[q.src + n])) : r_mesh[q.src + n];
       du[q.dst + n] = 0.0;
       r[q.dst + n] = val;
       d[q.dst + n] = val;
@@ -271,7 +282,10 @@ __global__ __launch_bounds__(256) void schwarz_cg_flat_kernel(const int* __restr
   }
 }
 
-// u += sum over the subdomains containing the element of (hat weights * du), in ascending subdomain order; one workgroup per mesh element
+// u += sum over the subdomains containing the element of (hat weights * du), in ascending subdomain order; one workgroup per mesh element.
+// STORE: u = that sum, for a start vector that is zero (d4est_krylov_pc_schwarz.c:69): the additions start from 0.0 instead of the
+// value read, which is what the add form computes on a zero-filled u, bit for bit, without the fill and without the read.
+template <bool STORE>
 __global__ __launch_bounds__(256) void schwarz_correction_kernel(const VirtDesc* __restrict__ vd, const int* __restrict__ mesh_first,
                                                                  const int* __restrict__ mesh_contrib,
                                                                  const int* __restrict__ mesh_stride, const int* __restrict__ mesh_N,
@@ -280,7 +294,7 @@ __global__ __launch_bounds__(256) void schwarz_correction_kernel(const VirtDesc*
   for (int e = blockIdx.x; e < n_mesh; e += gridDim.x) {
     const int N = mesh_N[e], n3 = N * N * N, c0 = mesh_first[e], c1 = mesh_first[e + 1];
     for (int n = threadIdx.x; n < n3; n += blockDim.x) {
-      double acc = u[mesh_stride[e] + n];
+      double acc = STORE ? 0.0 : u[mesh_stride[e] + n];
       for (int c = c0; c < c1; ++c) {
         const VirtDesc q = vd[mesh_contrib[c]];
         int i, j, k;
@@ -604,6 +618,7 @@ d4est_hip_schwarz_t* d4est_hip_schwarz_create(d4est_hip_plan_t* subdomain_plan, 
   sz->n_mesh = n_mesh_elements;
   sz->overlap = num_nodes_overlap;
   sz->nodal_size = subdomain_plan->local_nodes;
+  sz->fused_residual = std::getenv("D4EST_HIP_SCHWARZ_FUSED_RESIDUAL") != nullptr && std::getenv("D4EST_HIP_SCHWARZ_UNFUSED_RESIDUAL") == nullptr;
   // hat weights per degree: [left ramp | right ramp | core], d4est_solver_schwarz_operators.c:78-105
   const int rs = num_nodes_overlap;
   std::vector<int> wtab(Tables1D::kMaxDeg + 2, -1);
@@ -742,24 +757,41 @@ void d4est_hip_schwarz_apply_over_subdomains(d4est_hip_schwarz_t* sz, const doub
 void d4est_hip_schwarz_add_correction(d4est_hip_schwarz_t* sz, const double* du_dev, double* u_dev) {
   check_schwarz(sz, "schwarz_add_correction");
   if (sz->n_mesh == 0) return;
-  hipLaunchKernelGGL(schwarz_correction_kernel, dim3(std::min(sz->n_mesh, 65536)), dim3(256), 0, sz->plan->stream, sz->d_vd,
+  hipLaunchKernelGGL(schwarz_correction_kernel<false>, dim3(std::min(sz->n_mesh, 65536)), dim3(256), 0, sz->plan->stream, sz->d_vd,
                      sz->d_mesh_first, sz->d_mesh_contrib, sz->d_mesh_stride, sz->d_mesh_N, sz->n_mesh, sz->d_weights, du_dev, u_dev);
   HIP_CHECK(hipGetLastError());
 }
 
-int d4est_hip_schwarz_iterate(d4est_hip_schwarz_t* sz, double* u_dev, const double* r_dev, int subdomain_iter, double subdomain_atol,
-                              double subdomain_rtol) {
-  check_schwarz(sz, "schwarz_iterate");
-  // d4est_solver_schwarz_subdomain_solver_cg.c:86-92
-  if (subdomain_iter <= 0 || !(subdomain_rtol > 0) || !(subdomain_atol > 0)) D4EST_HIP_ABORT("schwarz_iterate: some subdomain solver options are <= 0");
-  if (sz->n_sub == 0) return 0;
+// u = sum of the weighted corrections (the start vector is zero and is neither filled nor read)
+static void store_correction(d4est_hip_schwarz_t* sz, const double* du_dev, double* u_dev) {
+  if (sz->n_mesh == 0) return;
+  hipLaunchKernelGGL(schwarz_correction_kernel<true>, dim3(std::min(sz->n_mesh, 65536)), dim3(256), 0, sz->plan->stream, sz->d_vd,
+                     sz->d_mesh_first, sz->d_mesh_contrib, sz->d_mesh_stride, sz->d_mesh_N, sz->n_mesh, sz->d_weights, du_dev, u_dev);
+  HIP_CHECK(hipGetLastError());
+}
+
+// d4est_solver_schwarz_iterate.  Au_dev == nullptr: r_dev is the residual.  Au_dev != nullptr: r_dev is the right-hand side and the
+// residual r_dev - Au_dev is formed in the CG start.  store: u = correction (zero start vector, not read).  read_sweeps: the blocking
+// read of the sweep counter at the end (the public entry's return value); without it the function returns -1 and the counters stay on
+// the device for d4est_hip_schwarz_get_info.
+static int iterate_body(d4est_hip_schwarz_t* sz, double* u_dev, const double* r_dev, const double* Au_dev, int subdomain_iter,
+                        double subdomain_atol, double subdomain_rtol, bool store, bool read_sweeps) {
+  if (sz->n_sub == 0) {
+    if (store && sz->mesh_nodes > 0) HIP_CHECK(hipMemsetAsync(u_dev, 0, (size_t)sz->mesh_nodes * sizeof(double), sz->plan->stream));
+    return read_sweeps ? 0 : -1;
+  }
   ensure_workspace(sz);
   ensure_zero_ghost(sz);
   hipStream_t st = sz->plan->stream;
   HIP_CHECK(hipMemsetAsync(sz->d_n_active, 0, 2 * sizeof(int), st));
-  hipLaunchKernelGGL(schwarz_cg_init_kernel, dim3(sz->n_sub), dim3(256), 0, st, sz->d_vd, sz->d_sub_first, r_dev, sz->d_du, sz->d_r,
-                     sz->d_d, sz->d_delta, sz->d_tol, sz->d_active, sz->d_final_iter, sz->d_n_active, subdomain_iter, subdomain_atol,
-                     subdomain_rtol);
+  if (Au_dev)
+    hipLaunchKernelGGL(schwarz_cg_init_kernel<true>, dim3(sz->n_sub), dim3(256), 0, st, sz->d_vd, sz->d_sub_first, r_dev, Au_dev, sz->d_du,
+                       sz->d_r, sz->d_d, sz->d_delta, sz->d_tol, sz->d_active, sz->d_final_iter, sz->d_n_active, subdomain_iter,
+                       subdomain_atol, subdomain_rtol);
+  else
+    hipLaunchKernelGGL(schwarz_cg_init_kernel<false>, dim3(sz->n_sub), dim3(256), 0, st, sz->d_vd, sz->d_sub_first, r_dev,
+                       (const double*)nullptr, sz->d_du, sz->d_r, sz->d_d, sz->d_delta, sz->d_tol, sz->d_active, sz->d_final_iter,
+                       sz->d_n_active, subdomain_iter, subdomain_atol, subdomain_rtol);
   HIP_CHECK(hipGetLastError());
   // A subdomain that has met its tolerance is frozen on the device (its workgroup returns at once), so sweeps past the point where
   // the reference's loops have all broken are no-ops: the host looks at the "still iterating" counter only before the first sweep
@@ -783,11 +815,21 @@ int d4est_hip_schwarz_iterate(d4est_hip_schwarz_t* sz, double* u_dev, const doub
                          sz->d_Ad, sz->d_delta, sz->d_tol, sz->d_active, sz->d_final_iter, sz->d_n_active, it);
     HIP_CHECK(hipGetLastError());
   }
-  d4est_hip_schwarz_add_correction(sz, sz->d_du, u_dev);
+  if (store) store_correction(sz, sz->d_du, u_dev);
+  else d4est_hip_schwarz_add_correction(sz, sz->d_du, u_dev);
+  if (!read_sweeps) return -1;   // the smoother discards the count: no synchronisation at the end
   int counters[2] = {0, 0};
   HIP_CHECK(hipMemcpyAsync(counters, sz->d_n_active, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
   return counters[1];
+}
+
+int d4est_hip_schwarz_iterate(d4est_hip_schwarz_t* sz, double* u_dev, const double* r_dev, int subdomain_iter, double subdomain_atol,
+                              double subdomain_rtol) {
+  check_schwarz(sz, "schwarz_iterate");
+  // d4est_solver_schwarz_subdomain_solver_cg.c:86-92
+  if (subdomain_iter <= 0 || !(subdomain_rtol > 0) || !(subdomain_atol > 0)) D4EST_HIP_ABORT("schwarz_iterate: some subdomain solver options are <= 0");
+  return iterate_body(sz, u_dev, r_dev, nullptr, subdomain_iter, subdomain_atol, subdomain_rtol, false, true);
 }
 
 void d4est_hip_schwarz_smooth(d4est_hip_schwarz_t* sz, d4est_hip_plan_t* mesh_plan, double* u_dev, const double* rhs_dev, double* r_dev,
@@ -818,3 +860,71 @@ void d4est_hip_schwarz_get_info(d4est_hip_schwarz_t* sz, int* final_iter_host, d
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// The smoother loop as the V-cycle object and the Schwarz preconditioner run it (d4est_hip_multigrid.hip, d4est_hip_pc.hip): the
+// handle's layout is private to this file, so the two loops live here.  Both differ from the public d4est_hip_schwarz_smooth /
+// _iterate in two ways that change no number: no iterate ends with a blocking read of the sweep counters, and -- for a handle created
+// under D4EST_HIP_SCHWARZ_FUSED_RESIDUAL=1 -- the residual of the intermediate iterations is formed inside the CG start.
+// ---------------------------------------------------------------------------
+namespace d4est_hip {
+
+int schwarz_smoother_check(const d4est_hip_schwarz* sz, const d4est_hip_plan* mesh_plan) {
+  if (!sz || !sz->plan || !mesh_plan) return 1;
+  if (mesh_plan->n_ghost > 0 || !mesh_plan->has_faces) return 4;   // (first: no handle makes such a plan acceptable)
+  if (mesh_plan->local_nodes != sz->mesh_nodes) return 2;
+  if (mesh_plan->stream != sz->plan->stream) return 3;
+  return 0;
+}
+
+bool schwarz_fused_residual(const d4est_hip_schwarz* sz) { return sz->fused_residual; }
+
+// d4est_solver_multigrid_smoother_schwarz (src/Solver/d4est_solver_multigrid_smoother_schwarz.c:89-204).  As in the reference
+// (vecs->Au = r, :112-113, :154-155) r is the operator's output vector, so the cycle's own Au is not touched.
+void schwarz_smoother_run(d4est_hip_schwarz* sz, d4est_hip_plan* mesh_plan, double* u, const double* rhs, double* r,
+                          int smoother_iterations, int subdomain_iter, double subdomain_atol, double subdomain_rtol) {
+  const int code = schwarz_smoother_check(sz, mesh_plan);
+  if (code != 0) D4EST_HIP_ABORT("schwarz smoother: the handle and the level's plan no longer match (code %d)", code);
+  const int n = mesh_plan->local_nodes;
+  for (int i = 0; i < smoother_iterations; ++i) {                                   // :110
+    apply_operator(mesh_plan, u, r);                                                // :112-126 (Au = r)
+    if (sz->fused_residual) {
+      // :128 (r = rhs - r) node by node inside the CG start, :136-146
+      iterate_body(sz, u, rhs, r, subdomain_iter, subdomain_atol, subdomain_rtol, false, false);
+    } else {
+      launch_residual_inplace(mesh_plan, n, rhs, r);                                // :128
+      iterate_body(sz, u, r, nullptr, subdomain_iter, subdomain_atol, subdomain_rtol, false, false);   // :136-146
+    }
+  }
+  apply_operator(mesh_plan, u, r);                                                  // :154-168
+  launch_residual_inplace(mesh_plan, n, rhs, r);                                    // :196
+}
+
+// d4est_krylov_pc_schwarz_apply (src/Solver/d4est_krylov_pc_schwarz.c:59-116): z = 0 (:69), then `iterations` times { Au = A z (:83-94),
+// residual = rhs - Au (:97), schwarz_iterate(z, residual) (:99-110) }.  In the first pass z is zero: on a plan with homogeneous boundary
+// data A z is zero and the residual is rhs itself, so the pass is one iterate on rhs whose correction is STORED into z -- the fill, the
+// apply and the subtraction fall away and every number is the one the literal sequence gives.  (With inhomogeneous data on the plan
+// the operator is affine, A 0 != 0, and the literal sequence runs.)
+void schwarz_pc_run(d4est_hip_schwarz* sz, d4est_hip_plan* mesh_plan, const double* rhs, double* z, double* Au, double* residual,
+                    int iterations, int subdomain_iter, double subdomain_atol, double subdomain_rtol) {
+  const int code = schwarz_smoother_check(sz, mesh_plan);
+  if (code != 0) D4EST_HIP_ABORT("schwarz preconditioner: the handle and the plan no longer match (code %d)", code);
+  const int n = mesh_plan->local_nodes;
+  const bool zero_start = !mesh_plan->bc_inhomogeneous;
+  if (!zero_start || iterations <= 0) HIP_CHECK(hipMemsetAsync(z, 0, std::max<size_t>((size_t)n, 1) * sizeof(double), mesh_plan->stream));   // :69
+  for (int i = 0; i < iterations; ++i) {                                            // :81
+    if (i == 0 && zero_start) {
+      iterate_body(sz, z, rhs, nullptr, subdomain_iter, subdomain_atol, subdomain_rtol, true, false);
+      continue;
+    }
+    apply_operator(mesh_plan, z, Au);                                               // :83-94
+    if (sz->fused_residual) {
+      iterate_body(sz, z, rhs, Au, subdomain_iter, subdomain_atol, subdomain_rtol, false, false);       // :97, :99-110
+    } else {
+      launch_residual(mesh_plan, n, rhs, Au, residual);                             // :97
+      iterate_body(sz, z, residual, nullptr, subdomain_iter, subdomain_atol, subdomain_rtol, false, false);   // :99-110
+    }
+  }
+}
+
+}  // namespace d4est_hip

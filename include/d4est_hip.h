@@ -25,6 +25,7 @@ extern "C" {
 
 typedef struct d4est_hip_plan d4est_hip_plan_t;
 typedef struct d4est_hip_transfer d4est_hip_transfer_t;   /* hp-multigrid inter-grid transfer, see below */
+typedef struct d4est_hip_schwarz d4est_hip_schwarz_t;     /* additive Schwarz smoother, see below */
 typedef struct d4est_hip_amr d4est_hip_amr_t;             /* one rank's hp-AMR bookkeeping, see below */
 
 /* quadrature types (reference: [quadrature] name = legendre | lobatto,
@@ -827,10 +828,12 @@ void d4est_hip_transfer_galerkin_blocks(d4est_hip_transfer_t* t, const double* f
  * reference's *_at0 arrays with stride_to_fine_data.  It aborts, with the message of the code, unless d4est_hip_multigrid_check
  * returns 0: 1 n_levels < 2 (the reference's abort at :1435-1438), 2 a NULL entry, 3 a transfer whose coarse / fine node counts are not
  * those of its two plans.
- * Not part of the object: the Schwarz smoother slot (d4est_hip_schwarz_smooth has the per-level smoother's contract, r = rhs - A u on
- * exit, and can go behind the same internal interface), the reuse_smoother and PETSc bottom solvers, the reference-named compat entry
- * points, hierarchies coarsened across ranks (every level's hooks are simply used).  The object never changes a plan's tuning: a
- * caller may set D4EST_HIP_TUNE_GRAPH (key 9) on launch-bound coarse plans itself. */
+ * The smoother is the Chebyshev driver or the Schwarz smoother (d4est_solver_multigrid_smoother_schwarz.c:89-204, the caller's Schwarz
+ * handle per level); the bottom solver is CG, Chebyshev or reuse_smoother (d4est_solver_multigrid_bottom_solver_reuse_smoother.c:20-39).
+ * Not part of the object: the Schwarz smoother on plans with ghost sides (the whole-element exchanges around an iterate are the
+ * host's), the PETSc bottom solver, the reference-named compat entry points, hierarchies coarsened across ranks (every level's hooks
+ * are simply used).  The object never changes a plan's tuning: a caller may set D4EST_HIP_TUNE_GRAPH (key 9) on launch-bound coarse
+ * plans itself. */
 typedef struct d4est_hip_multigrid d4est_hip_multigrid_t;
 int d4est_hip_multigrid_check(int n_levels, d4est_hip_plan_t* const* plans, d4est_hip_transfer_t* const* transfers);
 d4est_hip_multigrid_t* d4est_hip_multigrid_create(int n_levels, d4est_hip_plan_t* const* plans, d4est_hip_transfer_t* const* transfers);
@@ -848,12 +851,35 @@ void d4est_hip_multigrid_set_stream(d4est_hip_multigrid_t* mg, void* hip_stream)
 int d4est_hip_multigrid_set_smoother_cheby(d4est_hip_multigrid_t* mg, int cheby_imax, int cheby_eigs_cg_imax, double cheby_eigs_lmax_lmin_ratio,
                                            double cheby_eigs_max_multiplier, int cheby_eigs_reuse_fromdownvcycle,
                                            int cheby_eigs_reuse_fromlastvcycle, int cheby_use_new_cg_eigs, int cheby_use_zero_guess_for_eigs);
+/* [mg_smoother_schwarz] smoother_iterations and the three [d4est_solver_schwarz] CG options (as d4est_hip_schwarz_smooth takes them).
+ * schwarz_on_level[l] (n_levels entries) is the caller's Schwarz handle for plans[l], built as for d4est_hip_schwarz_smooth; it stays
+ * the caller's and must outlive the object.  Entry 0 may be NULL unless the reuse_smoother bottom solver is selected.  Per smoother
+ * call: smoother_iterations times { r = rhs - A u; schwarz_iterate(u, r) }, then r = rhs - A u; r is the operator's output vector as
+ * in the reference (vecs->Au = r), the cycle's Au is left alone.  Inside this loop no iterate ends with a host read; what remains is
+ * the look at the "still iterating" counter before the first and then every 8th subdomain sweep.  Environment
+ * D4EST_HIP_SCHWARZ_FUSED_RESIDUAL=1, read when the Schwarz handle is created, forms the residual of the intermediate iterations in
+ * the subdomain CG's start kernel instead of writing it to r first (same numbers, bit for bit; off by default because it measured no
+ * faster; D4EST_HIP_SCHWARZ_UNFUSED_RESIDUAL=1 forces the two kernels).
+ * d4est_hip_schwarz_get_info works after a cycle.  The smoother has no eigenvalue state: d4est_hip_multigrid_get_info reports -1.
+ * Returns 0, or -- leaving the object without a smoother -- 1 for a NULL entry on a level >= 1, 2 for a handle whose mesh node count is
+ * not plans[l]'s, 3 for a handle whose subdomain plan is not on the hierarchy's stream, 4 for a plan with ghost sides (or without
+ * faces), 5 for subdomain options <= 0 (d4est_solver_schwarz_subdomain_solver_cg.c:86-92) or a negative smoother_iterations. */
+int d4est_hip_multigrid_set_smoother_schwarz(d4est_hip_multigrid_t* mg, d4est_hip_schwarz_t* const* schwarz_on_level, int smoother_iterations,
+                                             int subdomain_iter, double subdomain_atol, double subdomain_rtol);
+/* One call of the current smoother on one level, as the V-cycle makes it: smooth A_level u = rhs, r = rhs - A u of the final iterate on
+ * exit (u, rhs, Au, r: device vectors of plans[level]'s local_nodes; Au is work).  For a host that drives its own cycle and for tests. */
+void d4est_hip_multigrid_smooth_level(d4est_hip_multigrid_t* mg, int level, double* u_dev, const double* rhs_dev, double* Au_dev,
+                                      double* r_dev);
+/* [mg_bottom_solver_reuse_smoother]: the bottom solve is the current smoother on level 0 (smoother->smooth(..., r, 0)).  The Chebyshev
+ * smoother takes eigs[0] by its own rules (eigs_compute as PRE_V left it); the Schwarz smoother needs schwarz_on_level[0]. */
+void d4est_hip_multigrid_set_bottom_solver_reuse_smoother(d4est_hip_multigrid_t* mg);
 /* [mg_bottom_solver_cg]: d4est_hip_cg_solve on plans[0] from err = 0 */
 void d4est_hip_multigrid_set_bottom_solver_cg(d4est_hip_multigrid_t* mg, int bottom_imax, double bottom_atol, double bottom_rtol);
 /* [mg_bottom_solver_cheby]: cg_eigs from the current iterate on every call, the multiplier, cheby_imax iterations */
 void d4est_hip_multigrid_set_bottom_solver_cheby(d4est_hip_multigrid_t* mg, int cheby_imax, int cheby_eigs_cg_imax, double lmax_lmin_ratio,
                                                  double max_multiplier, int use_new_cg_eigs);
-/* 1 once a smoother and a bottom solver are set, else 0; vcycle / solve / pc_apply abort while it is 0 */
+/* 1 once a smoother and a bottom solver are set (reuse_smoother: and the smoother covers level 0), else 0; vcycle / solve / pc_apply
+ * abort while it is 0 */
 int d4est_hip_multigrid_ready(const d4est_hip_multigrid_t* mg);
 /* One V-cycle on A u = rhs (device vectors of the top level's local_nodes; Au is work, left as the last smoother call leaves it).
  * vcycle_index is vcycle_num_finished as the eigenvalue-reuse rules see it.  Down, level = top ... 1: err = 0, smooth (u, rhs, Au) on
@@ -875,9 +901,10 @@ int d4est_hip_multigrid_solve(d4est_hip_multigrid_t* mg, double* u_dev, const do
  * A d4est host binds d4est_krylov_pc_t.pc_apply to it; d4est_hip_fcg_solve takes it as pc with pc_ctx = the object. */
 void d4est_hip_multigrid_set_pc(d4est_hip_multigrid_t* mg, int vcycle_imax, double vcycle_atol, double vcycle_rtol);
 void d4est_hip_multigrid_pc_apply(void* mg, const double* r_dev, double* z_dev);
-/* eigs_host[n_levels]: the spectral bound last used per level, after the multiplier (-1: none yet; level 0 is never smoothed and holds
- * the bottom Chebyshev solver's bound when that solver is set); the V-cycles of the last solve; the bottom solver's iterations in the
- * last cycle (CG: iterations made; Chebyshev: cheby_imax).  Any output may be NULL. */
+/* eigs_host[n_levels]: the spectral bound last used per level, after the multiplier (-1: none yet, and on every level with the
+ * Schwarz smoother; level 0 holds the bottom Chebyshev solver's bound when that solver is set, the smoother's own under
+ * reuse_smoother); the V-cycles of the last solve; the bottom solver's iterations in the last cycle (CG: iterations made; Chebyshev:
+ * cheby_imax; reuse_smoother: 0).  Any output may be NULL. */
 void d4est_hip_multigrid_get_info(const d4est_hip_multigrid_t* mg, double* eigs_host, int* vcycles, int* bottom_iterations);
 
 /* ---- additive Schwarz smoother ------------------------------------------------------------
@@ -900,7 +927,6 @@ void d4est_hip_multigrid_get_info(const d4est_hip_multigrid_t* mg, double* eigs_
  * Several ranks: the mesh handed over is the rank's EXTENDED mesh (own elements followed by the ghost layer, P4EST_CONNECT_FULL), subdomains
  * exist for the own elements only; the residual of the ghost-layer elements arrives by a whole-element exchange before schwarz_iterate and
  * their part of u (the corrections) is sent back to the owners afterwards (disco4est_amd/schwarz.py: SchwarzShard, parallel.ElementSchedule). */
-typedef struct d4est_hip_schwarz d4est_hip_schwarz_t;
 d4est_hip_schwarz_t* d4est_hip_schwarz_create(d4est_hip_plan_t* subdomain_plan, int n_subdomains, const int* sub_first,
                                               const int* sub_elem, const int* sub_faces, const int* sub_core_faces,
                                               int num_nodes_overlap, int n_mesh_elements, const int* mesh_deg,
@@ -935,6 +961,35 @@ void d4est_hip_schwarz_smooth(d4est_hip_schwarz_t* sz, d4est_hip_plan_t* mesh_pl
                               int smoother_iterations, int subdomain_iter, double subdomain_atol, double subdomain_rtol);
 /* schwarz->subdomain_solve_iterations / _residuals of the last iterate (d4est_solver_schwarz.c:259-260), host arrays of n_subdomains */
 void d4est_hip_schwarz_get_info(d4est_hip_schwarz_t* sz, int* final_iter_host, double* final_res_host);
+
+/* ---- the Chebyshev and Schwarz Krylov preconditioners (csrc/d4est_hip_pc.hip) --------------------------------------------------------
+ * d4est_krylov_pc_cheby_apply (src/Solver/d4est_krylov_pc_cheby.c:92-171) and d4est_krylov_pc_schwarz_apply
+ * (src/Solver/d4est_krylov_pc_schwarz.c:59-116) as d4est_hip_pc_fn: pass _apply as pc and the object as pc_ctx to d4est_hip_fcg_solve or
+ * d4est_hip_newton_solve; a d4est host binds d4est_krylov_pc_t.pc_apply to them.  Both run on the plan's stream; their scratch vectors
+ * are allocated at create, nothing per apply.  The plan (and the Schwarz handle) stay the caller's and must outlive the object.
+ *
+ * Chebyshev, the [d4est_krylov_pc_cheby] keys: z = 0; when !cheby_reuse_eig or no bound is held (eig == -1), cg_eigs runs
+ * cheby_eigs_cg_imax iterations from z, WHICH IT ADVANCES (with cheby_use_zero_guess_for_eigs from a zero scratch vector, z stays zero)
+ * and eig = bound * cheby_eigs_max_multiplier; then cheby_imax iterations on [eig / cheby_eigs_lmax_lmin_ratio, eig] without a final
+ * residual.  _eig returns the bound held (-1: none) and, optionally, how many cg_eigs runs the object has made; _reset_eig drops the
+ * bound (after the operator changed: a new linearisation). */
+typedef struct d4est_hip_pc_cheby d4est_hip_pc_cheby_t;
+d4est_hip_pc_cheby_t* d4est_hip_pc_cheby_create(d4est_hip_plan_t* plan, int cheby_imax, int cheby_eigs_cg_imax, double cheby_eigs_lmax_lmin_ratio,
+                                                double cheby_eigs_max_multiplier, int cheby_reuse_eig, int cheby_use_new_cg_eigs,
+                                                int cheby_use_zero_guess_for_eigs);
+void d4est_hip_pc_cheby_destroy(d4est_hip_pc_cheby_t* pc);
+void d4est_hip_pc_cheby_apply(void* pc, const double* r_dev, double* z_dev);
+double d4est_hip_pc_cheby_eig(const d4est_hip_pc_cheby_t* pc, int* cg_eigs_runs);
+void d4est_hip_pc_cheby_reset_eig(d4est_hip_pc_cheby_t* pc);
+/* Schwarz, [schwarz_pc] schwarz_pc_iterations and the three [d4est_solver_schwarz] CG options: z = 0, then schwarz_pc_iterations times
+ * { residual = r - A z; schwarz_iterate(z, residual) }.  In the first pass z is zero, so on a plan with homogeneous boundary data the
+ * residual is r itself and the correction is stored into z (no fill, no apply, no read of z; the same numbers).  mesh_plan is the
+ * plan of the mesh itself, as for d4est_hip_schwarz_smooth: one rank, the subdomain plan's stream.  create aborts on a mismatch. */
+typedef struct d4est_hip_pc_schwarz d4est_hip_pc_schwarz_t;
+d4est_hip_pc_schwarz_t* d4est_hip_pc_schwarz_create(d4est_hip_schwarz_t* schwarz, d4est_hip_plan_t* mesh_plan, int schwarz_pc_iterations,
+                                                    int subdomain_iter, double subdomain_atol, double subdomain_rtol);
+void d4est_hip_pc_schwarz_destroy(d4est_hip_pc_schwarz_t* pc);
+void d4est_hip_pc_schwarz_apply(void* pc, const double* r_dev, double* z_dev);
 
 /* ---- the hp-AMR step (csrc/d4est_hip_amr.hip) ----------------------------------------------------------------------------------------
  * What d4est_amr_step (src/hpAMR/d4est_amr.c:852-1035) does between two solves, minus p4est's own work: the estimator statistics, the
