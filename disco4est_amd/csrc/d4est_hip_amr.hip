@@ -648,8 +648,7 @@ void d4est_hip_amr_interpolate_field(d4est_hip_amr_t* A, const double* field_old
     const int n3 = A->max_n * A->max_n * A->max_n;
     const size_t lds = (size_t)2 * n3 * sizeof(double);
     if (lds > 160 * 1024) D4EST_HIP_ABORT("amr_interpolate_field: degree %d too high for the LDS-resident kernel", A->max_n - 1);
-    if (lds > 64 * 1024)
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(amr_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    set_lds_limit(amr_generic_kernel, lds);
     hipLaunchKernelGGL(amr_generic_kernel, dim3(std::min(L.n, 65536)), dim3(256), lds, A->stream, field_old_dev, field_new_dev, A->d_aux_rec,
                        A->d_aux_src, A->d_out_off, A->d_out_ops, A->d_opsT, list, L.n, n3);
   }

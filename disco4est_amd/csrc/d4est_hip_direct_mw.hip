@@ -571,15 +571,11 @@ bool launch_direct_mw_hi(d4est_hip_plan* plan, DirectHost* dh, const double* u, 
 #define D4EST_HIP_MW_LAUNCHER bool launch_direct_mw_hi
 #endif
 
-// the dynamic-LDS attribute of a kernel instance is set ONCE (a static flag per instantiation of this template), not at every launch:
-// the launch sits in the hot path of a Chebyshev iteration / a Schwarz CG sweep, and inside hipGraph capture regions
-template <typename K, K Kernel>
-static void mw_set_lds_limit_once(size_t bytes) {
-  static bool done = false;
-  if (done) return;
-  if (bytes > 48 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  done = true;
-}
+// the dynamic-LDS attribute of a kernel instance is set ONCE (set_lds_limit), not at every launch: the launch sits in the hot path of a
+// Chebyshev iteration / a Schwarz CG sweep, and inside hipGraph capture regions.  This unit asks from 48 KB on, as it always did:
+// MwCfg<15>::LDS_BYTES = 54 000 lies between that and the helper's 64 KB.
+constexpr size_t kMwLdsAskFrom = 48 * 1024;
+static_assert(MwCfg<15>::LDS_BYTES > kMwLdsAskFrom && MwCfg<15>::LDS_BYTES <= 64 * 1024, "the one size the 48 KB threshold is kept for");
 
 // vmode: VOL of operator_mw_kernel; + 8 (stream mode, plan->stream_mode) exists for the whole operator with the streamed metric (1 -> 9)
 D4EST_HIP_MW_LAUNCHER(d4est_hip_plan* plan, DirectHost* dh, const double* u, const double* ghost_trace, double* Au, const DirectFuse* cf,
@@ -589,7 +585,7 @@ D4EST_HIP_MW_LAUNCHER(d4est_hip_plan* plan, DirectHost* dh, const double* u, con
   if (vmode == 1 && vol.stream) vmode = 9;
 #define D4EST_HIP_MW_GO(N_, FUSE_, VOL_)                                                                                          \
   do {                                                                                                                             \
-    mw_set_lds_limit_once<decltype(&operator_mw_kernel<N_, FUSE_, VOL_>), &operator_mw_kernel<N_, FUSE_, VOL_>>(MwCfg<N_>::LDS_BYTES);  \
+    set_lds_limit(operator_mw_kernel<N_, FUSE_, VOL_>, MwCfg<N_>::LDS_BYTES, kMwLdsAskFrom);                                      \
     hipLaunchKernelGGL((operator_mw_kernel<N_, FUSE_, VOL_>), dim3(n), dim3(MwCfg<N_>::THREADS), MwCfg<N_>::LDS_BYTES, plan->stream, \
                        u, ghost_trace, Au, dh->d_sides, dh->d_ghost_off, dh->d_ops, plan->d_face_geom, plan->d_bndry, robin_c,     \
                        robin_r, n, dh->ns0, dh->ns_stride, chunk, cfv, vol, dh->d_list);                                           \

@@ -292,8 +292,7 @@ void estimator_setup(d4est_hip_plan* plan, const double* sj, const double* n, co
   // the residual kernel's LDS beyond the default 64 KB: raised once here, for the plan's largest bucket (at most 160 KB: see estimator_compute)
   size_t lds = 0;
   for (const Bucket& bk : plan->buckets) lds = std::max(lds, residual_lds_bytes(bk.N, bk.NQ));
-  if (lds > 64 * 1024 && lds <= 160 * 1024)
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(est_residual_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (lds <= 160 * 1024) set_lds_limit(est_residual_kernel, lds);
   HIP_CHECK(hipStreamSynchronize(plan->stream));   // (set-up: the caller's factor arrays may be freed after it)
   HIP_CHECK(hipFree(d_wt));
 }

@@ -3394,10 +3394,6 @@ static int xcd_chunk(const int* elist, int n, int grid) {
   static const bool no_remap = std::getenv("D4EST_HIP_NO_XCD_REMAP") != nullptr;
   return (!elist && n % 8 == 0 && grid % 8 == 0 && !no_remap) ? n / 8 : 0;
 }
-template <typename K>
-static void allow_lds(K kern, size_t lds) {
-  if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-}
 static const double* robin_c_of(const FaceHost& fh) { return fh.robin ? fh.d_robin_c : nullptr; }
 static const double* robin_r_of(const FaceHost& fh) { return fh.robin ? fh.d_robin_r : nullptr; }
 
@@ -3421,7 +3417,7 @@ static void run_trace_wave(d4est_hip_plan* plan, const FaceHost& fh, const doubl
 // the copy of u is sized by the largest LOCAL degree (cached at set-up: no per-launch walk over the elements)
 static void run_trace_mfma16(d4est_hip_plan* plan, const FaceHost& fh, const double* u, double* trace, int n, const int* elist) {
   const size_t lds = (size_t)(fh.max_local_N * 272 + 3 * 2 * 16 * 34) * sizeof(double);
-  allow_lds(trace_mfma16_kernel, lds);
+  set_lds_limit(trace_mfma16_kernel, lds);
   const int per_cu = (int)std::min<size_t>(8, (160 * 1024) / lds);
   hipLaunchKernelGGL(trace_mfma16_kernel, dim3(std::min(n, per_cu * face_cus(plan))), dim3(192), lds, plan->stream, u, trace,
                      (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, n, fh.max_local_N, elist);
@@ -3445,19 +3441,19 @@ static void run_trace_unit(d4est_hip_plan* plan, const FaceHost& fh, const doubl
 // tiled record kernel, 4 workgroups per CU.  hang_only = 1: the hanging sides of the listed elements (hp split), 0: every side
 static void run_trace_hp_mfma16(d4est_hip_plan* plan, const FaceHost& fh, const double* u, double* trace, int n, const int* elist, int hang_only) {
   const size_t lds = (size_t)(fh.hp_max_N * 272 + 3 * 2 * 16 * 34) * sizeof(double);
-  allow_lds(trace_hp_mfma16_kernel, lds);
+  set_lds_limit(trace_hp_mfma16_kernel, lds);
   hipLaunchKernelGGL(trace_hp_mfma16_kernel, dim3(std::min(n, 4 * face_cus(plan))), dim3(192), lds, plan->stream, u, trace, fh.d_rec,
                      fh.d_side_first, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, n, fh.hp_max_N, elist, hang_only);
 }
 static void run_trace_hp_generic(d4est_hip_plan* plan, const FaceHost& fh, const double* u, double* trace, int n) {
   const size_t lds = fh.hp_lds_doubles * sizeof(double);
-  allow_lds(trace_hp_kernel, lds);
+  set_lds_limit(trace_hp_kernel, lds);
   hipLaunchKernelGGL(trace_hp_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, u, trace, fh.d_rec, fh.d_elem_first,
                      (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, n, fh.hp_fld_stride);
 }
 static void run_trace_generic(d4est_hip_plan* plan, const FaceHost& fh, const double* u, double* trace, int n) {
   const size_t lds = generic_lds_bytes(plan);
-  allow_lds(trace_generic_kernel, lds);
+  set_lds_limit(trace_generic_kernel, lds);
   hipLaunchKernelGGL(trace_generic_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, u, trace, (const SideDesc*)plan->d_side_desc,
                      (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, n, fh.fld_stride);
 }
@@ -3468,7 +3464,7 @@ void launch_traces(d4est_hip_plan* plan, const double* u, double* trace, bool gh
     if (fh.hp) D4EST_HIP_ABORT("compute_ghost_traces: plans with hanging faces take their ghost traces from the trace exchange (d4est_hip_plan_*_sub offsets), not from whole ghost elements");
     if (fh.n_ghost_sides == 0) return;
     const size_t lds = generic_lds_bytes(plan);
-    allow_lds(ghost_trace_kernel, lds);
+    set_lds_limit(ghost_trace_kernel, lds);
     hipLaunchKernelGGL(ghost_trace_kernel, dim3(std::min(fh.n_ghost_sides, 16384)), dim3(256), lds, plan->stream, u, trace,
                        fh.d_ghost_sides, plan->d_face_ops, fh.n_ghost_sides, fh.fld_stride);
     HIP_CHECK(hipGetLastError());
@@ -3581,14 +3577,14 @@ static void run_flux_hp_mfma16(d4est_hip_plan* plan, const FaceHost& fh, const d
 }
 static void run_flux_hp_generic(d4est_hip_plan* plan, const FaceHost& fh, const double* trace, const double* ghost_trace, double* Au, int n) {
   const size_t lds = fh.hp_lds_doubles * sizeof(double);
-  allow_lds(flux_hp_kernel, lds);
+  set_lds_limit(flux_hp_kernel, lds);
   hipLaunchKernelGGL(flux_hp_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, trace, ghost_trace, Au, fh.d_rec, fh.d_elem_first,
                      (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, plan->d_face_geom, plan->d_bndry, robin_c_of(fh),
                      robin_r_of(fh), n, fh.hp_fld_stride);
 }
 static void run_flux_generic(d4est_hip_plan* plan, const FaceHost& fh, const double* trace, const double* ghost_trace, double* Au, int n) {
   const size_t lds = generic_lds_bytes(plan);
-  allow_lds(flux_generic_kernel, lds);
+  set_lds_limit(flux_generic_kernel, lds);
   hipLaunchKernelGGL(flux_generic_kernel, dim3(std::min(n, 16384)), dim3(256), lds, plan->stream, trace, ghost_trace, Au,
                      (const SideDesc*)plan->d_side_desc, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, plan->d_face_geom, plan->d_bndry,
                      robin_c_of(fh), robin_r_of(fh), n, fh.fld_stride);

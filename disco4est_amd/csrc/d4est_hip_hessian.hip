@@ -280,10 +280,8 @@ static HessHost* hess_prepare(d4est_hip_plan* plan, const char* who) {
     if (bk.n_elem > 0) lds = std::max(lds, hess_lds_bytes(bk.N, bk.NQ));
   }
   // the apply kernel's LDS beyond the default 64 KB.  The attribute belongs to the kernel on the current device, not to a plan, so it
-  // is set to the one fixed limit, on every set-up that needs it: no state to keep, nothing a smaller plan could lower
-  if (lds > 64 * 1024)
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(hessian_trace_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)kHessMaxLds));
+  // is set to the one fixed limit: nothing a smaller plan could lower
+  if (lds > 64 * 1024) set_lds_limit(hessian_trace_kernel, kHessMaxLds);
   return x;
 }
 

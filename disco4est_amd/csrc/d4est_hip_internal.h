@@ -5,6 +5,9 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
+#include <mutex>
+#include <utility>
 #include <vector>
 
 #include "../../include/d4est_hip.h"
@@ -190,6 +193,50 @@ namespace d4est_hip {
 // D4EST_HIP_TUNE_STIFFNESS_WAVE values that select the even-odd single-wavefront kernels (and the kernels built on their body): auto, 11,
 // and 12 = the same kernels with the 16-product body where auto / 11 take the collocated-gradient body (deg_quad = deg)
 inline bool tune_wave_eo(int tw) { return tw < 0 || tw == 11 || tw == 12; }
+
+// Dynamic LDS beyond `threshold` (64 KB: what a kernel may use without asking): hipFuncSetAttribute(MaxDynamicSharedMemorySize), once per
+// (device, kernel) and only ever raised.  The attribute belongs to the kernel on the current device, not to a plan; a driver call per
+// launch would sit in the hot path of every smoother iteration, and inside hipGraph capture regions.
+inline void raise_lds_limit(const void* fn, size_t bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<int, const void*>, size_t> done;
+  int device = 0;
+  HIP_CHECK(hipGetDevice(&device));
+  std::lock_guard<std::mutex> lock(mu);
+  size_t& set = done[{device, fn}];
+  if (set >= bytes) return;
+  HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  set = bytes;
+}
+template <typename K>
+inline void set_lds_limit(K kernel, size_t bytes, size_t threshold = 64 * 1024) {
+  if (bytes > threshold) raise_lds_limit(reinterpret_cast<const void*>(kernel), bytes);
+}
+
+// Mixed-degree plans put several buckets into one launch; its argument struct M (WaveEoMulti, NonlinMulti) lists at most M::MAXB of the
+// plan's first 32 buckets (one bit each in `covered`).  multi_append adds bucket i with its `workgroups` -- the fields every such kernel
+// reads and the running workgroup prefix -- and returns false, nothing changed, where a limit is reached.
+inline bool bucket_single_wave(const Bucket& bk) { return bk.n_elem > 0 && bk.N == bk.NQ && bk.N >= 2 && bk.N <= 8; }   // deg_quad = deg <= 7
+template <class M>
+inline bool multi_append(M& A, unsigned& covered, size_t i, const Bucket& bk, int workgroups) {
+  if (A.n == M::MAXB || i >= 32) return false;
+  const int j = A.n++;
+  A.wg_end[j] = (j > 0 ? A.wg_end[j - 1] : 0) + workgroups;
+  A.N[j] = bk.N; A.n_elem[j] = bk.n_elem; A.elem_offset[j] = bk.elem_offset;
+  A.EBf[j] = bk.d_EBf; A.EBb[j] = bk.d_EBb; A.wq[j] = bk.d_w;
+  covered |= 1u << i;
+  return true;
+}
+template <class M>
+inline int multi_workgroups(const M& A) { return A.n > 0 ? A.wg_end[A.n - 1] : 0; }
+// ... and the per-bucket launches take the rest: f(bucket) for every non-empty bucket without a bit in `covered`
+template <class F>
+inline void for_each_uncovered_bucket(const d4est_hip_plan* plan, unsigned covered, F&& f) {
+  for (size_t i = 0; i < plan->buckets.size(); ++i) {
+    const Bucket& bk = plan->buckets[i];
+    if (bk.n_elem > 0 && !(i < 32 && ((covered >> i) & 1u))) f(bk);
+  }
+}
 
 // what every setter that changes the plan's state does first (drop_graph of d4est_hip_capi.hip, and the setters of the other units)
 inline void plan_operator_changed(d4est_hip_plan* plan) {

@@ -334,10 +334,6 @@ static void build_windows(d4est_hip_transfer* t) {
   HIP_CHECK(hipMemcpy(t->d_woff, woff.data(), woff.size() * sizeof(long long), hipMemcpyHostToDevice));
 }
 
-static void set_lds(const void* fn, size_t lds) {
-  if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-}
-
 }  // namespace d4est_hip
 
 using namespace d4est_hip;
@@ -368,7 +364,7 @@ void d4est_hip_compute_weighted_mass_blocks(d4est_hip_plan_t* plan, const double
     const int nm = std::max(bk.N, bk.NQ), n3max = nm * nm * nm, N3 = bk.N * bk.N * bk.N;
     const size_t lds = (size_t)2 * n3max * sizeof(double);
     if (lds > 160 * 1024) D4EST_HIP_ABORT("compute_weighted_mass_blocks: degree pair (%d, %d) exceeds the kernel's LDS", bk.deg, bk.deg_quad);
-    set_lds(reinterpret_cast<const void*>(mass_blocks_kernel), lds);
+    set_lds_limit(mass_blocks_kernel, lds);
     // enough workgroups to fill the chip, at most one per column
     int chunks = std::max(1, std::min(N3, (4096 + bk.n_elem - 1) / bk.n_elem));
     const int cols = (N3 + chunks - 1) / chunks;
@@ -391,14 +387,14 @@ void d4est_hip_transfer_galerkin_blocks(d4est_hip_transfer_t* t, const double* f
   if (!t->d_work) HIP_CHECK(hipMalloc(&t->d_work, std::max<size_t>((size_t)t->work_doubles, 1) * sizeof(double)));
   const int n3 = t->max_n * t->max_n * t->max_n;
   const size_t lds2 = (size_t)2 * n3 * sizeof(double);
-  set_lds(reinterpret_cast<const void*>(galerkin_rows_kernel), lds2);
+  set_lds_limit(galerkin_rows_kernel, lds2);
   const int per = std::max(1, std::min(n3, (4096 + t->n_children - 1) / t->n_children));   // chunks per child / item
   const int rows = (n3 + per - 1) / per;
   hipLaunchKernelGGL(galerkin_rows_kernel, dim3(t->n_children, (n3 + rows - 1) / rows), dim3(256), lds2, t->stream, fine_blocks_dev,
                      t->d_child, t->d_moff, t->d_ops, t->d_work, n3, rows);
   const int acc_in_lds = ((size_t)3 * n3 * sizeof(double) <= 160 * 1024) ? 1 : 0;
   const size_t lds3 = (size_t)(acc_in_lds ? 3 : 2) * n3 * sizeof(double);
-  set_lds(reinterpret_cast<const void*>(galerkin_cols_kernel), lds3);
+  set_lds_limit(galerkin_cols_kernel, lds3);
   const int per_i = std::max(1, std::min(n3, (4096 + t->n_items - 1) / t->n_items));
   const int cols = (n3 + per_i - 1) / per_i;
   hipLaunchKernelGGL(galerkin_cols_kernel, dim3(t->n_items, (n3 + cols - 1) / cols), dim3(256), lds3, t->stream, t->d_work, t->d_child,
@@ -406,7 +402,7 @@ void d4est_hip_transfer_galerkin_blocks(d4est_hip_transfer_t* t, const double* f
   if (literal_window) {
     build_windows(t);
     const size_t lds1 = (size_t)n3 * sizeof(double);
-    set_lds(reinterpret_cast<const void*>(galerkin_cols_window_kernel), lds1);
+    set_lds_limit(galerkin_cols_window_kernel, lds1);
     hipLaunchKernelGGL(galerkin_cols_window_kernel, dim3(t->n_items, (n3 + cols - 1) / cols), dim3(256), lds1, t->stream, t->d_work,
                        t->d_child, t->d_moff, t->d_coff, t->d_item_first, t->d_window, t->d_woff, coarse_blocks_dev, cols);
   }

@@ -18,8 +18,6 @@
 // The power is a product of |k| factors (k < 0: one division of 1 by the product); k is wave-uniform, the loop does not diverge.
 #include <algorithm>
 #include <cmath>
-#include <mutex>
-#include <unordered_map>
 
 #include "d4est_hip_internal.h"
 #include "d4est_hip_wave.h"
@@ -242,90 +240,43 @@ __global__ __launch_bounds__(256) void nonlin_negate_kernel(int n, double* __res
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) x[i] = -1. * x[i];
 }
 
-
-// the (deg + 1, deg_quad + 1) pairs with a compiled kernel: those of D4EST_HIP_FAST_PAIRS and D4EST_HIP_BIG_PAIRS, the coverage of
-// d4est_hip_apply_galerkin_integral's one-kernel path (d4est_hip_volume.hip)
-#define D4EST_HIP_NONLIN_PAIRS(X)                                                                                       \
-  X(2, 2) X(3, 3) X(4, 4) X(5, 5) X(6, 6) X(7, 7) X(8, 8) X(9, 9) X(10, 10) X(11, 11) X(12, 12) X(13, 13) X(14, 14)     \
-  X(15, 15) X(16, 16) X(2, 3) X(3, 4) X(4, 5) X(8, 9) X(3, 6) X(4, 6) X(8, 10) X(17, 17) X(18, 18) X(19, 19) X(20, 20)
-
-static bool pair_built(int N, int NQ) {
-#define X(N_, NQ_) if (N == N_ && NQ == NQ_) return WaveCfg<N_, NQ_>::LDS_BYTES <= 160 * 1024;
-  D4EST_HIP_NONLIN_PAIRS(X)
-#undef X
-  return false;
-}
-
+// every bucket has a compiled (deg + 1, deg_quad + 1) pair (pair_built, d4est_hip_wave.h: the coverage of
+// d4est_hip_apply_galerkin_integral's one-kernel path in d4est_hip_volume.hip)
 static bool plan_fused(const d4est_hip_plan* plan) {
   for (const Bucket& bk : plan->buckets)
     if (bk.n_elem > 0 && !pair_built(bk.N, bk.NQ)) return false;
   return true;
 }
 
-template <typename K>
-static void set_lds_limit(K kernel, size_t bytes) {   // once per kernel instance (no driver call in the hot path)
-  if (bytes <= 64 * 1024) return;
-  static std::mutex mu;
-  static std::unordered_map<const void*, size_t> done;
-  const void* key = reinterpret_cast<const void*>(kernel);
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = done.find(key);
-  if (it != done.end() && it->second >= bytes) return;
-  HIP_CHECK(hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  done[key] = bytes;
-}
-
 // every bucket of a plan for which plan_fused() holds
 template <bool COEFF>
 static void launch_fused(d4est_hip_plan* plan, const double* u, double* out, PowArgs P, double* c_out, double* wjc_out) {
   unsigned covered = 0u;
-  {
-    NonlinMulti A;
-    size_t lds = 0;
-    int wgs = 0;
-    for (size_t i = 0; i < plan->buckets.size() && i < 32; ++i) {
-      const Bucket& bk = plan->buckets[i];
-      if (bk.n_elem == 0 || bk.N != bk.NQ || bk.N < 2 || bk.N > 8 || A.n == NonlinMulti::MAXB) continue;
-      size_t l = 0;
-      int epb = 1;
-#define X(N_) if (bk.N == N_) { l = WaveCfg<N_, N_>::LDS_BYTES; epb = WaveCfg<N_, N_>::EPB; }
-      X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-#undef X
-      lds = std::max(lds, l);
-      wgs += (bk.n_elem + epb - 1) / epb;
-      const int j = A.n++;
-      A.wg_end[j] = wgs; A.N[j] = bk.N; A.n_elem[j] = bk.n_elem; A.elem_offset[j] = bk.elem_offset;
-      A.EBf[j] = bk.d_EBf; A.EBb[j] = bk.d_EBb; A.wq[j] = bk.d_w;
-      covered |= 1u << i;
-    }
-    if (A.n >= 2)
-      hipLaunchKernelGGL((nonlin_multi_kernel<COEFF>), dim3(wgs), dim3(64), lds, plan->stream, u, out, plan->d_J, plan->d_ns_list,
-                         plan->d_qs_list, P, c_out, wjc_out, A);
-    else
-      covered = 0u;
+  NonlinMulti A;   // mixed-degree plans: one launch for the deg_quad = deg <= 7 buckets
+  size_t lds = 0;
+  for (size_t i = 0; i < plan->buckets.size(); ++i) {
+    const Bucket& bk = plan->buckets[i];
+    if (!bucket_single_wave(bk)) continue;
+    const WaveCfgSquare w = wave_cfg_square(bk.N);
+    if (!multi_append(A, covered, i, bk, (bk.n_elem + w.epb - 1) / w.epb)) continue;
+    lds = std::max(lds, w.lds_bytes);
   }
-  size_t bucket_index = 0;
-  for (const Bucket& bk : plan->buckets) {
-    const size_t this_bucket = bucket_index++;
-    if (bk.n_elem == 0) continue;
-    if (this_bucket < 32 && ((covered >> this_bucket) & 1u)) continue;
-    bool done = false;
-#define X(N_, NQ_)                                                                                                          \
-  if (!done && bk.N == N_ && bk.NQ == NQ_) {                                                                                \
-    using C = WaveCfg<N_, NQ_>;                                                                                             \
-    if (C::LDS_BYTES <= 160 * 1024) {                                                                                       \
-      const int grid = (bk.n_elem + C::EPB - 1) / C::EPB;                                                                   \
-      set_lds_limit(nonlin_kernel<N_, NQ_, COEFF>, C::LDS_BYTES);                                                           \
-      hipLaunchKernelGGL((nonlin_kernel<N_, NQ_, COEFF>), dim3(grid), dim3(C::THREADS), C::LDS_BYTES, plan->stream, u, out, \
-                         plan->d_J, plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_EBb, \
-                         bk.d_EBf, bk.d_w, P, c_out, wjc_out);                                                              \
-      done = true;                                                                                                          \
-    }                                                                                                                       \
-  }
-    D4EST_HIP_NONLIN_PAIRS(X)
-#undef X
-    if (!done) D4EST_HIP_ABORT("nonlinear term: no kernel for (N, NQ) = (%d, %d)", bk.N, bk.NQ);   // plan_fused() excludes this
-  }
+  if (A.n >= 2)
+    hipLaunchKernelGGL((nonlin_multi_kernel<COEFF>), dim3(multi_workgroups(A)), dim3(64), lds, plan->stream, u, out, plan->d_J,
+                       plan->d_ns_list, plan->d_qs_list, P, c_out, wjc_out, A);
+  else
+    covered = 0u;
+  for_each_uncovered_bucket(plan, covered, [&](const Bucket& bk) {
+    const bool built = for_built_pair(bk.N, bk.NQ, [&](auto n, auto nq) {
+      constexpr int N = decltype(n)::value, NQ = decltype(nq)::value;
+      using C = WaveCfg<N, NQ>;
+      set_lds_limit(nonlin_kernel<N, NQ, COEFF>, C::LDS_BYTES);
+      hipLaunchKernelGGL((nonlin_kernel<N, NQ, COEFF>), dim3((bk.n_elem + C::EPB - 1) / C::EPB), dim3(C::THREADS), C::LDS_BYTES, plan->stream,
+                         u, out, plan->d_J, plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_EBb,
+                         bk.d_EBf, bk.d_w, P, c_out, wjc_out);
+    });
+    if (!built) D4EST_HIP_ABORT("nonlinear term: no kernel for (N, NQ) = (%d, %d)", bk.N, bk.NQ);   // plan_fused() excludes this
+  });
   HIP_CHECK(hipGetLastError());
 }
 

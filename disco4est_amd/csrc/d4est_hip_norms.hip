@@ -40,7 +40,6 @@
 //   norms_reduce_kernel    one 1024-thread workgroup: masked fixed-order sum (or maximum) of per-element arrays
 #include <algorithm>
 #include <cmath>
-#include <mutex>
 
 #include "d4est_hip_elem_l2.h"
 #include "d4est_hip_internal.h"
@@ -327,12 +326,8 @@ void norms_error(d4est_hip_plan* plan, const double* u, const double* u_compare,
 }
 
 // the two kernels below may need more dynamic LDS than the default 64 KB.  The attribute belongs to the kernel, not to a plan, so it is
-// raised ONCE per process, to the kernel's own limit (kElemL2MaxLds), the first time a bucket beyond 64 KB is launched: no runtime call
-// on the later launches, and no plan can lower what another plan needs.
-static void raise_lds_once(const void* kernel, std::once_flag& once) {
-  std::call_once(once, [kernel] { HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kElemL2MaxLds)); });
-}
-static std::once_flag g_l2_lds_once, g_gradient_lds_once;
+// raised once per device (set_lds_limit), to the kernel's own limit (kElemL2MaxLds), the first time a bucket beyond 64 KB is launched: no
+// runtime call on the later launches, and no plan can lower what another plan needs.
 
 void norms_l2_sqr(d4est_hip_plan* plan, const double* v, const int* skip, double* l2_array, double* sum) {
   if (!plan->has_geometry) D4EST_HIP_ABORT("norm_l2_sqr: the plan has no volume geometry (plan_set_geometry)");
@@ -343,7 +338,7 @@ void norms_l2_sqr(d4est_hip_plan* plan, const double* v, const int* skip, double
     if (bk.n_elem == 0) continue;
     const size_t lds = elem_l2_lds_bytes(bk.N, bk.NQ);
     if (lds > kElemL2MaxLds) D4EST_HIP_ABORT("norm_l2_sqr: (deg, deg_quad) = (%d, %d) needs %zu bytes of LDS", bk.deg, bk.deg_quad, lds);
-    if (lds > 64 * 1024) raise_lds_once(reinterpret_cast<const void*>(norms_l2_kernel), g_l2_lds_once);
+    if (lds > 64 * 1024) set_lds_limit(norms_l2_kernel, kElemL2MaxLds);
     hipLaunchKernelGGL(norms_l2_kernel, dim3(std::min(bk.n_elem, 16384)), dim3(256), lds, plan->stream, v, plan->d_J,
                        plan->d_elem_ids + bk.elem_offset, plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_B,
                        bk.d_w, bk.N, bk.NQ, arr);
@@ -391,7 +386,7 @@ void norms_ip_energy_sqr(d4est_hip_plan* plan, const double* v, const double* gh
       if (bk.n_elem == 0) continue;
       const size_t lds = gradient_lds_bytes(bk.N, bk.NQ);
       if (lds > kElemL2MaxLds) D4EST_HIP_ABORT("ip_energy_norm_sqr: (deg, deg_quad) = (%d, %d) needs %zu bytes of LDS", bk.deg, bk.deg_quad, lds);
-      if (lds > 64 * 1024) raise_lds_once(reinterpret_cast<const void*>(norms_gradient_kernel), g_gradient_lds_once);
+      if (lds > 64 * 1024) set_lds_limit(norms_gradient_kernel, kElemL2MaxLds);
       hipLaunchKernelGGL(norms_gradient_kernel, dim3(std::min(bk.n_elem, 16384)), dim3(256), lds, plan->stream, v, plan->d_metric,
                          plan->d_elem_ids + bk.elem_offset, plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_B,
                          bk.d_D, bk.N, bk.NQ, t);

@@ -390,11 +390,6 @@ __global__ __launch_bounds__((GalerkinCfg<NH, DMAX>::THREADS * GalerkinCfg<NH, D
   }
 }
 
-template <typename K>
-static void fast_lds_limit(K kernel, size_t bytes) {
-  if (bytes > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-}
-
 // child groups a restriction / Galerkin launch of one list runs with: the instance's CGMAX where the list alone does not fill the chip
 // (coarse levels); with thousands of coarse elements one group per element keeps more elements in flight (level 5, p = 3: 61 us against
 // 113 us with groups).  The ONE statement of the rule: the launches and d4est_hip_transfer_describe both call it.
@@ -406,7 +401,7 @@ template <int NH, int DMAX, bool ADD>
 static void go_prolong(d4est_hip_transfer* t, const double* xc, double* xf, const int* list, int n) {
   using C = TransferCfg<NH, DMAX>;
   const size_t lds = (size_t)C::LDS_PROLONG * sizeof(double);
-  fast_lds_limit(prolong_fast_kernel<NH, DMAX, ADD>, lds);
+  set_lds_limit(prolong_fast_kernel<NH, DMAX, ADD>, lds);
   hipLaunchKernelGGL((prolong_fast_kernel<NH, DMAX, ADD>), dim3(n), dim3(C::THREADS), lds, t->stream, xc, xf, t->d_child, t->d_off, t->d_opsT, list);
 }
 template <int NH, int DMAX>
@@ -415,7 +410,7 @@ static void go_restrict(d4est_hip_transfer* t, const double* xf, double* xc, con
   // child groups: as many of the item's children at once as the LDS (and 1024 threads) hold
   const int cg = child_groups(C::CGMAX, n_children, n);
   const size_t lds = (size_t)cg * C::LDS_RESTRICT * sizeof(double);
-  fast_lds_limit(restrict_fast_kernel<NH, DMAX>, lds);
+  set_lds_limit(restrict_fast_kernel<NH, DMAX>, lds);
   hipLaunchKernelGGL((restrict_fast_kernel<NH, DMAX>), dim3(n), dim3(C::THREADS * cg), lds, t->stream, xf, xc, t->d_child, t->d_off,
                      t->d_item_first, ops, list, cg);
 }
@@ -454,7 +449,7 @@ static void go_galerkin(d4est_hip_transfer* t, const double* u, double* Au, cons
   using C = GalerkinCfg<NH, DMAX>;
   const int cg = child_groups(C::CGMAX, n_children, n);
   const size_t lds = (size_t)cg * C::LDS * sizeof(double);
-  fast_lds_limit(galerkin_fast_kernel<NH, DMAX>, lds);
+  set_lds_limit(galerkin_fast_kernel<NH, DMAX>, lds);
   hipLaunchKernelGGL((galerkin_fast_kernel<NH, DMAX>), dim3(n), dim3(C::THREADS * cg), lds, st, u, Au, wjc, t->d_child, t->d_off, t->d_item_first,
                      t->d_gal_child, t->d_gal_qs, t->d_gal_T, t->d_gal_TT, list, cg);
 }
@@ -759,7 +754,7 @@ static void launch_prolong(d4est_hip_transfer_t* t, const double* x_coarse_dev, 
     if (L.NH > 0) { d4est_hip::launch_fast_prolong<ADD>(t, x_coarse_dev, x_fine_dev, L.NH, L.dmax, t->d_lists + L.first, L.n); continue; }
     const int n3 = t->max_n * t->max_n * t->max_n;
     const size_t lds = (size_t)2 * n3 * sizeof(double);
-    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(d4est_hip::prolong_kernel<ADD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    d4est_hip::set_lds_limit(d4est_hip::prolong_kernel<ADD>, lds);
     hipLaunchKernelGGL(d4est_hip::prolong_kernel<ADD>, dim3(std::min(L.n, 65536)), dim3(256), lds, t->stream, x_coarse_dev, x_fine_dev,
                        t->d_child, t->d_off, t->d_ops, t->d_lists + L.first, L.n, n3);
   }
@@ -788,7 +783,7 @@ static void launch_restrict(d4est_hip_transfer_t* t, const double* x_fine_dev, d
     const size_t lds = (size_t)(acc_in_lds ? 3 : 2) * n3 * sizeof(double);
     if (lds > 160 * 1024) D4EST_HIP_ABORT("%s: degree too high for the LDS-resident kernel", who);
     const void* fn = project ? reinterpret_cast<const void*>(d4est_hip::restrict_kernel<false>) : reinterpret_cast<const void*>(d4est_hip::restrict_kernel<true>);
-    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    d4est_hip::set_lds_limit(fn, lds);
     if (project)
       hipLaunchKernelGGL(d4est_hip::restrict_kernel<false>, dim3(std::min(L.n, 65536)), dim3(256), lds, t->stream, x_fine_dev, x_coarse_dev,
                          t->d_child, t->d_off, t->d_item_first, t->d_rops, t->d_lists + L.first, L.n, n3, acc_in_lds);

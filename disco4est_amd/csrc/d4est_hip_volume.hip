@@ -18,8 +18,6 @@
 // element is the algorithmic minimum: u once, the 6-entry symmetric metric once,
 // Au once (64 B/DoF at Nq = N).
 #include <algorithm>
-#include <mutex>
-#include <unordered_map>
 #include <cstring>
 
 #include "d4est_hip_internal.h"
@@ -1459,28 +1457,8 @@ __global__ __launch_bounds__(256) void metric_precombine_kernel(const double* __
 // ---------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------
-#define D4EST_HIP_FAST_PAIRS(X) \
-  X(2, 2) X(3, 3) X(4, 4) X(5, 5) X(6, 6) X(7, 7) X(8, 8) X(9, 9) X(10, 10) X(11, 11) X(12, 12) \
-  X(13, 13) X(14, 14) X(15, 15) X(16, 16)                                                       \
-  X(2, 3) X(3, 4) X(4, 5) X(8, 9) X(3, 6) X(4, 6) X(8, 10)
-
-// p = 16 .. 19 (the reference's tables stop at 20 Lobatto points): only the two-field multi-wave kernels fit the 160 KB LDS
-#define D4EST_HIP_BIG_PAIRS(X) X(17, 17) X(18, 18) X(19, 19) X(20, 20)
-
-// (once per kernel instance and size: a driver call per launch would sit in the hot path of every smoother iteration, and inside a
-// hipGraph capture region)
-template <typename K>
-static void set_lds_limit(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return;
-  static std::mutex mu;
-  static std::unordered_map<const void*, size_t> done;
-  const void* key = reinterpret_cast<const void*>(kernel);
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = done.find(key);
-  if (it != done.end() && it->second >= bytes) return;
-  HIP_CHECK(hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  done[key] = bytes;
-}
+// The (N, NQ) pairs with compiled kernels and their dispatcher for_built_pair: d4est_hip_wave.h.  set_lds_limit, the mixed-degree work-list
+// helpers (multi_append, for_each_uncovered_bucket): d4est_hip_internal.h.
 
 static void ensure_scratch(d4est_hip_plan* plan, size_t doubles) {
   if (plan->scratch_doubles >= doubles) return;
@@ -1505,6 +1483,17 @@ static void launch_generic(d4est_hip_plan* plan, const Bucket& bk, int mode, con
                      per_block, coeff);
 }
 
+// The bucket's metric is rebuilt from its six constants per element instead of being streamed.  Bucket::affine is only ever set after
+// plan->d_metric_affine was allocated (launch_brick_geometry, launch_metric_precombine) and the array lives as long as the plan, so the
+// test of the pointer that some launches used to add could never fail; launch_stiffness_view clears `affine` for the views it launches.
+// What a kernel family needs beyond this (an affine instance that exists, the even-odd tables) stands where that family is chosen.
+static bool bucket_affine_on(const d4est_hip_plan* plan, const Bucket& bk) {
+  return bk.affine && plan->tuning[D4EST_HIP_TUNE_AFFINE] != 0;
+}
+static const double* bucket_affine_constants(const d4est_hip_plan* plan, const Bucket& bk) {
+  return plan->d_metric_affine + (size_t)6 * bk.elem_offset;
+}
+
 // deg_quad = deg <= 7: the single-wavefront even-odd kernels run the collocated-gradient body (stiffness_wave_eo_element_cg) unless tuning
 // key D4EST_HIP_TUNE_STIFFNESS_WAVE = 12 asks for the 16-product body (A/B runs, tests/test_volume_cg_gpu.py)
 static bool wave_collocated(const d4est_hip_plan* plan, const Bucket& bk) {
@@ -1524,84 +1513,212 @@ static void wave_entry_tag(char* tag, size_t n) {
   std::snprintf(tag, n, ",entry%d%s", kWaveCgEntry, kWaveCgSplit ? ",split" : "");
 }
 
+// Which stiffness kernel one bucket gets: decided here, in one place, from the tuning keys, the stream mode and the bucket; the launchers
+// below only launch.
+enum class StiffnessFamily { single_wave, mfma16, multi_wave, three_field, generic };
+enum class WaveBody { eo, wave2, pair, plain };   // single_wave only: stiffness_wave_eo_kernel / _wave2_kernel / _pair_kernel / _wave_kernel
+struct StiffnessChoice {
+  StiffnessFamily family = StiffnessFamily::generic;
+  WaveBody body = WaveBody::plain;
+  bool eo = false;       // even-odd tables
+  bool affine = false;   // metric from the bucket's affine constants
+  bool pf = false;       // prefetching (three-buffer) instance
+  bool nt = false;       // stream-mode (non-temporal) twin
+  bool cg = false;       // single_wave: collocated-gradient body
+  bool entry = false;    // single_wave, cg: metric stream on the entry-prefetch schedule
+};
+
+static StiffnessChoice stiffness_choice(const d4est_hip_plan* plan, const Bucket& bk) {
+  StiffnessChoice c;
+  const int tw = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_WAVE], tp = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_PREFETCH];
+  const int big = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_BIGP];
+  const bool affine_ok = bucket_affine_on(plan, bk);
+  // auto-tuning (measured on MI355X, p = 7): up to ~2 resident rounds (16 one-wave workgroups per CU)
+  // the two-buffer wave kernel wins; for larger buckets the 3-buffer kernel with the metric requested
+  // at entry streams HBM best.  profiles/r01_*_ab.txt
+  const bool use_wave = (tw < 0) ? (bk.n_elem <= 8192 || affine_ok) : (tw != 0);
+  const bool use_pf = (tp < 0) ? !use_wave : (tp != 0);
+  const bool one_wave = bk.NQ * bk.NQ <= 64;
+  const bool use_eo = bk.d_EBf && plan->tuning[D4EST_HIP_TUNE_STIFFNESS_EO] != 0;   // (the even-odd contractions take sizes of either parity)
+  if (!pair_built(bk.N, bk.NQ)) return c;
+  if (bk.N > 16) {   // D4EST_HIP_BIG_PAIRS (kBigPair): the two-field multi-wave kernels or nothing
+    if (big == 0) return c;
+    c.family = StiffnessFamily::multi_wave;
+  } else if (one_wave && use_wave) {
+    c.family = StiffnessFamily::single_wave;
+  } else if (bk.N >= 13 && bk.NQ == bk.N && (big == 2 || (bk.N == 16 && big < 0))) {
+    c.family = StiffnessFamily::mfma16;
+  } else if (!one_wave && big != 0) {
+    // p >= 8: multi-wave workgroup, two LDS fields (sequential field hand-off) -> 1.5x the residency
+    c.family = StiffnessFamily::multi_wave;
+  } else {
+    c.family = StiffnessFamily::three_field;
+  }
+  switch (c.family) {
+    case StiffnessFamily::single_wave:
+      c.eo = tune_wave_eo(tw) && bk.d_EBf;   // (key 1 chooses among the one-wave kernels; key 6 does not apply to them)
+      c.body = c.eo ? WaveBody::eo
+                    : (tw == 3 || tune_wave_eo(tw)) ? WaveBody::wave2
+                    : (tw == 2 && bk.N % 2 == 0 && bk.NQ % 2 == 0) ? WaveBody::pair : WaveBody::plain;
+      c.affine = affine_ok && c.eo;   // only the even-odd kernel has an affine instance
+      c.cg = c.eo && wave_collocated(plan, bk);
+      c.entry = c.cg && !c.affine && wave_entry(plan, bk.N, false);
+      c.pf = c.body == WaveBody::plain && use_pf;
+      break;
+    case StiffnessFamily::mfma16:
+      c.affine = affine_ok && bk.N == 16;   // the one affine instance that is built (stream mode is a kernel argument here, not a twin)
+      break;
+    case StiffnessFamily::multi_wave:
+      c.eo = use_eo;
+      c.affine = affine_ok && use_eo;       // only the even-odd kernel has an affine instance
+      c.nt = use_eo && !c.affine && plan->stream_mode != 0;   // NT twin: stream mode (plan->stream_mode, d4est_hip_wave.h)
+      break;
+    case StiffnessFamily::three_field:
+      c.eo = use_eo;
+      c.pf = bk.NQ <= 8 && use_pf;
+      c.nt = c.pf && use_eo && plan->stream_mode != 0;
+      break;
+    case StiffnessFamily::generic: break;
+  }
+  return c;
+}
+
 template <int N, int NQ>
-static void launch_stiffness_wave(d4est_hip_plan* plan, const Bucket& bk, bool use_pf, const double* u, double* Au) {
-  if constexpr (NQ * NQ <= 64 && NQ >= N) {
-    using W = WaveCfg<N, NQ>;
-    const int grid = (bk.n_elem + W::EPB - 1) / W::EPB;
-    const int ts = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_STAGGER];
-    const int cus_ = plan->n_cus > 0 ? plan->n_cus : 256;
-    // stagger is an experiment knob only: delaying half of the resident workgroups changed config-2 time by +-3 %
-    // (noise level) in every grouping tried, so auto = off (profiles/r01_d_notes.txt)
-    (void)cus_;
-    const int stagger = ts < 0 ? 0 : ts;
-    const int tw_ = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_WAVE];
-    const bool use_affine = bk.affine && plan->tuning[D4EST_HIP_TUNE_AFFINE] != 0 && bk.d_EBf && tune_wave_eo(tw_);
-    const bool cg = wave_collocated(plan, bk);   // deg_quad = deg: the collocated-gradient body, its tables in the places of EGf / EGb
-    const double* EGf = cg ? bk.d_EDq : bk.d_EGf;
-    const double* EGb = cg ? bk.d_EDqT : bk.d_EGb;
-    auto go = [&](auto kern, const double* affine, const double* wq) {
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(64), W::LDS_BYTES, plan->stream, u, Au, plan->d_metric, plan->d_ns_list + bk.elem_offset,
-                         plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_EBf, EGf, bk.d_EBb, EGb, bk.ns0, bk.ns_stride, bk.qs0,
-                         bk.qs_stride, affine, wq);
+static void launch_stiffness_wave(d4est_hip_plan* plan, const Bucket& bk, const StiffnessChoice& c, const double* u, double* Au) {
+  static_assert(NQ * NQ <= 64 && NQ >= N, "one element per NQ * NQ lanes of a wavefront");
+  using W = WaveCfg<N, NQ>;
+  const int grid = (bk.n_elem + W::EPB - 1) / W::EPB;
+  // stagger is an experiment knob only: delaying half of the resident workgroups changed config-2 time by +-3 %
+  // (noise level) in every grouping tried, so auto = off (profiles/r01_d_notes.txt)
+  const int ts = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_STAGGER];
+  const int stagger = ts < 0 ? 0 : ts;
+  const int* ns_list = plan->d_ns_list + bk.elem_offset;
+  const int* qs_list = plan->d_qs_list + bk.elem_offset;
+  if (c.body == WaveBody::eo) {
+    char tag[24] = "";
+    if (c.entry) wave_entry_tag(tag, sizeof(tag));
+    std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_kernel<%d,%d%s%s%s>", N, NQ,
+                  c.affine ? ",affine" : "", c.cg ? ",cg" : "", tag);
+    // deg_quad = deg: the collocated-gradient body, its tables in the places of EGf / EGb
+    auto go = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(64), W::LDS_BYTES, plan->stream, u, Au, plan->d_metric, ns_list, qs_list, bk.n_elem,
+                         bk.d_EBf, c.cg ? bk.d_EDq : bk.d_EGf, bk.d_EBb, c.cg ? bk.d_EDqT : bk.d_EGb, bk.ns0, bk.ns_stride, bk.qs0,
+                         bk.qs_stride, c.affine ? bucket_affine_constants(plan, bk) : (const double*)nullptr,
+                         c.affine ? bk.d_w : (const double*)nullptr);
     };
-    if (use_affine) {
-      std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_kernel<%d,%d,affine%s>", N, NQ, cg ? ",cg" : "");
-      const double* aff = plan->d_metric_affine + (size_t)6 * bk.elem_offset;
-      if constexpr (kWaveCollocated<N, NQ>) { if (cg) go(stiffness_wave_eo_kernel<N, NQ, true, true>, aff, bk.d_w); }
-      if (!cg) go(stiffness_wave_eo_kernel<N, NQ, true, false>, aff, bk.d_w);
-    } else if (tune_wave_eo(tw_) && bk.d_EBf) {
-      const bool entry = cg && wave_entry(plan, N, false);
-      char tag[24] = "";
-      if (entry) wave_entry_tag(tag, sizeof(tag));
-      std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_kernel<%d,%d%s%s>", N, NQ, cg ? ",cg" : "", tag);
-      if constexpr (kWaveCollocated<N, NQ>) {
-        if (entry) go(stiffness_wave_eo_kernel<N, NQ, false, true, true>, nullptr, nullptr);
-        else if (cg) go(stiffness_wave_eo_kernel<N, NQ, false, true>, nullptr, nullptr);
-      }
-      if (!cg) go(stiffness_wave_eo_kernel<N, NQ, false, false>, nullptr, nullptr);
-    } else if (tw_ == 3 || tune_wave_eo(tw_)) {
-      std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave2_kernel<%d,%d>", N, NQ);
-      hipLaunchKernelGGL((stiffness_wave2_kernel<N, NQ>), dim3(grid), dim3(64), W::LDS_BYTES, plan->stream, u, Au, plan->d_metric,
-                         plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_B, bk.d_G, bk.d_BT,
-                         bk.d_GT, stagger);
-    } else if (plan->tuning[D4EST_HIP_TUNE_STIFFNESS_WAVE] == 2 && N % 2 == 0 && NQ % 2 == 0) {
-      std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_pair_kernel<%d,%d>", N, NQ);
-      if constexpr (N % 2 == 0 && NQ % 2 == 0)
-        hipLaunchKernelGGL((stiffness_pair_kernel<N, NQ>), dim3(grid), dim3(128), (W::LDS_BYTES / 2) * 3, plan->stream, u, Au,
-                           plan->d_metric, plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem,
-                           bk.d_B, bk.d_G, bk.d_BT, bk.d_GT);
-    } else if (use_pf) {
-      std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_kernel<%d,%d,true>", N, NQ);
-      hipLaunchKernelGGL((stiffness_wave_kernel<N, NQ, true>), dim3(grid), dim3(64), W::LDS_BYTES, plan->stream, u, Au,
-                         plan->d_metric, plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem,
-                         bk.d_B, bk.d_G, bk.d_BT, bk.d_GT, stagger);
-    } else {
-      std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_kernel<%d,%d,false>", N, NQ);
-      hipLaunchKernelGGL((stiffness_wave_kernel<N, NQ, false>), dim3(grid), dim3(64), W::LDS_BYTES, plan->stream, u, Au,
-                         plan->d_metric, plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem,
-                         bk.d_B, bk.d_G, bk.d_BT, bk.d_GT, stagger);
+    if constexpr (kWaveCollocated<N, NQ>) {   // (c.cg implies it)
+      if (c.cg && c.affine) return go(stiffness_wave_eo_kernel<N, NQ, true, true>);
+      if (c.entry) return go(stiffness_wave_eo_kernel<N, NQ, false, true, true>);
+      if (c.cg) return go(stiffness_wave_eo_kernel<N, NQ, false, true>);
     }
+    if (c.affine) go(stiffness_wave_eo_kernel<N, NQ, true, false>);
+    else go(stiffness_wave_eo_kernel<N, NQ, false, false>);
+    return;
+  }
+  auto go = [&](auto kern, int threads, size_t lds, auto... last) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, plan->stream, u, Au, plan->d_metric, ns_list, qs_list, bk.n_elem, bk.d_B,
+                       bk.d_G, bk.d_BT, bk.d_GT, last...);
+  };
+  if (c.body == WaveBody::wave2) {
+    std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave2_kernel<%d,%d>", N, NQ);
+    go(stiffness_wave2_kernel<N, NQ>, 64, W::LDS_BYTES, stagger);
+  } else if (c.body == WaveBody::pair) {
+    std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_pair_kernel<%d,%d>", N, NQ);
+    if constexpr (N % 2 == 0 && NQ % 2 == 0) go(stiffness_pair_kernel<N, NQ>, 128, (W::LDS_BYTES / 2) * 3);
+  } else {
+    std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_kernel<%d,%d,%s>", N, NQ, c.pf ? "true" : "false");
+    // (the kernel's last two parameters have defaults a function pointer loses: no affine constants)
+    if (c.pf) go(stiffness_wave_kernel<N, NQ, true>, 64, W::LDS_BYTES, stagger, (const double*)nullptr, (const double*)nullptr);
+    else go(stiffness_wave_kernel<N, NQ, false>, 64, W::LDS_BYTES, stagger, (const double*)nullptr, (const double*)nullptr);
   }
 }
 
-static void launch_stiffness_mfma16(d4est_hip_plan* plan, const Bucket& bk, const double* u, double* Au) {
-  const bool aff = bk.affine && plan->tuning[D4EST_HIP_TUNE_AFFINE] != 0 && plan->d_metric_affine && bk.N == 16;
+static void launch_stiffness_mfma16(d4est_hip_plan* plan, const Bucket& bk, const StiffnessChoice& c, const double* u, double* Au) {
   std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_mfma16_kernel<%d%s> (512 threads, v_mfma_f64_16x16x4)", bk.N,
-                aff ? ",affine" : "");
+                c.affine ? ",affine" : "");
   const int cus = plan->n_cus > 0 ? plan->n_cus : 256;
   const int grid = bk.n_elem < cus ? bk.n_elem : cus;   // one 102 KB workgroup per CU, persistent over the bucket
   auto go = [&](auto kern) {
     set_lds_limit(kern, Mfma16Cfg::LDS_BYTES);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), Mfma16Cfg::LDS_BYTES, plan->stream, u, Au, plan->d_metric,
                        plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_B, bk.d_G,
-                       aff ? plan->d_metric_affine + (size_t)6 * bk.elem_offset : (const double*)nullptr, bk.d_w, plan->stream_mode);
+                       c.affine ? bucket_affine_constants(plan, bk) : (const double*)nullptr, bk.d_w, plan->stream_mode);
   };
-  if (aff) go(stiffness_mfma16_kernel<16, true>);
+  if (c.affine) go(stiffness_mfma16_kernel<16, true>);
   else if (bk.N == 16) go(stiffness_mfma16_kernel<16>);
   else if (bk.N == 15) go(stiffness_mfma16_kernel<15>);
   else if (bk.N == 14) go(stiffness_mfma16_kernel<14>);
   else go(stiffness_mfma16_kernel<13>);
+}
+
+// p >= 8: one element per multi-wave workgroup, two LDS fields.  The one copy of this launch: both pair lists come here.
+template <int N, int NQ>
+static void launch_stiffness_mw(d4est_hip_plan* plan, const Bucket& bk, const StiffnessChoice& c, const double* u, double* Au) {
+  using W = WaveCfg<N, NQ>;
+  std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_kernel<%d,%d,false,%s%s> (%d threads)", N, NQ,
+                c.eo ? "eo" : "plain", c.affine ? ",affine" : "", W::THREADS);
+  auto go = [&](auto kern, const double* o0, const double* o1, const double* o2, const double* o3, int stagger, const double* affine,
+                const double* wq) {
+    set_lds_limit(kern, W::LDS_BYTES);
+    hipLaunchKernelGGL(kern, dim3(bk.n_elem), dim3(W::THREADS), W::LDS_BYTES, plan->stream, u, Au, plan->d_metric,
+                       plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, o0, o1, o2, o3, stagger, affine, wq);
+  };
+  if (!c.eo) return go(stiffness_wave_kernel<N, NQ, false>, bk.d_B, bk.d_G, bk.d_BT, bk.d_GT, 0, nullptr, nullptr);
+  constexpr bool kCg = kMwCollocated<N, NQ, false, true>;   // deg_quad = deg: the collocated-gradient tables in the places of EGb / EGf
+  const double* Gb = kCg ? bk.d_EDq : bk.d_EGb;
+  const double* Gf = kCg ? bk.d_EDqT : bk.d_EGf;
+  const int ts = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_STAGGER];
+  // the affine bucket's six constants per element, or nullptr = stream the metric
+  if (c.affine) go(stiffness_wave_kernel<N, NQ, false, true, true>, bk.d_EBb, Gb, bk.d_EBf, Gf, 0, bucket_affine_constants(plan, bk), bk.d_w);
+  else if (c.nt) go(stiffness_wave_kernel<N, NQ, false, true, false, true>, bk.d_EBb, Gb, bk.d_EBf, Gf, ts < 0 ? 0 : ts, nullptr, nullptr);
+  else go(stiffness_wave_kernel<N, NQ, false, true>, bk.d_EBb, Gb, bk.d_EBf, Gf, ts < 0 ? 0 : ts, nullptr, nullptr);
+}
+
+// the three-field kernel: deg_quad > deg pairs beyond one wavefront, large one-wave buckets (the prefetching instance), and every pair
+// up to p = 15 with tuning key D4EST_HIP_TUNE_STIFFNESS_BIGP = 0
+template <int N, int NQ>
+static void launch_stiffness_3field(d4est_hip_plan* plan, const Bucket& bk, const StiffnessChoice& c, const double* u, double* Au) {
+  using C = VolCfg<N, NQ>;
+  static_assert(C::LDS_BYTES <= 160 * 1024, "three LDS fields of a fast pair fit");
+  constexpr bool kCanPF = (NQ <= 8);
+  const int grid = (bk.n_elem + C::EPB - 1) / C::EPB;
+  std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_kernel<%d,%d,%s,%s>", N, NQ, c.pf ? "true" : "false",
+                c.eo ? "eo" : "plain");
+  auto go = [&](auto kern) {
+    set_lds_limit(kern, C::LDS_BYTES);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), C::LDS_BYTES, plan->stream, u, Au, plan->d_metric,
+                       plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, c.eo ? bk.d_EBb : bk.d_B,
+                       c.eo ? bk.d_EGb : bk.d_G, c.eo ? bk.d_EBf : bk.d_BT, c.eo ? bk.d_EGf : bk.d_GT);
+  };
+  if (c.nt) go(stiffness_kernel<N, NQ, kCanPF, true, true>);
+  else if (c.pf && c.eo) go(stiffness_kernel<N, NQ, kCanPF, true>);
+  else if (c.pf) go(stiffness_kernel<N, NQ, kCanPF, false>);
+  else if (c.eo) go(stiffness_kernel<N, NQ, false, true>);
+  else go(stiffness_kernel<N, NQ, false, false>);
+}
+
+static void launch_stiffness_generic(d4est_hip_plan* plan, const Bucket& bk, const double* u, double* Au) {
+  std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::generic_volume_kernel (N=%d,NQ=%d)", bk.N, bk.NQ);
+  launch_generic(plan, bk, 3, u, Au);
+}
+
+// Mixed-degree plans: which buckets the one-launch kernels take.  The one-wavefront even-odd body (deg_quad = deg <= 7) ...
+static bool bucket_single_wave_eo(const Bucket& bk) { return bucket_single_wave(bk) && bk.d_EBf; }
+// ... and the collocated multi-wave body, N = lo .. hi
+static bool bucket_multi_wave(const Bucket& bk, int lo, int hi) {
+  return bk.n_elem > 0 && bk.N == bk.NQ && bk.N >= lo && bk.N <= hi && bk.d_EDq;
+}
+static int bucket_workgroups(const Bucket& bk) { return (bk.n_elem + wave_cfg_square(bk.N).epb - 1) / wave_cfg_square(bk.N).epb; }
+// the tables in the EGf / EGb places of the newest entry: the collocated-gradient pair where the body is the collocated one
+static bool multi_wave_eo_tables(const d4est_hip_plan* plan, WaveEoMulti& A, const Bucket& bk) {
+  const bool cg = wave_collocated(plan, bk);
+  A.EGf[A.n - 1] = cg ? bk.d_EDq : bk.d_EGf;
+  A.EGb[A.n - 1] = cg ? bk.d_EDqT : bk.d_EGb;
+  return cg;
+}
+static void multi_mw_tables(WaveEoMulti& A, const Bucket& bk) {
+  A.EGf[A.n - 1] = bk.d_EDqT;
+  A.EGb[A.n - 1] = bk.d_EDq;
 }
 
 // Mixed-degree plans: the buckets the single-wavefront even-odd kernel would take (deg_quad = deg <= 7, automatic kernel choice) go
@@ -1614,26 +1731,15 @@ static unsigned launch_stiffness_multi(d4est_hip_plan* plan, const double* u, do
     WaveEoMulti A;
     size_t lds = 0;
     unsigned mine = 0u;
-    int wgs = 0;
-    bool all_cg = true;
-    for (size_t i = 0; i < plan->buckets.size() && i < 32; ++i) {
+    bool all_cg = true;   // (the same answer for every bucket: they all have deg_quad = deg)
+    for (size_t i = 0; i < plan->buckets.size(); ++i) {
       const Bucket& bk = plan->buckets[i];
-      if (bk.n_elem == 0 || bk.N != bk.NQ || bk.N < 2 || bk.N > 8 || !bk.d_EBf || A.n == WaveEoMulti::MAXB) continue;
-      const bool use_affine = bk.affine && plan->tuning[D4EST_HIP_TUNE_AFFINE] != 0 && plan->d_metric_affine;
-      if ((int)use_affine != aff || !(bk.n_elem <= 8192 || use_affine)) continue;   // (larger buckets: the prefetching kernel, see below)
-      size_t l = 0;
-      int epb = 1;
-#define X(N_) if (bk.N == N_) { l = WaveCfg<N_, N_>::LDS_BYTES; epb = WaveCfg<N_, N_>::EPB; }
-      X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-#undef X
-      lds = std::max(lds, l);
-      wgs += (bk.n_elem + epb - 1) / epb;
-      const int j = A.n++;
-      A.wg_end[j] = wgs; A.N[j] = bk.N; A.n_elem[j] = bk.n_elem; A.elem_offset[j] = bk.elem_offset;
-      const bool cg = wave_collocated(plan, bk);   // (the same answer for every bucket: they all have deg_quad = deg)
-      all_cg = all_cg && cg;
-      A.EBf[j] = bk.d_EBf; A.EGf[j] = cg ? bk.d_EDq : bk.d_EGf; A.EBb[j] = bk.d_EBb; A.EGb[j] = cg ? bk.d_EDqT : bk.d_EGb; A.wq[j] = bk.d_w;
-      mine |= 1u << i;
+      if (!bucket_single_wave_eo(bk)) continue;
+      const bool use_affine = bucket_affine_on(plan, bk);
+      if ((int)use_affine != aff || !(bk.n_elem <= 8192 || use_affine)) continue;   // (larger buckets: the prefetching kernel, stiffness_choice)
+      if (!multi_append(A, mine, i, bk, bucket_workgroups(bk))) continue;
+      lds = std::max(lds, wave_cfg_square(bk.N).lds_bytes);
+      all_cg = multi_wave_eo_tables(plan, A, bk) && all_cg;
     }
     if (A.n < 2) continue;
     const bool entry = !aff && all_cg && wave_entry(plan, 0, true);
@@ -1641,7 +1747,7 @@ static unsigned launch_stiffness_multi(d4est_hip_plan* plan, const double* u, do
     if (entry) wave_entry_tag(tag, sizeof(tag));
     std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_eo_multi_kernel<%s%s%s> (%d buckets)", aff ? "affine" : "general", all_cg ? ",cg" : "", tag, A.n);
     auto go = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(wgs), dim3(64), lds, plan->stream, u, Au, plan->d_metric, plan->d_ns_list, plan->d_qs_list,
+      hipLaunchKernelGGL(kern, dim3(multi_workgroups(A)), dim3(64), lds, plan->stream, u, Au, plan->d_metric, plan->d_ns_list, plan->d_qs_list,
                          aff ? plan->d_metric_affine : (const double*)nullptr, A);
     };
     if (aff) { if (all_cg) go(stiffness_wave_eo_multi_kernel<true, true>); else go(stiffness_wave_eo_multi_kernel<true, false>); }
@@ -1652,34 +1758,33 @@ static unsigned launch_stiffness_multi(d4est_hip_plan* plan, const double* u, do
   return covered;
 }
 
+// the tuning under which stiffness_choice gives a deg_quad = deg >= 9 bucket the even-odd multi-wave kernel
+static bool tune_multi_wave_auto(const d4est_hip_plan* plan) {
+  const int big = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_BIGP];
+  return (big < 0 || big == 1) && plan->tuning[D4EST_HIP_TUNE_STIFFNESS_EO] != 0;
+}
+
 // ... and the p = 8 ... 12 buckets of such a plan by workgroup size (stiffness_mw_multi_kernel): general path, automatic kernel choice
 static unsigned launch_stiffness_multi_mw(d4est_hip_plan* plan, const double* u, double* Au) {
-  if (plan->tuning[D4EST_HIP_TUNE_STIFFNESS_BIGP] >= 0 && plan->tuning[D4EST_HIP_TUNE_STIFFNESS_BIGP] != 1) return 0u;
-  if (plan->tuning[D4EST_HIP_TUNE_STIFFNESS_EO] == 0) return 0u;
+  if (!tune_multi_wave_auto(plan)) return 0u;
   unsigned covered = 0u;
   for (int threads = 128; threads <= 192; threads += 64) {
     WaveEoMulti A;
     size_t lds = 0;
     unsigned mine = 0u;
-    int wgs = 0;
-    for (size_t i = 0; i < plan->buckets.size() && i < 32; ++i) {
+    for (size_t i = 0; i < plan->buckets.size(); ++i) {
       const Bucket& bk = plan->buckets[i];
-      if (bk.n_elem == 0 || bk.N != bk.NQ || bk.N < 9 || bk.N > 13 || !bk.d_EDq || A.n == WaveEoMulti::MAXB) continue;
-      if (bk.affine && plan->tuning[D4EST_HIP_TUNE_AFFINE] != 0 && plan->d_metric_affine) continue;   // (affine buckets keep their kernel)
-      const int th = ((bk.N * bk.N + 63) / 64) * 64;
-      if (th != threads) continue;
-      lds = std::max(lds, (size_t)2 * bk.N * bk.N * (bk.N | 1) * sizeof(double));
-      wgs += bk.n_elem;
-      const int j = A.n++;
-      A.wg_end[j] = wgs; A.N[j] = bk.N; A.n_elem[j] = bk.n_elem; A.elem_offset[j] = bk.elem_offset;
-      A.EBf[j] = bk.d_EBf; A.EGf[j] = bk.d_EDqT; A.EBb[j] = bk.d_EBb; A.EGb[j] = bk.d_EDq; A.wq[j] = bk.d_w;
-      mine |= 1u << i;
+      if (!bucket_multi_wave(bk, 9, 13) || bucket_affine_on(plan, bk)) continue;   // (affine buckets keep their kernel)
+      if (((bk.N * bk.N + 63) / 64) * 64 != threads) continue;   // (WaveCfg<N, N>::THREADS)
+      if (!multi_append(A, mine, i, bk, bucket_workgroups(bk))) continue;
+      lds = std::max(lds, wave_cfg_square(bk.N).lds_bytes);
+      multi_mw_tables(A, bk);
     }
     if (A.n < 2) continue;
     std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_mw_multi_kernel<%d> (%d buckets)", threads, A.n);
     auto go = [&](auto kern) {
       set_lds_limit(kern, lds);
-      hipLaunchKernelGGL(kern, dim3(wgs), dim3(threads), lds, plan->stream, u, Au, plan->d_metric, plan->d_ns_list, plan->d_qs_list, A);
+      hipLaunchKernelGGL(kern, dim3(multi_workgroups(A)), dim3(threads), lds, plan->stream, u, Au, plan->d_metric, plan->d_ns_list, plan->d_qs_list, A);
     };
     if (threads == 128) { if (plan->stream_mode) go(stiffness_mw_multi_kernel<128, true>); else go(stiffness_mw_multi_kernel<128, false>); }
     else { if (plan->stream_mode) go(stiffness_mw_multi_kernel<192, true>); else go(stiffness_mw_multi_kernel<192, false>); }
@@ -1688,55 +1793,38 @@ static unsigned launch_stiffness_multi_mw(d4est_hip_plan* plan, const double* u,
   return covered;
 }
 
-
 // ... and both kinds in one launch where a plan has p <= 7 buckets AND 128-thread multi-wave buckets (stiffness_all_multi_kernel)
 static unsigned launch_stiffness_all_multi(d4est_hip_plan* plan, const double* u, double* Au) {
   const int tw = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_WAVE];
   if (!tune_wave_eo(tw) || plan->tuning[D4EST_HIP_TUNE_STIFFNESS_PREFETCH] > 0) return 0u;
-  if (plan->tuning[D4EST_HIP_TUNE_STIFFNESS_BIGP] >= 0 && plan->tuning[D4EST_HIP_TUNE_STIFFNESS_BIGP] != 1) return 0u;
-  if (plan->tuning[D4EST_HIP_TUNE_STIFFNESS_EO] == 0) return 0u;
+  if (!tune_multi_wave_auto(plan)) return 0u;
   static const bool split = std::getenv("D4EST_HIP_STIFFNESS_SPLIT_LAUNCH") != nullptr;
   if (split) return 0u;
   WaveEoMulti A;
   size_t lds = 0;
   unsigned mine = 0u;
-  int wgs = 0, n_eo = 0, n_mw = 0;
+  int n_eo = 0, n_mw = 0;
   bool all_cg = true;   // the one-wavefront buckets in the collocated-gradient form (the same answer for each of them)
-  for (size_t i = 0; i < plan->buckets.size() && i < 32; ++i) {
+  for (size_t i = 0; i < plan->buckets.size(); ++i) {
     const Bucket& bk = plan->buckets[i];
-    if (bk.n_elem == 0 || bk.N != bk.NQ || A.n == WaveEoMulti::MAXB) continue;
-    if (bk.affine && plan->tuning[D4EST_HIP_TUNE_AFFINE] != 0 && plan->d_metric_affine) continue;   // (affine buckets keep their kernels)
-    const int j = A.n;
-    if (bk.N >= 2 && bk.N <= 8 && bk.d_EBf && bk.n_elem <= 8192) {
-      size_t l = 0;
-      int epb = 1;
-#define X(N_) if (bk.N == N_) { l = WaveCfg<N_, N_>::LDS_BYTES; epb = WaveCfg<N_, N_>::EPB; }
-      X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-#undef X
-      lds = std::max(lds, 2 * l);
-      const int units = (bk.n_elem + epb - 1) / epb;
-      wgs += (units + 1) / 2;
-      const bool cg = wave_collocated(plan, bk);
-      all_cg = all_cg && cg;
-      A.EBf[j] = bk.d_EBf; A.EGf[j] = cg ? bk.d_EDq : bk.d_EGf; A.EBb[j] = bk.d_EBb; A.EGb[j] = cg ? bk.d_EDqT : bk.d_EGb;
+    if (bucket_affine_on(plan, bk)) continue;   // (affine buckets keep their kernels)
+    if (bucket_single_wave_eo(bk) && bk.n_elem <= 8192) {
+      if (!multi_append(A, mine, i, bk, (bucket_workgroups(bk) + 1) / 2)) continue;   // two one-wave work units per 128-thread workgroup
+      lds = std::max(lds, 2 * wave_cfg_square(bk.N).lds_bytes);
+      all_cg = multi_wave_eo_tables(plan, A, bk) && all_cg;
       ++n_eo;
-    } else if (bk.N >= 9 && bk.N <= 11 && bk.d_EDq) {
-      lds = std::max(lds, (size_t)2 * bk.N * bk.N * (bk.N | 1) * sizeof(double));
-      wgs += bk.n_elem;
-      A.EBf[j] = bk.d_EBf; A.EGf[j] = bk.d_EDqT; A.EBb[j] = bk.d_EBb; A.EGb[j] = bk.d_EDq;
+    } else if (bucket_multi_wave(bk, 9, 11)) {
+      if (!multi_append(A, mine, i, bk, bucket_workgroups(bk))) continue;
+      lds = std::max(lds, wave_cfg_square(bk.N).lds_bytes);
+      multi_mw_tables(A, bk);
       ++n_mw;
-    } else {
-      continue;
     }
-    A.n = j + 1;
-    A.wg_end[j] = wgs; A.N[j] = bk.N; A.n_elem[j] = bk.n_elem; A.elem_offset[j] = bk.elem_offset; A.wq[j] = bk.d_w;
-    mine |= 1u << i;
   }
   if (n_eo == 0 || n_mw == 0) return 0u;   // one kind only: the launches above
   std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_all_multi_kernel%s (%d + %d buckets)", all_cg ? "<cg>" : "", n_eo, n_mw);
   auto go = [&](auto kern) {
     set_lds_limit(kern, lds);
-    hipLaunchKernelGGL(kern, dim3(wgs), dim3(128), lds, plan->stream, u, Au, plan->d_metric, plan->d_ns_list, plan->d_qs_list, A);
+    hipLaunchKernelGGL(kern, dim3(multi_workgroups(A)), dim3(128), lds, plan->stream, u, Au, plan->d_metric, plan->d_ns_list, plan->d_qs_list, A);
   };
   if (all_cg) { if (plan->stream_mode) go(stiffness_all_multi_kernel<true, true>); else go(stiffness_all_multi_kernel<false, true>); }
   else { if (plan->stream_mode) go(stiffness_all_multi_kernel<true, false>); else go(stiffness_all_multi_kernel<false, false>); }
@@ -1747,161 +1835,47 @@ void launch_stiffness(d4est_hip_plan* plan, const double* u, double* Au) {
   if (!plan->has_geometry) D4EST_HIP_ABORT("apply_stiffness_matrix: d4est_hip_plan_set_geometry was not called");
   unsigned covered = launch_stiffness_all_multi(plan, u, Au);
   if (covered == 0u) covered = launch_stiffness_multi(plan, u, Au) | launch_stiffness_multi_mw(plan, u, Au);
-  size_t bucket_index = 0;
-  for (const Bucket& bk : plan->buckets) {
-    const size_t this_bucket = bucket_index++;
-    if (bk.n_elem == 0) continue;
-    if (this_bucket < 32 && ((covered >> this_bucket) & 1u)) continue;
-    bool done = false;
-    // auto-tuning (measured on MI355X, p = 7): up to ~2 resident rounds (16 one-wave workgroups per CU)
-    // the two-buffer wave kernel wins; for larger buckets the 3-buffer kernel with the metric requested
-    // at entry streams HBM best.  profiles/r01_*_ab.txt
-    const int tw = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_WAVE], tp = plan->tuning[D4EST_HIP_TUNE_STIFFNESS_PREFETCH];
-    const bool affine_ok = bk.affine && plan->tuning[D4EST_HIP_TUNE_AFFINE] != 0;
-    // multi-wave kernels (p >= 8): the affine bucket's six constants per element, or nullptr = stream the metric
-#define D4EST_AFF_ARGS (affine_ok && plan->d_metric_affine ? plan->d_metric_affine + (size_t)6 * bk.elem_offset : (const double*)nullptr), bk.d_w
-    const bool use_wave = (tw < 0) ? (bk.n_elem <= 8192 || affine_ok) : (tw != 0);
-    const bool use_pf = (tp < 0) ? !use_wave : (tp != 0);
-#define X(N_, NQ_)                                                                                              \
-  if (!done && bk.N == N_ && bk.NQ == NQ_) {                                                                    \
-    using C = VolCfg<N_, NQ_>;                                                                                  \
-    if (C::LDS_BYTES <= 160 * 1024) {                                                                           \
-      const int grid = (bk.n_elem + C::EPB - 1) / C::EPB;                                                       \
-      constexpr bool kWave = (NQ_ * NQ_ <= 64);                                                                 \
-      constexpr bool kEven = true;   /* the even-odd contractions take sizes of either parity */                                                   \
-      const bool use_eo = kEven && bk.d_EBf && plan->tuning[D4EST_HIP_TUNE_STIFFNESS_EO] != 0;                  \
-      if (kWave && use_wave) {                                               \
-        launch_stiffness_wave<N_, (kWave ? NQ_ : N_)>(plan, bk, use_pf, u, Au);                                 \
-      } else if (N_ >= 13 && N_ <= 16 && NQ_ == N_ && (plan->tuning[D4EST_HIP_TUNE_STIFFNESS_BIGP] == 2 || (N_ == 16 && plan->tuning[D4EST_HIP_TUNE_STIFFNESS_BIGP] < 0))) { \
-        launch_stiffness_mfma16(plan, bk, u, Au);                                                               \
-      } else if (!kWave && plan->tuning[D4EST_HIP_TUNE_STIFFNESS_BIGP] != 0) {                                  \
-        /* p >= 8: multi-wave workgroup, two LDS fields (sequential field hand-off) -> 1.5x the residency */  \
-        using W = WaveCfg<N_, NQ_>;                                                                             \
-        std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_kernel<%d,%d,false,%s%s> (%d threads)", N_, NQ_, use_eo ? "eo" : "plain", (use_eo && affine_ok && plan->d_metric_affine) ? ",affine" : "", W::THREADS); \
-        if (use_eo) {                                                                                           \
-          if (affine_ok && plan->d_metric_affine) {                                                             \
-            set_lds_limit(stiffness_wave_kernel<N_, NQ_, false, kEven, true>, W::LDS_BYTES);                    \
-            hipLaunchKernelGGL((stiffness_wave_kernel<N_, NQ_, false, kEven, true>), dim3(bk.n_elem), dim3(W::THREADS), W::LDS_BYTES, \
-                               plan->stream, u, Au, plan->d_metric, plan->d_ns_list + bk.elem_offset,           \
-                               plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_EBb, (kMwCollocated<N_, NQ_, false, true> ? bk.d_EDq : bk.d_EGb), bk.d_EBf, (kMwCollocated<N_, NQ_, false, true> ? bk.d_EDqT : bk.d_EGf), 0, D4EST_AFF_ARGS); \
-          } else {                                                                                              \
-          auto go_mw = [&](auto kern) {   /* NT twin: stream mode (plan->stream_mode, d4est_hip_wave.h) */ \
-            set_lds_limit(kern, W::LDS_BYTES); \
-            hipLaunchKernelGGL(kern, dim3(bk.n_elem), dim3(W::THREADS), W::LDS_BYTES, \
-                             plan->stream, u, Au, plan->d_metric, plan->d_ns_list + bk.elem_offset,             \
-                             plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_EBb, (kMwCollocated<N_, NQ_, false, true> ? bk.d_EDq : bk.d_EGb), bk.d_EBf, (kMwCollocated<N_, NQ_, false, true> ? bk.d_EDqT : bk.d_EGf), (plan->tuning[D4EST_HIP_TUNE_STIFFNESS_STAGGER] < 0 ? 0 : plan->tuning[D4EST_HIP_TUNE_STIFFNESS_STAGGER]), (const double*)nullptr, (const double*)nullptr); \
-          }; \
-          if (plan->stream_mode) go_mw(stiffness_wave_kernel<N_, NQ_, false, kEven, false, true>); \
-          else go_mw(stiffness_wave_kernel<N_, NQ_, false, kEven>); \
-          }                                                                                                     \
-        } else {                                                                                                \
-          set_lds_limit(stiffness_wave_kernel<N_, NQ_, false>, W::LDS_BYTES);                                   \
-          hipLaunchKernelGGL((stiffness_wave_kernel<N_, NQ_, false>), dim3(bk.n_elem), dim3(W::THREADS), W::LDS_BYTES, \
-                             plan->stream, u, Au, plan->d_metric, plan->d_ns_list + bk.elem_offset,             \
-                             plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_B, bk.d_G, bk.d_BT, bk.d_GT, 0); \
-        }                                                                                                       \
-      } else {                                                                                                  \
-        constexpr bool kCanPF = (NQ_ <= 8);                                                                     \
-        const bool pf = kCanPF && use_pf;                                                                       \
-        std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_kernel<%d,%d,%s,%s>", N_, NQ_, pf ? "true" : "false", use_eo ? "eo" : "plain"); \
-        const double* o0 = use_eo ? bk.d_EBb : bk.d_B;                                                          \
-        const double* o1 = use_eo ? bk.d_EGb : bk.d_G;                                                          \
-        const double* o2 = use_eo ? bk.d_EBf : bk.d_BT;                                                         \
-        const double* o3 = use_eo ? bk.d_EGf : bk.d_GT;                                                         \
-        auto go = [&](auto kern) {                                                                              \
-          set_lds_limit(kern, C::LDS_BYTES);                                                                    \
-          hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), C::LDS_BYTES, plan->stream, u, Au, plan->d_metric, \
-                             plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, o0, o1, o2, o3); \
-        };                                                                                                      \
-        if (pf && use_eo && plan->stream_mode) go(stiffness_kernel<N_, NQ_, kCanPF, kEven, true>);              \
-        else if (pf && use_eo) go(stiffness_kernel<N_, NQ_, kCanPF, kEven>);                                    \
-        else if (pf) go(stiffness_kernel<N_, NQ_, kCanPF, false>);                                              \
-        else if (use_eo) go(stiffness_kernel<N_, NQ_, false, kEven>);                                           \
-        else go(stiffness_kernel<N_, NQ_, false, false>);                                                       \
-      }                                                                                                         \
-      done = true;                                                                                              \
-    }                                                                                                           \
-  }
-    D4EST_HIP_FAST_PAIRS(X)
-#undef X
-#define X(N_, NQ_)                                                                                              \
-  if (!done && bk.N == N_ && bk.NQ == NQ_ && plan->tuning[D4EST_HIP_TUNE_STIFFNESS_BIGP] != 0) {                \
-    using W = WaveCfg<N_, NQ_>;                                                                                 \
-    static_assert(W::LDS_BYTES <= 160 * 1024, "two-field kernel does not fit the LDS");                         \
-    constexpr bool kEven = true;   /* the even-odd contractions take sizes of either parity */                                                     \
-    const bool use_eo = kEven && bk.d_EBf && plan->tuning[D4EST_HIP_TUNE_STIFFNESS_EO] != 0;                    \
-    std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::stiffness_wave_kernel<%d,%d,false,%s%s> (%d threads)", N_, NQ_, use_eo ? "eo" : "plain", (use_eo && affine_ok && plan->d_metric_affine) ? ",affine" : "", W::THREADS); \
-    if (use_eo) {                                                                                               \
-      if (affine_ok && plan->d_metric_affine) {                                                                 \
-        set_lds_limit(stiffness_wave_kernel<N_, NQ_, false, kEven, true>, W::LDS_BYTES);                        \
-        hipLaunchKernelGGL((stiffness_wave_kernel<N_, NQ_, false, kEven, true>), dim3(bk.n_elem), dim3(W::THREADS), W::LDS_BYTES, \
-                           plan->stream, u, Au, plan->d_metric, plan->d_ns_list + bk.elem_offset,               \
-                           plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_EBb, (kMwCollocated<N_, NQ_, false, true> ? bk.d_EDq : bk.d_EGb), bk.d_EBf, (kMwCollocated<N_, NQ_, false, true> ? bk.d_EDqT : bk.d_EGf), 0, D4EST_AFF_ARGS); \
-      } else {                                                                                                  \
-      auto go_mw = [&](auto kern) {   /* NT twin: stream mode (plan->stream_mode, d4est_hip_wave.h) */ \
-        set_lds_limit(kern, W::LDS_BYTES); \
-        hipLaunchKernelGGL(kern, dim3(bk.n_elem), dim3(W::THREADS), W::LDS_BYTES, \
-                         plan->stream, u, Au, plan->d_metric, plan->d_ns_list + bk.elem_offset,                 \
-                         plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_EBb, (kMwCollocated<N_, NQ_, false, true> ? bk.d_EDq : bk.d_EGb), bk.d_EBf, (kMwCollocated<N_, NQ_, false, true> ? bk.d_EDqT : bk.d_EGf), (plan->tuning[D4EST_HIP_TUNE_STIFFNESS_STAGGER] < 0 ? 0 : plan->tuning[D4EST_HIP_TUNE_STIFFNESS_STAGGER]), (const double*)nullptr, (const double*)nullptr); \
-      }; \
-      if (plan->stream_mode) go_mw(stiffness_wave_kernel<N_, NQ_, false, kEven, false, true>); \
-      else go_mw(stiffness_wave_kernel<N_, NQ_, false, kEven>); \
-      }                                                                                                         \
-    } else {                                                                                                    \
-      set_lds_limit(stiffness_wave_kernel<N_, NQ_, false, false>, W::LDS_BYTES);                                \
-      hipLaunchKernelGGL((stiffness_wave_kernel<N_, NQ_, false, false>), dim3(bk.n_elem), dim3(W::THREADS), W::LDS_BYTES, \
-                         plan->stream, u, Au, plan->d_metric, plan->d_ns_list + bk.elem_offset,                 \
-                         plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_B, bk.d_G, bk.d_BT, bk.d_GT, 0);     \
-    }                                                                                                           \
-    done = true;                                                                                                \
-  }
-    D4EST_HIP_BIG_PAIRS(X)
-#undef X
-#undef D4EST_AFF_ARGS
-    if (!done) {
-      std::snprintf(plan->last_kernel, sizeof(plan->last_kernel), "d4est_hip::generic_volume_kernel (N=%d,NQ=%d)", bk.N, bk.NQ);
-      launch_generic(plan, bk, 3, u, Au);
-    }
-  }
+  for_each_uncovered_bucket(plan, covered, [&](const Bucket& bk) {
+    const StiffnessChoice c = stiffness_choice(plan, bk);
+    if (c.family == StiffnessFamily::generic) return launch_stiffness_generic(plan, bk, u, Au);
+    if (c.family == StiffnessFamily::mfma16) return launch_stiffness_mfma16(plan, bk, c, u, Au);
+    for_built_pair(bk.N, bk.NQ, [&](auto n, auto nq) {
+      constexpr int N = decltype(n)::value, NQ = decltype(nq)::value;
+      // (a run-time test, as it always was: the multi-wave instances of the one-wavefront pairs stay in the code object)
+      if (c.family == StiffnessFamily::multi_wave) launch_stiffness_mw<N, NQ>(plan, bk, c, u, Au);
+      if constexpr (NQ * NQ <= 64) {
+        if (c.family == StiffnessFamily::single_wave) launch_stiffness_wave<N, NQ>(plan, bk, c, u, Au);
+      }
+      if constexpr (!kBigPair<N>) {
+        if (c.family == StiffnessFamily::three_field) launch_stiffness_3field<N, NQ>(plan, bk, c, u, Au);
+      }
+    });
+  });
   HIP_CHECK(hipGetLastError());
 }
 
 // which = 0: the quadrature interpolation B; 1: B^-1 (inverse mass); 2: 1-D mass M; 3: M^-1 (square nodal applies)
 template <int MODE>
 static void launch_mass_like_mode(d4est_hip_plan* plan, const double* in, double* out, const double* coeff, int which) {
+  const bool use_eo = which == 0 && plan->tuning[D4EST_HIP_TUNE_STIFFNESS_EO] != 0;
   unsigned covered = 0u;
   if constexpr (MODE == 0 || MODE == 3) {
-    if (which == 0 && plan->tuning[D4EST_HIP_TUNE_STIFFNESS_EO] != 0) {   // mixed-degree plans: one launch for the deg_quad = deg <= 7 buckets
+    if (use_eo) {   // mixed-degree plans: one launch for the deg_quad = deg <= 7 buckets
       WaveEoMulti A;
       size_t lds = 0;
-      int wgs = 0;
-      for (size_t i = 0; i < plan->buckets.size() && i < 32; ++i) {
+      for (size_t i = 0; i < plan->buckets.size(); ++i) {
         const Bucket& bk = plan->buckets[i];
-        if (bk.n_elem == 0 || bk.N != bk.NQ || bk.N < 2 || bk.N > 8 || !bk.d_EBf || A.n == WaveEoMulti::MAXB) continue;
-        size_t l = 0;
-        int epb = 1;
-#define X(N_) if (bk.N == N_) { l = WaveCfg<N_, N_>::LDS_BYTES; epb = WaveCfg<N_, N_>::EPB; }
-        X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-#undef X
-        lds = std::max(lds, l);
-        wgs += (bk.n_elem + epb - 1) / epb;
-        const int j = A.n++;
-        A.wg_end[j] = wgs; A.N[j] = bk.N; A.n_elem[j] = bk.n_elem; A.elem_offset[j] = bk.elem_offset;
-        A.EBf[j] = bk.d_EBf; A.EBb[j] = bk.d_EBb; A.wq[j] = bk.d_w;
-        covered |= 1u << i;
+        if (!bucket_single_wave_eo(bk) || !multi_append(A, covered, i, bk, bucket_workgroups(bk))) continue;
+        lds = std::max(lds, wave_cfg_square(bk.N).lds_bytes);
       }
       if (A.n >= 2)
-        hipLaunchKernelGGL((mass_like_multi_kernel<MODE>), dim3(wgs), dim3(64), lds, plan->stream, in, out, plan->d_J, plan->d_ns_list,
-                           plan->d_qs_list, coeff, A);
+        hipLaunchKernelGGL((mass_like_multi_kernel<MODE>), dim3(multi_workgroups(A)), dim3(64), lds, plan->stream, in, out, plan->d_J,
+                           plan->d_ns_list, plan->d_qs_list, coeff, A);
       else
         covered = 0u;
     }
   }
-  size_t bucket_index = 0;
-  for (const Bucket& bk : plan->buckets) {
-    const size_t this_bucket = bucket_index++;
-    if (bk.n_elem == 0) continue;
-    if (this_bucket < 32 && ((covered >> this_bucket) & 1u)) continue;
+  for_each_uncovered_bucket(plan, covered, [&](const Bucket& bk) {
     if (which == 1 && bk.N != bk.NQ) D4EST_HIP_ABORT("apply_inverse_mass_matrix needs deg_quad == deg (reference asserts the same, d4est_quadrature.c:1233)");
     const double* op = which == 0 ? bk.d_B : (which == 1 ? bk.d_BinvT : (which == 2 ? bk.d_M : bk.d_Minv));
     const double* opT = which == 0 ? bk.d_BT : (which == 1 ? bk.d_Binv : (which == 2 ? bk.d_MT : bk.d_MinvT));
@@ -1909,32 +1883,19 @@ static void launch_mass_like_mode(d4est_hip_plan* plan, const double* in, double
     const int* qs_list = (which >= 2) ? plan->d_ns_list + bk.elem_offset : plan->d_qs_list + bk.elem_offset;
     const int NQe = (which >= 2) ? bk.N : bk.NQ;
     const double* wts = (which == 1) ? bk.d_wGL : bk.d_w;  // the inverse mass is always Gauss-Legendre (d4est_quadrature.c:1239-1241)
-    bool done = false;
-#define X(N_, NQ_)                                                                                                    \
-  if (!done && bk.N == N_ && NQe == NQ_) {                                                                            \
-    using C = WaveCfg<N_, NQ_>;                                                                                       \
-    if (C::LDS_BYTES <= 160 * 1024) {                                                                                 \
-      const int grid = (bk.n_elem + C::EPB - 1) / C::EPB;                                                             \
-      constexpr bool kEven = true;   /* the even-odd contractions take sizes of either parity */                                                         \
-      if (kEven && which == 0 && bk.d_EBf && plan->tuning[D4EST_HIP_TUNE_STIFFNESS_EO] != 0) {                        \
-        set_lds_limit(mass_like_kernel<N_, NQ_, MODE, kEven>, C::LDS_BYTES);                                          \
-        hipLaunchKernelGGL((mass_like_kernel<N_, NQ_, MODE, kEven>), dim3(grid), dim3(C::THREADS), C::LDS_BYTES, plan->stream, \
-                           in, out, plan->d_J, plan->d_ns_list + bk.elem_offset, qs_list, bk.n_elem, bk.d_EBb, bk.d_EBf, wts, \
-                           coeff);                                                                                    \
-      } else {                                                                                                        \
-        set_lds_limit(mass_like_kernel<N_, NQ_, MODE, false>, C::LDS_BYTES);                                          \
-        hipLaunchKernelGGL((mass_like_kernel<N_, NQ_, MODE, false>), dim3(grid), dim3(C::THREADS), C::LDS_BYTES, plan->stream, \
-                           in, out, plan->d_J, plan->d_ns_list + bk.elem_offset, qs_list, bk.n_elem, op, opT, wts,     \
-                           coeff);                                                                                    \
-      }                                                                                                               \
-      done = true;                                                                                                    \
-    }                                                                                                                 \
-  }
-    D4EST_HIP_FAST_PAIRS(X)
-    D4EST_HIP_BIG_PAIRS(X)
-#undef X
-    if (!done) launch_generic(plan, bk, MODE == 3 ? 4 : (MODE == 4 ? 5 : MODE), in, out, coeff, op, qs_list, NQe, wts);
-  }
+    const bool built = for_built_pair(bk.N, NQe, [&](auto n, auto nq) {
+      constexpr int N = decltype(n)::value, NQ = decltype(nq)::value;
+      using C = WaveCfg<N, NQ>;
+      auto go = [&](auto kern, const double* fwd, const double* bwd) {
+        set_lds_limit(kern, C::LDS_BYTES);
+        hipLaunchKernelGGL(kern, dim3((bk.n_elem + C::EPB - 1) / C::EPB), dim3(C::THREADS), C::LDS_BYTES, plan->stream, in, out, plan->d_J,
+                           plan->d_ns_list + bk.elem_offset, qs_list, bk.n_elem, fwd, bwd, wts, coeff);
+      };
+      if (use_eo && bk.d_EBf) go(mass_like_kernel<N, NQ, MODE, true>, bk.d_EBb, bk.d_EBf);
+      else go(mass_like_kernel<N, NQ, MODE, false>, op, opT);
+    });
+    if (!built) launch_generic(plan, bk, MODE == 3 ? 4 : (MODE == 4 ? 5 : MODE), in, out, coeff, op, qs_list, NQe, wts);
+  });
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1978,31 +1939,23 @@ void launch_stiffness_view(d4est_hip_plan* plan, const double* u, double* Au, in
 }
 
 void launch_dudr(d4est_hip_plan* plan, const double* u, double* d0, double* d1, double* d2) {
-  for (const Bucket& bk : plan->buckets) {
-    if (bk.n_elem == 0) continue;
-    bool done = false;
-#define X(N_, NQ_)                                                                                         \
-  if (!done && N_ == NQ_ && bk.N == N_) {                                                                  \
-    using C = WaveCfg<N_, N_>;                                                                               \
-    if (C::LDS_BYTES <= 160 * 1024) {                                                                      \
-      set_lds_limit(dudr_kernel<N_>, C::LDS_BYTES);                                                        \
-      const int grid = (bk.n_elem + C::EPB - 1) / C::EPB;                                                  \
-      hipLaunchKernelGGL((dudr_kernel<N_>), dim3(grid), dim3(C::THREADS), C::LDS_BYTES, plan->stream, u,   \
-                         d0, d1, d2, plan->d_ns_list + bk.elem_offset, bk.n_elem, bk.d_DT);                                                                          \
-      done = true;                                                                                         \
-    }                                                                                                      \
-  }
-    D4EST_HIP_FAST_PAIRS(X)
-    D4EST_HIP_BIG_PAIRS(X)
-#undef X
-    if (!done) {
+  for_each_uncovered_bucket(plan, 0u, [&](const Bucket& bk) {
+    const bool built = for_built_pair(bk.N, bk.N, [&](auto n, auto) {   // (du/dr has no quadrature side: the square pair of bk.N)
+      constexpr int N = decltype(n)::value;
+      using C = WaveCfg<N, N>;
+      set_lds_limit(dudr_kernel<N>, C::LDS_BYTES);
+      hipLaunchKernelGGL((dudr_kernel<N>), dim3((bk.n_elem + C::EPB - 1) / C::EPB), dim3(C::THREADS), C::LDS_BYTES, plan->stream, u, d0, d1,
+                         d2, plan->d_ns_list + bk.elem_offset, bk.n_elem, bk.d_DT);
+    });
+    if (!built) {
       const int grid = bk.n_elem < 2048 ? bk.n_elem : 2048;
       hipLaunchKernelGGL(generic_dudr_kernel, dim3(grid), dim3(256), 0, plan->stream, u, d0, d1, d2,
                          plan->d_ns_list + bk.elem_offset, bk.n_elem, bk.N, bk.d_D);
     }
-  }
+  });
   HIP_CHECK(hipGetLastError());
 }
+
 
 // ---------------------------------------------------------------------------
 // Geometric factors of the reference's `brick` geometry generated on the device (brick only):

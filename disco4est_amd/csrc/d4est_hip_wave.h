@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace d4est_hip {
 
 // The 1-D operator entries are wave-uniform: they are fetched with scalar loads
@@ -524,6 +526,50 @@ struct WaveCfg {
   static constexpr int LDS_PER_ELEM = 2 * FS;
   static constexpr size_t LDS_BYTES = (size_t)EPB * LDS_PER_ELEM * sizeof(double);
 };
+
+// WaveCfg<N, N> from a run-time N: what the mixed-degree launches need of each bucket (LDS of the launch = the largest bucket's)
+struct WaveCfgSquare {
+  size_t lds_bytes;
+  int epb;   // elements per workgroup
+};
+constexpr WaveCfgSquare wave_cfg_square(int N) {
+  const int epb = (N * N <= 64) ? 64 / (N * N) : 1;
+  return {(size_t)epb * 2 * (N * N * (N | 1)) * sizeof(double), epb};
+}
+template <int N>
+constexpr bool wave_cfg_square_agrees() {
+  static_assert(wave_cfg_square(N).lds_bytes == WaveCfg<N, N>::LDS_BYTES && wave_cfg_square(N).epb == WaveCfg<N, N>::EPB, "wave_cfg_square");
+  if constexpr (N > 2) return wave_cfg_square_agrees<N - 1>();
+  return true;
+}
+static_assert(wave_cfg_square_agrees<13>(), "N = 2 .. 13: every degree a mixed-degree launch takes");
+
+// The (deg + 1, deg_quad + 1) pairs with compiled volume kernels (stiffness, the mass-like applies, du/dr, the fused nonlinear term); every
+// other pair takes the generic kernels.
+#define D4EST_HIP_FAST_PAIRS(X) \
+  X(2, 2) X(3, 3) X(4, 4) X(5, 5) X(6, 6) X(7, 7) X(8, 8) X(9, 9) X(10, 10) X(11, 11) X(12, 12) \
+  X(13, 13) X(14, 14) X(15, 15) X(16, 16)                                                       \
+  X(2, 3) X(3, 4) X(4, 5) X(8, 9) X(3, 6) X(4, 6) X(8, 10)
+// p = 16 .. 19 (the reference's tables stop at 20 Lobatto points): only the two-field multi-wave kernels fit the 160 KB LDS
+#define D4EST_HIP_BIG_PAIRS(X) X(17, 17) X(18, 18) X(19, 19) X(20, 20)
+template <int N>
+inline constexpr bool kBigPair = N > 16;
+
+// f(integral_constant N, integral_constant NQ) for the pair of the two lists that matches; false (f not called) when there is none
+template <class F>
+inline bool for_built_pair(int N, int NQ, F&& f) {
+#define X(N_, NQ_)                                                                                             \
+  if (N == N_ && NQ == NQ_) {                                                                                  \
+    static_assert(WaveCfg<N_, NQ_>::LDS_BYTES <= 160 * 1024, "the two-field LDS image of a built pair fits");  \
+    f(std::integral_constant<int, N_>{}, std::integral_constant<int, NQ_>{});                                  \
+    return true;                                                                                               \
+  }
+  D4EST_HIP_FAST_PAIRS(X)
+  D4EST_HIP_BIG_PAIRS(X)
+#undef X
+  return false;
+}
+inline bool pair_built(int N, int NQ) { return for_built_pair(N, NQ, [](auto, auto) {}); }
 
 // ---------------------------------------------------------------------------
 // The sum-factorised stiffness apply of ONE element by the NQ*NQ lanes `te` of a wavefront in the even-odd form (derivation, table

@@ -91,17 +91,20 @@ def _macro_pairs(source, macro):
 
 
 def test_sweep_covers_the_compiled_pairs():
-    """tests/test_nonlinear_sweep_gpu.py launches what D4EST_HIP_NONLIN_PAIRS compiles, no more and no less; the macro is the union of
-    the two pair lists of the Galerkin integral's one-kernel path, as its comment says; and every listed pair fits pair_built's LDS limit
-    (WaveCfg::LDS_BYTES = 2 EPB NQ^2 (NQ | 1) doubles), so none of them silently composes"""
+    """tests/test_nonlinear_sweep_gpu.py launches what the fused nonlinear kernels are compiled for, no more and no less: the two pair
+    lists of d4est_hip_wave.h, which the nonlinear unit and the Galerkin integral's one-kernel path both walk through for_built_pair (the
+    nonlinear unit keeps no list of its own); and every listed pair fits pair_built's LDS limit (WaveCfg::LDS_BYTES = 2 EPB NQ^2 (NQ | 1)
+    doubles), so none of them silently composes"""
     from tests.test_nonlinear_sweep_gpu import PAIRS, elements_per_workgroup
-    nonlin = _macro_pairs("d4est_hip_nonlinear.hip", "D4EST_HIP_NONLIN_PAIRS")
+    fast = _macro_pairs("d4est_hip_wave.h", "D4EST_HIP_FAST_PAIRS")
+    big = _macro_pairs("d4est_hip_wave.h", "D4EST_HIP_BIG_PAIRS")
+    assert not set(fast) & set(big) and len(fast + big) == len(set(fast + big))
+    nonlin = fast + big
     assert len(nonlin) == len(set(nonlin)) == 26
     assert PAIRS == nonlin
-    fast = _macro_pairs("d4est_hip_volume.hip", "D4EST_HIP_FAST_PAIRS")
-    big = _macro_pairs("d4est_hip_volume.hip", "D4EST_HIP_BIG_PAIRS")
-    assert not set(fast) & set(big) and len(fast + big) == len(set(fast + big))
-    assert set(nonlin) == set(fast) | set(big)
+    for unit in ("d4est_hip_nonlinear.hip", "d4est_hip_volume.hip"):
+        txt = open(os.path.join(ROOT, "disco4est_amd", "csrc", unit)).read()
+        assert "for_built_pair(" in txt and not re.search(r"^#define\s+D4EST_HIP_\w*PAIRS", txt, flags=re.M), unit
     for N, NQ in nonlin:
         assert 2 <= N <= NQ
         assert elements_per_workgroup(NQ) == max(1, 64 // (NQ * NQ))

@@ -1,5 +1,5 @@
 """GPU sweep over EVERY compile-time instance of the fused nonlinear kernels (csrc/d4est_hip_nonlinear.hip): the 26 (N, NQ) pairs of
-D4EST_HIP_NONLIN_PAIRS in the term form (d4est_hip_apply_nonlinear_term) and in the coefficient form (d4est_hip_plan_linearise, read
+D4EST_HIP_FAST_PAIRS and D4EST_HIP_BIG_PAIRS (csrc/d4est_hip_wave.h) in the term form (d4est_hip_apply_nonlinear_term) and in the coefficient form (d4est_hip_plan_linearise, read
 back through d4est_hip_plan_lhs_coefficient_arrays), the branches of the host dispatcher launch_fused (the multi launch next to
 per-bucket launches, one equal-order bucket, no bucket for the multi kernel, a bucket without a pair, MAXB buckets), ragged last
 workgroups, Lobatto quadrature, a hanging mesh, a partition, an empty plan, and the zeroth-order term of apply_lhs on its own scale.
@@ -25,7 +25,7 @@ ELEM_RTOL = 20 * RTOL
 GUARD = 64
 SENTINEL = -1.2345678e77
 
-# D4EST_HIP_NONLIN_PAIRS, in the macro's order: (deg + 1, deg_quad + 1)
+# D4EST_HIP_FAST_PAIRS then D4EST_HIP_BIG_PAIRS, in the macros' order: (deg + 1, deg_quad + 1)
 PAIRS = [(2, 2), (3, 3), (4, 4), (5, 5), (6, 6), (7, 7), (8, 8), (9, 9), (10, 10), (11, 11), (12, 12), (13, 13), (14, 14), (15, 15),
          (16, 16), (2, 3), (3, 4), (4, 5), (8, 9), (3, 6), (4, 6), (8, 10), (17, 17), (18, 18), (19, 19), (20, 20)]
 # (k, with b): the powers of the shipped problems (u^5; (b + u)^-7 and its derivative's -8) and the degenerate k = 1, 0

@@ -124,6 +124,93 @@ def run_case(name, make, tune, extra, dev, mark):
         del ex
 
 
+# ---- the volume unit (d4est_hip_volume.hip, the fused term of d4est_hip_nonlinear.hip): `--volume`
+# One plan per (degrees, deg_quad - deg, level, straight / curved); on it apply_stiffness_matrix under every listed tuning (key: value),
+# then the mass-like applies, du/dr and the fused nonlinear term with tuning key 6 at -1 and 0.  Per apply: last_kernel() and the SHA-256
+# of every output.  D4EST_HIP_STIFFNESS_SPLIT_LAUNCH is read once per process: run `--volume mixed` again with it set.
+def _grid(**keys):
+    """every combination of the values listed per tuning key, as {key: value} dicts"""
+    out = [{}]
+    for k, vals in keys.items():
+        out = [{**t, int(k[1:]): v} for t in out for v in vals]
+    return out
+
+
+WAVE_TUNINGS = [{0: a, 1: b, 7: 0, 16: e} for a, b in ((-1, -1), (0, 0), (1, 0), (0, 1), (1, 1), (0, 2), (0, 3), (0, 11), (0, 12)) for e in (1, 0)]
+AFFINE_TOO = [{0: a, 1: b, 16: e} for a, b in ((-1, -1), (0, 0), (0, 11), (0, 12), (0, 3)) for e in (1, 0)]
+BIG_TUNINGS = _grid(k4=(-1, 0, 1, 2), k6=(-1, 0), k12=(1, 0))
+ALTERNATE = lambda a, b: np.where(np.arange(8) % 2 == 0, a, b).astype(np.int32)   # noqa: E731
+VOLUME_CASES = (
+    [("wave", deg, inc, 1, WAVE_TUNINGS + AFFINE_TOO) for deg in (1, 3, 5, 6, 7) for inc in (0, 1, 2)]
+    + [("multiwave", deg, 0, 1, BIG_TUNINGS) for deg in (8, 9, 11, 12, 13, 14, 15)]
+    + [("big", deg, 0, 1, _grid(k4=(-1, 0), k6=(-1, 0))) for deg in (16, 19)]
+    + [("generic", 20, 0, 0, [{}])]
+    + [("mixed", ALTERNATE(a, b), 0, 1, [{}, {7: 0}, {16: 1}, {1: 12}, {12: 1}, {4: 0}, {6: 0}]) for a, b in ((3, 4), (9, 11), (9, 12), (8, 10), (11, 12), (3, 9))]
+    + [("threshold", deg, 0, 5, [{}, {7: 0}, {0: 0}]) for deg in (1, 3)]
+)
+
+
+def run_volume_case(kind, deg, inc, level, tunings, dev, mark):
+    for curved in ((True,) if kind == "threshold" else (False, True)):
+        m = M.BrickMesh(level, deg, inc)
+        J, rst = m.geometry(M.SineMap(0.05) if curved else None)
+        plan = Plan(m.deg, m.deg_quad, m.nodal_stride, m.quad_stride, m.quad_type)
+        plan.set_geometry(J, rst)
+        u = torch.from_numpy(m.field()).to(dev)
+        fq = torch.from_numpy(1.0 + M.splitmix64_uniform(7, m.local_nodes_quad)).to(dev)
+        name = "volume-%s p%s+%d level %d %s" % (kind, deg if np.isscalar(deg) else "%d/%d" % (deg[0], deg[1]), inc, level, "curved" if curved else "straight")
+        mark.zero_()
+        print("%s: %d elements" % (name, m.n_elements), flush=True)
+        for tune in tunings:
+            for k in (0, 1, 4, 6, 7, 12, 16):
+                plan.set_tuning(k, tune.get(k, -1))
+            out = torch.full_like(u, float("nan"))
+            plan.apply_stiffness_matrix(u, out)
+            print("  stiffness %-44s Au %s  [%s]" % (sorted(tune.items()), sha(out), plan.last_kernel()), flush=True)
+        for k in (0, 1, 4, 7, 12, 16):
+            plan.set_tuning(k, -1)
+        for key6 in (-1, 0):
+            plan.set_tuning(6, key6)
+            n, q = torch.full_like(u, float("nan")), torch.full_like(fq, float("nan"))
+            line = []
+            for label, call, res in (("mass", lambda: plan.apply_mass_matrix(u, n), n), ("galerkin", lambda: plan.apply_galerkin_integral(fq, n), n),
+                                     ("interpolate", lambda: plan.interpolate(u, q), q), ("weighted", lambda: plan.apply_weighted_mass_matrix(u, fq, n), n),
+                                     ("mij", lambda: plan.apply_mij(u, n), n), ("invmij", lambda: plan.apply_invmij(u, n), n)):
+                call()
+                line.append("%s %s" % (label, sha(res)))
+            if inc == 0:   # (the inverse mass needs deg_quad = deg)
+                plan.apply_inverse_mass_matrix(u, n)
+                line.append("invmass %s" % sha(n))
+            d = [torch.full_like(u, float("nan")) for _ in range(3)]
+            plan.compute_dudr(u, *d)
+            line += ["dudr%d %s" % (i, sha(t)) for i, t in enumerate(d)]
+            plan.set_nonlinear_power(fq, None, 3)
+            plan.apply_nonlinear_term(u, n)
+            line.append("nonlinear(fused %d) %s" % (plan.nonlinear_fused(), sha(n)))
+            print("  key 6 = %2d: %s" % (key6, "  ".join(line)), flush=True)
+        plan.destroy()
+
+
+def digest(listing):
+    """a listing of this tool, one line per case: the case's heading, how many result lines follow it and the SHA-256 of those lines
+    (short enough to commit and to read; two listings agree exactly when their digests do); the distinct last_kernel strings after it"""
+    cases, kernels = [], {}
+    for line in open(listing):
+        if not line.strip() or line.startswith("#"):
+            continue
+        if not line.startswith(" "):
+            cases.append([line.strip(), 0, hashlib.sha256()])
+            continue
+        cases[-1][1] += 1
+        cases[-1][2].update(line.encode())
+        if line.rstrip().endswith("]") and "[d4est_hip::" in line:
+            name = line[line.index("[d4est_hip::") + 1:line.rstrip().rindex("]")]
+            kernels[name] = kernels.get(name, 0) + 1
+    for head, n, h in cases:
+        print("%s | %d lines | %s" % (head, n, h.hexdigest()))
+    print("last_kernel strings:\n%s" % "\n".join("  %4d x %s" % (n, name) for name, n in sorted(kernels.items())))
+
+
 def launches(trace_csv):
     """the library's launches in the kernel trace of one run (rocprofv3 --kernel-trace --output-format csv), in dispatch order: (queue,
     name, grid, workgroup, LDS bytes); queues are numbered by first appearance, their ids differ from process to process.  torch's own
@@ -154,13 +241,23 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
     ap.add_argument("--compare", nargs=2, metavar="TRACE_CSV", default=None, help="compare two kernel traces of this tool instead of running")
+    ap.add_argument("--volume", nargs="*", metavar="KIND", default=None,
+                    help="the volume unit's cases instead of the operator's (all kinds, or of wave multiwave big generic mixed threshold)")
+    ap.add_argument("--digest", metavar="LISTING", default=None, help="one line per case of a listing this tool printed, instead of running")
     args = ap.parse_args()
     if args.compare:
         sys.exit(compare(*args.compare))
+    if args.digest:
+        return digest(args.digest)
     if not torch.cuda.is_available():
         sys.exit("launch_sequence: no GPU")
     dev = torch.device("cuda:0")
     mark = torch.ones(12345, dtype=torch.float64, device=dev)
+    if args.volume is not None:
+        for case in VOLUME_CASES:
+            if not args.volume or case[0] in args.volume:
+                run_volume_case(*case, dev, mark)
+        return
     for name, make, tune, extra in CASES:
         if args.only is None or name in args.only:
             run_case(name, make, tune, extra, dev, mark)
