@@ -140,6 +140,8 @@ SIGNATURES = {
     "d4est_hip_cg_solve_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_double_p]),
     "d4est_hip_fcg_solve": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp, _vp, _c_double_p]),
     "d4est_hip_plan_set_nonlinear_power": (None, [_vp, _vp, _vp, ctypes.c_int]),
+    "d4est_hip_plan_set_nonlinear_abs_power": (None, [_vp, _vp, _vp, ctypes.c_double]),
+    "d4est_hip_plan_nonlinear_exponent": (ctypes.c_int, [_vp, _vp]),
     "d4est_hip_apply_nonlinear_term": (None, [_vp, _vp, ctypes.c_int, _vp]),
     "d4est_hip_plan_nonlinear_fused": (ctypes.c_int, [_vp]),
     "d4est_hip_plan_linearise": (None, [_vp, _vp]),
@@ -245,6 +247,16 @@ SIGNATURES = {
     "d4est_hip_plan_set_cds_term_analytic": (None, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double]),
     "d4est_hip_plan_set_cds_term_xyz": (None, [_vp, _vp, ctypes.c_int, _vp]),
     "d4est_hip_plan_nonlinear_coefficients": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "d4est_hip_plan_set_okendon_term_brick": (None, [_vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_double, _vp]),
+    "d4est_hip_plan_set_okendon_term_analytic": (None, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double]),
+    "d4est_hip_plan_set_okendon_term_xyz": (None, [_vp, _vp, ctypes.c_int, _vp]),
+    "d4est_hip_plan_set_boyen_york_term_brick": (None, [_vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_double, _vp]),
+    "d4est_hip_plan_set_boyen_york_term_analytic": (None, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double]),
+    "d4est_hip_plan_set_boyen_york_term_xyz": (None, [_vp, _vp, ctypes.c_int, _vp]),
+    "d4est_hip_plan_build_load_by_id_brick": (None, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_double, _vp, ctypes.c_int, _vp]),
+    "d4est_hip_plan_build_load_by_id_analytic": (None, [_vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
+                                                        ctypes.c_double, ctypes.c_int, _vp]),
+    "d4est_hip_plan_build_load_by_id_xyz": (None, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp]),
     "d4est_hip_plan_compute_boundary_xyz_brick": (None, [_vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
     "d4est_hip_plan_compute_boundary_xyz_analytic": (None, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double, _vp]),
     "d4est_hip_plan_set_robin_by_id_brick": (None, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_double, _vp]),
@@ -252,8 +264,9 @@ SIGNATURES = {
 }
 
 # problem fields and Robin callbacks by id (D4EST_HIP_FIELD_* / D4EST_HIP_ROBIN_*)
-FIELD = {"PUNCTURE_K2": 0, "PUNCTURE_A": 1, "PUNCTURE_B": 2, "CDS_A": 3, "CDS_PSI": 4, "INV_R": 5}
-ROBIN_COEFF = {"INV_R": 0, "BRICK": 1}
+FIELD = {"PUNCTURE_K2": 0, "PUNCTURE_A": 1, "PUNCTURE_B": 2, "CDS_A": 3, "CDS_PSI": 4, "INV_R": 5, "OKENDON_U": 6, "BY_PSI": 7, "BY_A": 8,
+         "LORENTZIAN_U": 9, "LORENTZIAN_RHS": 10, "LORENTZIAN_ROBIN": 11, "STAMM_U": 12, "STAMM_RHS": 13}
+ROBIN_COEFF = {"INV_R": 0, "BRICK": 1, "LORENTZIAN": 2}
 ROBIN_RHS = {"ZERO": 0, "INV_R": 1}
 MAX_PUNCTURES = 10
 
@@ -267,16 +280,38 @@ def puncture_params(C, P, S, M, puncture_eps=1e-15):
     return np.concatenate([[float(n), float(puncture_eps)], np.concatenate([C, P, S, M[:, None]], axis=1).reshape(-1)])
 
 
+def okendon_params(p):
+    """the parameter vector of OKENDON_U and the Okendon term: {p}, 0 < p < 1"""
+    assert 0.0 < float(p) < 1.0
+    return np.array([float(p)])
+
+
+def boyen_york_params(a, P):
+    """the parameter vector of BY_PSI, BY_A and the Boyen-York term: {a, P}"""
+    return np.array([float(a), float(P)])
+
+
+def stamm_params(c2x, c2y, c2z):
+    """the parameter vector of STAMM_U and STAMM_RHS: {c2x, c2y, c2z}"""
+    return np.array([float(c2x), float(c2y), float(c2z)])
+
+
 def _field_params(field_id, params):
     fid = FIELD[field_id] if isinstance(field_id, str) else int(field_id)
-    assert 0 <= fid <= 5, "unknown field id"
-    if fid == 5:
+    assert 0 <= fid <= 13, "unknown field id"
+    if fid == 5 or 9 <= fid <= 11:
         return fid, np.zeros(1), 0
     pr = np.ascontiguousarray(params, dtype=np.float64).reshape(-1)
     if fid <= 2:
         assert pr.size >= 2 and pr[0] == int(pr[0]) and 1 <= pr[0] < MAX_PUNCTURES and pr.size == 2 + 10 * int(pr[0]), "puncture params"
-    else:
+    elif fid <= 4:
         assert pr.size == 8, "star params: cx, cy, cz, R, rho0, C0, alpha, beta"
+    elif fid == 6:
+        assert pr.size == 1 and 0.0 < pr[0] < 1.0, "Okendon params: p, 0 < p < 1"
+    elif fid <= 8:
+        assert pr.size == 2, "Boyen-York params: a, P"
+    else:
+        assert pr.size == 3, "Stamm params: c2x, c2y, c2z"
     return fid, pr, pr.size
 
 
@@ -968,6 +1003,19 @@ class Plan:
         self.lib.d4est_hip_plan_set_nonlinear_power(self.handle, _ptr(a_quad) if a_quad is not None else None,
                                                     _ptr(b_quad) if b_quad is not None else None, int(k))
 
+    def set_nonlinear_abs_power(self, a_quad, b_quad, s):
+        """registers the real form f(x, u) = a |b + u|^s (Jacobian s a |b + u|^(s-1)), evaluated as a pow(t t, s/2), t = b + V u;
+        tensors and capture as set_nonlinear_power.  Setting either form clears the other"""
+        for t in (a_quad, b_quad):
+            assert t is None or t.numel() == self.local_nodes_quad
+        self.lib.d4est_hip_plan_set_nonlinear_abs_power(self.handle, _ptr(a_quad) if a_quad is not None else None,
+                                                        _ptr(b_quad) if b_quad is not None else None, float(s))
+
+    def nonlinear_exponent(self):
+        """s of the real form that is set, or None (the integer form, or no term)"""
+        s = ctypes.c_double(0.0)
+        return s.value if self.lib.d4est_hip_plan_nonlinear_exponent(self.handle, ctypes.byref(s)) else None
+
     def apply_nonlinear_term(self, u, out, beta=0):
         """out = beta out + V^T W J a (b + V u)^k (beta 0 or 1), one kernel where nonlinear_fused() holds"""
         assert u.numel() == self.local_nodes and out.numel() == self.local_nodes
@@ -1069,6 +1117,33 @@ class Plan:
         set_puncture_term; afterwards the plan is as set_nonlinear_power(a, None, 5) leaves it"""
         self._set_term("cds", "CDS_A", params, brick, analytic, xyz)
 
+    def set_okendon_term(self, params, brick=None, analytic=None, xyz=None):
+        """the Okendon term |u|^p (capi.okendon_params): a = 1, b = 0, the real form with s = p; sources as set_puncture_term;
+        afterwards the plan is as set_nonlinear_abs_power(a, None, p) leaves it"""
+        self._set_term("okendon", "OKENDON_U", params, brick, analytic, xyz)
+
+    def set_boyen_york_term(self, params, brick=None, analytic=None, xyz=None):
+        """the Boyen-York term a u^-7, a = BY_A (capi.boyen_york_params); sources as set_puncture_term; afterwards the plan is as
+        set_nonlinear_power(a, None, -7) leaves it"""
+        self._set_term("boyen_york", "BY_A", params, brick, analytic, xyz)
+
+    def build_load(self, field_id, params, out, beta=0, brick=None, analytic=None, xyz=None):
+        """out = beta out + V^T W J f(x_quad), f a problem field (capi.FIELD name or id): the load vector of a linear problem in one
+        kernel per degree bucket where apply_galerkin_integral has a one-kernel path; sources as set_puncture_term"""
+        assert (brick is not None) + (analytic is not None) + (xyz is not None) == 1, "one of brick / analytic / xyz"
+        assert out.numel() == self.local_nodes and beta in (0, 1)
+        fid, pr, n_params = _field_params(field_id, params)
+        pp = pr.ctypes.data_as(_vp)
+        if brick is not None:
+            keep, args = self._brick_source(brick)
+            self.lib.d4est_hip_plan_build_load_by_id_brick(self.handle, fid, pp, n_params, *args, int(beta), _ptr(out))
+        elif analytic is not None:
+            keep, args = self._analytic_source(analytic)
+            self.lib.d4est_hip_plan_build_load_by_id_analytic(self.handle, fid, pp, n_params, *args, int(beta), _ptr(out))
+        else:
+            assert xyz.numel() == 3 * self.local_nodes_quad
+            self.lib.d4est_hip_plan_build_load_by_id_xyz(self.handle, fid, pp, n_params, _ptr(xyz), int(beta), _ptr(out))
+
     def nonlinear_coefficients(self, device=None):
         """(a, b, k) of the power term that is set: torch VIEWS of the plan-owned arrays (b None when b = 0), or None when the term is
         off; valid until the term changes or the plan is destroyed"""
@@ -1125,7 +1200,7 @@ class Plan:
         assert (brick is None) != (analytic is None), "one of brick / analytic"
         c = ROBIN_COEFF[coeff_id] if isinstance(coeff_id, str) else int(coeff_id)
         r = ROBIN_RHS[rhs_id] if isinstance(rhs_id, str) else int(rhs_id)
-        assert c in (0, 1) and r in (0, 1), "unknown Robin id"
+        assert c in (0, 1, 2) and r in (0, 1), "unknown Robin id"
         assert not (c == 1 and brick is None), "ROBIN_COEFF_BRICK needs the brick source"
         if brick is not None:
             keep, args = self._brick_source(brick)

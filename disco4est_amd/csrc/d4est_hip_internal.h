@@ -499,6 +499,11 @@ void nonlinear_destroy(d4est_hip_plan* plan);
 // the plan-owned a (and, with_b, b; else b is dropped and *b = nullptr) of the power term with exponent k, allocated if need be: the
 // state d4est_hip_plan_set_nonlinear_power leaves, for a caller that writes the values itself on the plan's stream
 void nonlinear_term_arrays(d4est_hip_plan* plan, int k, bool with_b, double** a, double** b);
+// the same for the REAL power term a |b + u|^s; either call clears the other form
+void nonlinear_term_arrays_real(d4est_hip_plan* plan, double s, bool with_b, double** a, double** b);
+// plan-owned temporaries of the composed load vector (d4est_hip_problem.hip), allocated on first use and freed with the plan:
+// local_nodes_quad doubles (shared with the composed nonlinear term) and, with want_xyz, 3 local_nodes_quad more
+void nonlinear_load_scratch(d4est_hip_plan* plan, bool want_xyz, double** f_quad, double** xyz_quad);
 
 // d4est_hip_capi.hip (defined among its extern "C" entry points; not in the header: internal): {geom_type, params} of the analytic entry
 // points -> TreeMapParams; aborts with `who` on a bad type, radius or flag

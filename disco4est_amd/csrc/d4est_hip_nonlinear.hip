@@ -16,12 +16,15 @@
 // quadrature-sized temporary.  The coefficient form stops at the quadrature nodes and writes c = k a (b + V u0)^(k-1) and w J c, the two
 // arrays d4est_hip_plan_set_lhs_coefficient and the first apply_lhs after it would have produced in a copy and a second pass.
 // The power is a product of |k| factors (k < 0: one division of 1 by the product); k is wave-uniform, the loop does not diverge.
+// The body (d4est_hip_pointwise.h) takes the pointwise function as a template parameter: PowArgs is the integer form above, AbsPowArgs
+// the real form a |b + u|^s of Okendon's callbacks (src/Problems/Okendon/okendon_fcns.h:114-145), evaluated with pow as they are.
 #include <algorithm>
 #include <cmath>
 
 #include "d4est_hip_internal.h"
 #include "d4est_hip_wave.h"
 #include "d4est_hip_mwave.h"
+#include "d4est_hip_pointwise.h"
 
 namespace d4est_hip {
 
@@ -29,164 +32,15 @@ struct NonlinHost {
   double* d_a = nullptr;     // plan-owned copies of the caller's arrays (local_nodes_quad each); d_a == nullptr: the term is off
   double* d_b = nullptr;     // nullptr: b = 0
   int k = 0;
-  double* d_uq = nullptr;    // composed path only: V u at the quadrature nodes
+  bool real = false;         // the real form a |b + u|^s (d4est_hip_plan_set_nonlinear_abs_power); then k = 0
+  double s = 0.;
+  double* d_xyzq = nullptr;  // composed load vector only: x | y | z at the quadrature nodes (nonlinear_load_scratch)
+  double* d_uq = nullptr;   // composed path only: V u at the quadrature nodes
   // Newton loop: F(u), the step, the Krylov solver's A u; one device scalar and its pinned host mirror
   double *d_f = nullptr, *d_step = nullptr, *d_Au = nullptr, *d_norm = nullptr, *h_norm = nullptr;
 };
 
 static NonlinHost* host_of(const d4est_hip_plan* plan) { return static_cast<NonlinHost*>(plan->nonlin); }
-
-struct PowArgs {
-  const double* a;
-  const double* b;   // may be null
-  int k;
-  int beta;          // term form: 0 overwrite, 1 accumulate
-};
-
-// base^k by repeated multiplication (the reference's callbacks multiply out; no pow)
-__device__ __forceinline__ double pow_int(double base, int k) {
-  const int m = k < 0 ? -k : k;
-  double p = 1.0;
-  for (int i = 0; i < m; ++i) p *= base;
-  return k < 0 ? 1.0 / p : p;
-}
-__device__ __forceinline__ double power_term(double a, double b, double u, int k) { return a * pow_int(b + u, k); }
-// d/du of the above: k a (b + u)^(k-1); k = 0: exactly 0 (not 0 * (b + u)^-1)
-__device__ __forceinline__ double power_coeff(double a, double b, double u, int k) {
-  return k == 0 ? 0.0 : ((double)k * a) * pow_int(b + u, k - 1);
-}
-
-// dst += the LDS image (store_element_image of d4est_hip_wave.h with the reference's axpy 1.0)
-template <int N, int PL, int PN>
-__device__ __forceinline__ void add_element_image(double* __restrict__ dst, const double* R, int te) {
-  constexpr int N3 = N * N * N, NL = (N3 + PL - 1) / PL;
-#pragma unroll
-  for (int q = 0; q < NL; ++q) {
-    const int idx = te + PL * q;
-    const int i = idx % N, j = (idx / N) % N, k = idx / (N * N);
-    if (N3 % PL == 0 || idx < N3) dst[idx] = dst[idx] + R[i + PN * (j + N * k)];
-  }
-}
-
-// Bop / BopT: the even-odd tables of B^T / B (Bucket::d_EBb / d_EBf), as mass_like_body takes them with EO = true
-template <int N, int NQ, bool COEFF>
-__device__ __forceinline__ void nonlin_body(double* smem, int wg, const double* __restrict__ u, double* __restrict__ out,
-                                            const double* __restrict__ Jq, const int* __restrict__ ns_list,
-                                            const int* __restrict__ qs_list, int n_bucket, const double* __restrict__ Bop,
-                                            const double* __restrict__ BopT, const double* __restrict__ wq, PowArgs P,
-                                            double* __restrict__ c_out, double* __restrict__ wjc_out) {
-  using C = WaveCfg<N, NQ>;
-  constexpr int PL = C::PL, PN = C::PN, PQ = C::PQ;
-
-  const int tid = threadIdx.x;
-  const int slot = tid / PL;
-  const int te = tid - slot * PL;
-  const int a = te % NQ, b = te / NQ;
-  const int ei = wg * C::EPB + slot;
-  const bool active = (slot < C::EPB) && (ei < n_bucket);
-  double* R0 = smem + (active ? slot : 0) * C::LDS_PER_ELEM;
-  double* R1 = R0 + C::FS;
-
-  int ns = 0, qs = 0;
-  if (active) {
-    ns = ns_list[ei];
-    qs = qs_list[ei];
-  }
-
-  // ---- forward: g = (V u)(a, b, :) ----
-  double g[NQ];
-  if (active) load_element_image<N, PL, PN>(R0, u + ns, te);
-  __syncthreads();
-  if (active && a < N && b < N) {  // r
-    double x[N], y[NQ];
-#pragma unroll
-    for (int i = 0; i < N; ++i) x[i] = lds_ld(&R0[i + PN * (a + N * b)]);
-    fwd<N, NQ, true, false>(BopT, x, y);
-#pragma unroll
-    for (int iq = 0; iq < NQ; ++iq) R1[a + PN * (iq + NQ * b)] = y[iq];
-  }
-  __syncthreads();
-  if (active && b < N) {  // s
-    double x[N], y[NQ];
-#pragma unroll
-    for (int j = 0; j < N; ++j) x[j] = lds_ld(&R1[j + PN * (a + NQ * b)]);
-    fwd<N, NQ, true, false>(BopT, x, y);
-#pragma unroll
-    for (int jq = 0; jq < NQ; ++jq) R0[b + PN * (a + NQ * jq)] = y[jq];
-  }
-  __syncthreads();
-  if (active) {  // t
-    double x[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) x[k] = lds_ld(&R0[k + PN * (a + NQ * b)]);
-    fwd<N, NQ, true, false>(BopT, x, g);
-  }
-
-  // ---- pointwise, at the thread's NQ quadrature nodes ----
-  if constexpr (COEFF) {
-    if (active) {
-      const double wab = wq[b] * wq[a];
-#pragma unroll
-      for (int kq = 0; kq < NQ; ++kq) {
-        const int q = qs + a + NQ * (b + NQ * kq);
-        const double c = power_coeff(P.a[q], P.b ? P.b[q] : 0.0, g[kq], P.k);
-        c_out[q] = c;
-        wjc_out[q] = (wq[kq] * wab) * (Jq[q] * c);   // the rounding of lhs_wjc_kernel (d4est_hip_solver.hip)
-      }
-    }
-    return;
-  } else {
-    double c[N];
-    if (active) {
-      const double wab = wq[a] * wq[b];
-#pragma unroll
-      for (int kq = 0; kq < NQ; ++kq) {
-        const int q = qs + a + NQ * (b + NQ * kq);
-        const double sc = (wq[kq] * wab) * Jq[q];
-        g[kq] = power_term(P.a[q], P.b ? P.b[q] : 0.0, g[kq], P.k) * sc;
-      }
-      bwd<NQ, N, true, false, false>(Bop, g, c);
-    }
-    // ---- backward: V^T, as mass_like_body ----
-    __syncthreads();
-    if (active) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) R0[b + PQ * (a + NQ * k)] = c[k];
-    }
-    __syncthreads();
-    if (active && b < N) {
-      double x[NQ], y[N];
-#pragma unroll
-      for (int jq = 0; jq < NQ; ++jq) x[jq] = lds_ld(&R0[jq + PQ * (a + NQ * b)]);
-      bwd<NQ, N, true, false, false>(Bop, x, y);
-#pragma unroll
-      for (int j = 0; j < N; ++j) R1[a + PQ * (j + N * b)] = y[j];
-    }
-    __syncthreads();
-    if (active && a < N && b < N) {
-      double x[NQ], o[N];
-#pragma unroll
-      for (int iq = 0; iq < NQ; ++iq) x[iq] = lds_ld(&R1[iq + PQ * (a + N * b)]);
-      bwd<NQ, N, true, false, false>(Bop, x, o);
-#pragma unroll
-      for (int i = 0; i < N; ++i) R0[i + PN * (a + N * b)] = o[i];
-    }
-    __syncthreads();
-    if (active) {
-      if (P.beta) add_element_image<N, PL, PN>(out + ns, R0, te);
-      else store_element_image<N, PL, PN>(out + ns, R0, te);
-    }
-  }
-}
-
-template <int N, int NQ, bool COEFF>
-__global__ __launch_bounds__((WaveCfg<N, NQ>::THREADS)) void nonlin_kernel(
-    const double* __restrict__ u, double* __restrict__ out, const double* __restrict__ Jq, const int* __restrict__ ns_list,
-    const int* __restrict__ qs_list, int n_bucket, const double* __restrict__ Bop, const double* __restrict__ BopT,
-    const double* __restrict__ wq, PowArgs P, double* __restrict__ c_out, double* __restrict__ wjc_out) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  nonlin_body<N, NQ, COEFF>(smem, blockIdx.x, u, out, Jq, ns_list, qs_list, n_bucket, Bop, BopT, wq, P, c_out, wjc_out);
-}
 
 // Mixed-degree plans: all buckets with deg_quad = deg <= 7 in ONE launch (the rule of mass_like_multi_kernel): one 64-lane workgroup
 // per work unit, which looks its bucket up (wave-uniform) and runs that degree's body
@@ -202,10 +56,10 @@ struct NonlinMulti {
   const double* wq[MAXB] = {};
 };
 
-template <bool COEFF>
+template <bool COEFF, class F>
 __global__ __launch_bounds__(64) void nonlin_multi_kernel(const double* __restrict__ u, double* __restrict__ out,
                                                           const double* __restrict__ Jq, const int* __restrict__ ns_list_all,
-                                                          const int* __restrict__ qs_list_all, PowArgs P, double* __restrict__ c_out,
+                                                          const int* __restrict__ qs_list_all, F P, double* __restrict__ c_out,
                                                           double* __restrict__ wjc_out, NonlinMulti A) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int blk = blockIdx.x;
@@ -218,7 +72,7 @@ __global__ __launch_bounds__(64) void nonlin_multi_kernel(const double* __restri
   const double* wq = A.wq[bi];
 #define D4EST_CASE(N_)                                                                                                              \
   case N_:                                                                                                                          \
-    nonlin_body<N_, N_, COEFF>(smem, wg, u, out, Jq, ns_list_all + off, qs_list_all + off, nb, EBb, EBf, wq, P, c_out, wjc_out);    \
+    nonlin_body<N_, N_, COEFF, F>(smem, wg, u, out, Jq, ns_list_all + off, qs_list_all + off, nb, EBb, EBf, wq, P, c_out, wjc_out); \
     break;
   switch (A.N[bi]) {
     D4EST_CASE(2) D4EST_CASE(3) D4EST_CASE(4) D4EST_CASE(5) D4EST_CASE(6) D4EST_CASE(7) D4EST_CASE(8)
@@ -228,29 +82,21 @@ __global__ __launch_bounds__(64) void nonlin_multi_kernel(const double* __restri
 }
 
 // composed path (a bucket without a compiled pair): the pointwise step between d4est_hip_interpolate and the integral / the w J c pass
-template <bool COEFF>
-__global__ __launch_bounds__(256) void nonlin_pointwise_kernel(long long n, double* __restrict__ uq, PowArgs P) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const double b = P.b ? P.b[i] : 0.0;
-    uq[i] = COEFF ? power_coeff(P.a[i], b, uq[i], P.k) : power_term(P.a[i], b, uq[i], P.k);
-  }
+template <bool COEFF, class F>
+__global__ __launch_bounds__(256) void nonlin_pointwise_kernel(long long n, double* __restrict__ uq, F P) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    uq[i] = COEFF ? P.coeff(0, i, 0, 0, 0, uq[i]) : P.term(0, i, 0, 0, 0, uq[i]);
 }
 
 __global__ __launch_bounds__(256) void nonlin_negate_kernel(int n, double* __restrict__ x) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) x[i] = -1. * x[i];
 }
 
-// every bucket has a compiled (deg + 1, deg_quad + 1) pair (pair_built, d4est_hip_wave.h: the coverage of
-// d4est_hip_apply_galerkin_integral's one-kernel path in d4est_hip_volume.hip)
-static bool plan_fused(const d4est_hip_plan* plan) {
-  for (const Bucket& bk : plan->buckets)
-    if (bk.n_elem > 0 && !pair_built(bk.N, bk.NQ)) return false;
-  return true;
-}
+static bool plan_fused(const d4est_hip_plan* plan) { return plan_pairs_built(plan); }
 
 // every bucket of a plan for which plan_fused() holds
-template <bool COEFF>
-static void launch_fused(d4est_hip_plan* plan, const double* u, double* out, PowArgs P, double* c_out, double* wjc_out) {
+template <bool COEFF, class F>
+static void launch_fused(d4est_hip_plan* plan, const double* u, double* out, F P, double* c_out, double* wjc_out) {
   unsigned covered = 0u;
   NonlinMulti A;   // mixed-degree plans: one launch for the deg_quad = deg <= 7 buckets
   size_t lds = 0;
@@ -262,7 +108,7 @@ static void launch_fused(d4est_hip_plan* plan, const double* u, double* out, Pow
     lds = std::max(lds, w.lds_bytes);
   }
   if (A.n >= 2)
-    hipLaunchKernelGGL((nonlin_multi_kernel<COEFF>), dim3(multi_workgroups(A)), dim3(64), lds, plan->stream, u, out, plan->d_J,
+    hipLaunchKernelGGL((nonlin_multi_kernel<COEFF, F>), dim3(multi_workgroups(A)), dim3(64), lds, plan->stream, u, out, plan->d_J,
                        plan->d_ns_list, plan->d_qs_list, P, c_out, wjc_out, A);
   else
     covered = 0u;
@@ -270,8 +116,8 @@ static void launch_fused(d4est_hip_plan* plan, const double* u, double* out, Pow
     const bool built = for_built_pair(bk.N, bk.NQ, [&](auto n, auto nq) {
       constexpr int N = decltype(n)::value, NQ = decltype(nq)::value;
       using C = WaveCfg<N, NQ>;
-      set_lds_limit(nonlin_kernel<N, NQ, COEFF>, C::LDS_BYTES);
-      hipLaunchKernelGGL((nonlin_kernel<N, NQ, COEFF>), dim3((bk.n_elem + C::EPB - 1) / C::EPB), dim3(C::THREADS), C::LDS_BYTES, plan->stream,
+      set_lds_limit(nonlin_kernel<N, NQ, COEFF, F>, C::LDS_BYTES);
+      hipLaunchKernelGGL((nonlin_kernel<N, NQ, COEFF, F>), dim3((bk.n_elem + C::EPB - 1) / C::EPB), dim3(C::THREADS), C::LDS_BYTES, plan->stream,
                          u, out, plan->d_J, plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem, bk.d_EBb,
                          bk.d_EBf, bk.d_w, P, c_out, wjc_out);
     });
@@ -282,7 +128,7 @@ static void launch_fused(d4est_hip_plan* plan, const double* u, double* out, Pow
 
 static NonlinHost* need_term(d4est_hip_plan* plan, const char* who) {
   NonlinHost* h = host_of(plan);
-  if (!h || !h->d_a) D4EST_HIP_ABORT("%s: no power term is set (d4est_hip_plan_set_nonlinear_power)", who);
+  if (!h || !h->d_a) D4EST_HIP_ABORT("%s: no power term is set (d4est_hip_plan_set_nonlinear_power / _abs_power)", who);
   if (!plan->has_geometry) D4EST_HIP_ABORT("%s: d4est_hip_plan_set_geometry was not called", who);
   return h;
 }
@@ -293,7 +139,7 @@ static void ensure_uq(d4est_hip_plan* plan, NonlinHost* h) {
   if (!h->d_uq) HIP_CHECK(hipMalloc(&h->d_uq, nq_alloc(plan)));
 }
 
-void nonlinear_term_arrays(d4est_hip_plan* plan, int k, bool with_b, double** a, double** b) {
+static void term_arrays(d4est_hip_plan* plan, bool real, int k, double s, bool with_b, double** a, double** b) {
   NonlinHost* h = host_of(plan);
   if (!h) { h = new NonlinHost; plan->nonlin = h; }
   if (!h->d_a) HIP_CHECK(hipMalloc(&h->d_a, nq_alloc(plan)));
@@ -302,15 +148,52 @@ void nonlinear_term_arrays(d4est_hip_plan* plan, int k, bool with_b, double** a,
   } else {
     (void)hipFree(h->d_b); h->d_b = nullptr;
   }
-  h->k = k;
+  h->k = k;         // setting either form clears the other
+  h->real = real;
+  h->s = s;
   *a = h->d_a;
   *b = h->d_b;
+}
+
+void nonlinear_term_arrays(d4est_hip_plan* plan, int k, bool with_b, double** a, double** b) {
+  term_arrays(plan, false, k, 0., with_b, a, b);
+}
+
+void nonlinear_term_arrays_real(d4est_hip_plan* plan, double s, bool with_b, double** a, double** b) {
+  term_arrays(plan, true, 0, s, with_b, a, b);
+}
+
+// the term switched off (a == NULL of either setter)
+static void term_off(d4est_hip_plan* plan) {
+  NonlinHost* h = host_of(plan);
+  if (!h) { h = new NonlinHost; plan->nonlin = h; }
+  (void)hipFree(h->d_a); h->d_a = nullptr;
+  (void)hipFree(h->d_b); h->d_b = nullptr;
+  h->k = 0;
+  h->real = false;
+  h->s = 0.;
+}
+
+// f(P) with the pointwise function of the form that is set
+template <class Fn>
+static void with_form(const NonlinHost* h, int beta, Fn&& f) {
+  if (h->real) f(AbsPowArgs{h->d_a, h->d_b, h->s, beta});
+  else f(PowArgs{h->d_a, h->d_b, h->k, beta});
+}
+
+void nonlinear_load_scratch(d4est_hip_plan* plan, bool want_xyz, double** f_quad, double** xyz_quad) {
+  NonlinHost* h = host_of(plan);
+  if (!h) { h = new NonlinHost; plan->nonlin = h; }
+  ensure_uq(plan, h);
+  if (want_xyz && !h->d_xyzq) HIP_CHECK(hipMalloc(&h->d_xyzq, 3 * nq_alloc(plan)));
+  *f_quad = h->d_uq;
+  *xyz_quad = want_xyz ? h->d_xyzq : nullptr;
 }
 
 void nonlinear_destroy(d4est_hip_plan* plan) {
   NonlinHost* h = host_of(plan);
   if (!h) return;
-  (void)hipFree(h->d_a); (void)hipFree(h->d_b); (void)hipFree(h->d_uq);
+  (void)hipFree(h->d_a); (void)hipFree(h->d_b); (void)hipFree(h->d_uq); (void)hipFree(h->d_xyzq);
   (void)hipFree(h->d_f); (void)hipFree(h->d_step); (void)hipFree(h->d_Au); (void)hipFree(h->d_norm);
   if (h->h_norm) (void)hipHostFree(h->h_norm);
   delete h;
@@ -320,7 +203,6 @@ void nonlinear_destroy(d4est_hip_plan* plan) {
 }  // namespace d4est_hip
 
 using d4est_hip::NonlinHost;
-using d4est_hip::PowArgs;
 
 extern "C" {
 
@@ -329,16 +211,26 @@ void d4est_hip_plan_set_nonlinear_power(d4est_hip_plan_t* plan, const double* a_
   if (k < -16 || k > 16) D4EST_HIP_ABORT("plan_set_nonlinear_power: k = %d is outside [-16, 16]", k);
   const size_t bytes = (size_t)plan->local_nodes_quad * sizeof(double);
   if (!a_quad_dev) {   // the term is off
-    NonlinHost* h = d4est_hip::host_of(plan);
-    if (!h) { h = new NonlinHost; plan->nonlin = h; }
-    (void)hipFree(h->d_a); h->d_a = nullptr;
-    (void)hipFree(h->d_b); h->d_b = nullptr;
-    h->k = 0;
+    d4est_hip::term_off(plan);
     return;
   }
   // the values are CAPTURED here, as d4est_hip_plan_set_lhs_coefficient captures its coefficient
   double *d_a = nullptr, *d_b = nullptr;
   d4est_hip::nonlinear_term_arrays(plan, k, b_quad_dev != nullptr, &d_a, &d_b);
+  HIP_CHECK(hipMemcpyAsync(d_a, a_quad_dev, bytes, hipMemcpyDeviceToDevice, plan->stream));
+  if (b_quad_dev) HIP_CHECK(hipMemcpyAsync(d_b, b_quad_dev, bytes, hipMemcpyDeviceToDevice, plan->stream));
+}
+
+void d4est_hip_plan_set_nonlinear_abs_power(d4est_hip_plan_t* plan, const double* a_quad_dev, const double* b_quad_dev, double s) {
+  if (!plan) D4EST_HIP_ABORT("plan_set_nonlinear_abs_power: NULL plan");
+  if (!std::isfinite(s)) D4EST_HIP_ABORT("plan_set_nonlinear_abs_power: s = %g", s);
+  const size_t bytes = (size_t)plan->local_nodes_quad * sizeof(double);
+  if (!a_quad_dev) {   // the term is off
+    d4est_hip::term_off(plan);
+    return;
+  }
+  double *d_a = nullptr, *d_b = nullptr;
+  d4est_hip::nonlinear_term_arrays_real(plan, s, b_quad_dev != nullptr, &d_a, &d_b);
   HIP_CHECK(hipMemcpyAsync(d_a, a_quad_dev, bytes, hipMemcpyDeviceToDevice, plan->stream));
   if (b_quad_dev) HIP_CHECK(hipMemcpyAsync(d_b, b_quad_dev, bytes, hipMemcpyDeviceToDevice, plan->stream));
 }
@@ -349,7 +241,15 @@ int d4est_hip_plan_nonlinear_coefficients(const d4est_hip_plan_t* plan, const do
   if (!h || !h->d_a) return 0;
   if (a_dev) *a_dev = h->d_a;
   if (b_dev) *b_dev = h->d_b;
-  if (k) *k = h->k;
+  if (k) *k = h->k;   // 0 while the real form is set (d4est_hip_plan_nonlinear_exponent)
+  return 1;
+}
+
+int d4est_hip_plan_nonlinear_exponent(const d4est_hip_plan_t* plan, double* s) {
+  if (!plan) D4EST_HIP_ABORT("plan_nonlinear_exponent: NULL plan");
+  const NonlinHost* h = d4est_hip::host_of(plan);
+  if (!h || !h->d_a || !h->real) return 0;
+  if (s) *s = h->s;
   return 1;
 }
 
@@ -365,16 +265,18 @@ void d4est_hip_apply_nonlinear_term(d4est_hip_plan_t* plan, const double* u_dev,
   }
   if (!plan->has_geometry) D4EST_HIP_ABORT("apply_nonlinear_term: d4est_hip_plan_set_geometry was not called");
   if (n == 0) return;
-  const PowArgs P = {h->d_a, h->d_b, h->k, beta};
   if (d4est_hip::plan_fused(plan)) {
-    d4est_hip::launch_fused<false>(plan, u_dev, out_dev, P, nullptr, nullptr);
+    d4est_hip::with_form(h, beta, [&](auto P) { d4est_hip::launch_fused<false>(plan, u_dev, out_dev, P, nullptr, nullptr); });
     return;
   }
   // composed: interpolate, pointwise, integrate (+ axpy 1.0)
   d4est_hip::ensure_uq(plan, h);
   d4est_hip::launch_mass_like(plan, 2, u_dev, h->d_uq);
   const long long nq = plan->local_nodes_quad;
-  hipLaunchKernelGGL((d4est_hip::nonlin_pointwise_kernel<false>), dim3(d4est_hip::grid_for(nq)), dim3(256), 0, plan->stream, nq, h->d_uq, P);
+  d4est_hip::with_form(h, beta, [&](auto P) {
+    hipLaunchKernelGGL((d4est_hip::nonlin_pointwise_kernel<false, decltype(P)>), dim3(d4est_hip::grid_for(nq)), dim3(256), 0, plan->stream, nq,
+                       h->d_uq, P);
+  });
   if (!beta) {
     d4est_hip::launch_mass_like(plan, 1, h->d_uq, out_dev);
   } else {
@@ -400,16 +302,18 @@ void d4est_hip_plan_linearise(d4est_hip_plan_t* plan, const double* u0_dev) {
   if (!plan->d_lhs_wjc) HIP_CHECK(hipMalloc(&plan->d_lhs_wjc, d4est_hip::nq_alloc(plan)));
   plan->d_lhs_coeff = plan->d_lhs_c;   // non-null = the term is on (the caller's array is never read after the capture)
   if (plan->local_nodes == 0) return;
-  const PowArgs P = {h->d_a, h->d_b, h->k, 0};
   if (d4est_hip::plan_fused(plan)) {
-    d4est_hip::launch_fused<true>(plan, u0_dev, nullptr, P, plan->d_lhs_c, plan->d_lhs_wjc);
+    d4est_hip::with_form(h, 0, [&](auto P) { d4est_hip::launch_fused<true>(plan, u0_dev, nullptr, P, plan->d_lhs_c, plan->d_lhs_wjc); });
     plan->lhs_wjc_valid = true;   // ... and w J c is already formed (set_lhs_coefficient leaves it to the first apply)
     return;
   }
   // composed: V u0 into the coefficient array, c in place; w J c by the first apply (ensure_lhs_wjc)
   d4est_hip::launch_mass_like(plan, 2, u0_dev, plan->d_lhs_c);
   const long long nq = plan->local_nodes_quad;
-  hipLaunchKernelGGL((d4est_hip::nonlin_pointwise_kernel<true>), dim3(d4est_hip::grid_for(nq)), dim3(256), 0, plan->stream, nq, plan->d_lhs_c, P);
+  d4est_hip::with_form(h, 0, [&](auto P) {
+    hipLaunchKernelGGL((d4est_hip::nonlin_pointwise_kernel<true, decltype(P)>), dim3(d4est_hip::grid_for(nq)), dim3(256), 0, plan->stream, nq,
+                       plan->d_lhs_c, P);
+  });
   HIP_CHECK(hipGetLastError());
 }
 

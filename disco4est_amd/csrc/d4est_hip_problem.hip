@@ -22,6 +22,7 @@
 
 #include "d4est_hip_internal.h"
 #include "d4est_hip_maps.h"
+#include "d4est_hip_pointwise.h"
 
 #pragma clang fp contract(off)
 
@@ -113,6 +114,85 @@ __device__ __forceinline__ double inv_r(double x, double y, double z) {
   return 1 / sqrt(r2);
 }
 
+// ---- the fields of the remaining problem families ------------------------------------------------------------------------------------
+// okendon_analytic_solution, the DIM == 3 branch (src/Problems/Okendon/okendon_fcns.h:70-96); params {p}
+__device__ __forceinline__ double okendon_u(const FieldParams& F, double x, double y, double z) {
+  const double p = F.p[0];
+  const double M = 1. / (pow((2. / (1. - p)) * (1 + (2. / (1. - p))), (1. / (1. - p))));
+  const double r2 = x * x + y * y + z * z;
+  return M * pow(r2, 1 / (1 - p));
+}
+
+// boyen_york_model_analytic_solution (src/Problems/BoyenYorkModel/boyen_york_model_fcns.h:67-95); params {a, P}
+__device__ __forceinline__ double by_psi(const FieldParams& F, double x, double y, double z) {
+  const double r2 = x * x + y * y + z * z;
+  const double r = sqrt(r2);
+  const double r3 = r * r2;
+  const double r4 = r2 * r2;
+  const double a = F.p[0], P = F.p[1];
+  const double E = sqrt(P * P + 4 * a * a);
+  const double t1 = 1.;
+  const double t2 = 2. * E / r;
+  const double t3 = 6 * a * a / (r2);
+  const double t4 = 2 * a * a * E / (r3);
+  const double t5 = a * a * a * a / (r4);
+  return pow((t1 + t2 + t3 + t4 + t5), .25);
+}
+
+// boyen_york_model_helmholtz_fcn (:110-128)
+__device__ __forceinline__ double by_a(const FieldParams& F, double x, double y, double z) {
+  const double a = F.p[0], P = F.p[1];
+  const double r2 = x * x + y * y + z * z;
+  const double r4 = r2 * r2;
+  const double a2 = a * a;
+  const double P2 = P * P;
+  return .75 * (P2 / r4) * (1 - (a2 / r2)) * (1 - (a2 / r2));
+}
+
+// poisson_lorentzian_analytic_solution / _rhs_fcn / _robin_coeff_fcn (src/Problems/Poisson/poisson_lorentzian_fcns.h:55-67, :71-82, :22-36)
+__device__ __forceinline__ double lorentzian_u(double x, double y, double z) {
+  const double r = sqrt(x * x + y * y + z * z);
+  return 1. / sqrt(1. + r * r);
+}
+__device__ __forceinline__ double lorentzian_rhs(double x, double y, double z) { return 3. / pow((1. + x * x + y * y + z * z), 2.5); }
+__device__ __forceinline__ double lorentzian_robin(double x, double y, double z) {
+  const double r2 = x * x + y * y + z * z;
+  return sqrt(r2) / (1. + r2);
+}
+
+// stamm_analytic_solution, the DIM == 3 branch (src/Problems/Stamm/stamm_fcns.h:78-114); params {c2x, c2y, c2z}.
+// d4est_util_dbl_pow_int(rp, 3) is (rp rp) rp (src/Utilities/d4est_util.c:157-185)
+__device__ __forceinline__ double stamm_u(const FieldParams& F, double x, double y, double z) {
+  const double xp = x - F.p[0], yp = y - F.p[1], zp = z - F.p[2];
+  const double rp = sqrt(xp * xp + yp * yp + zp * zp);
+  return x * (1. - x) * y * (1. - y) * z * (1. - z) * ((rp * rp) * rp);
+}
+
+// stamm_rhs_fcn, the DIM == 3 branch (:149-208), term by term in the reference's order; S = |c2 - x|^2, pow_int(., 2) is one product
+__device__ __forceinline__ double stamm_rhs(const FieldParams& F, double x, double y, double z) {
+  const double c2x = F.p[0], c2y = F.p[1], c2z = F.p[2];
+  if (x == c2x && y == c2y && z == c2z) return 0.;
+  const double dx2 = (c2x - x) * (c2x - x), dy2 = (c2y - y) * (c2y - y), dz2 = (c2z - z) * (c2z - z);
+  const double S = dx2 + dy2 + dz2;
+  const double S2 = S * S;
+  double ret = (-2 * (1 - x) * x * (1 - y) * y * S2 +
+                9 * (1 - x) * x * (1 - y) * y * S * (1 - z) * z +
+                6 * (1 - x) * (-c2x + x) * (1 - y) * y * S * (1 - z) * z -
+                6 * x * (-c2x + x) * (1 - y) * y * S * (1 - z) * z +
+                6 * (1 - x) * x * (1 - y) * (-c2y + y) * S * (1 - z) * z -
+                6 * (1 - x) * x * y * (-c2y + y) * S * (1 - z) * z -
+                2 * (1 - x) * x * S2 * (1 - z) * z -
+                2 * (1 - y) * y * S2 * (1 - z) * z -
+                3 * dx2 * (-1 + x) * x * (-1 + y) * y * (-1 + z) * z -
+                3 * (-1 + x) * x * dy2 * (-1 + y) * y * (-1 + z) * z -
+                3 * (-1 + x) * x * (-1 + y) * y * dz2 * (-1 + z) * z +
+                6 * (1 - x) * x * (1 - y) * y * S * (1 - z) * (-c2z + z) -
+                6 * (1 - x) * x * (1 - y) * y * S * z * (-c2z + z)) /
+               sqrt(S);
+  ret *= -1;
+  return ret;
+}
+
 __device__ __forceinline__ double field_value(int id, const FieldParams& F, double x, double y, double z) {
   switch (id) {   // wave-uniform
     case D4EST_HIP_FIELD_PUNCTURE_K2: return puncture_k2(F, x, y, z);
@@ -120,6 +200,14 @@ __device__ __forceinline__ double field_value(int id, const FieldParams& F, doub
     case D4EST_HIP_FIELD_PUNCTURE_B: return puncture_b(F, x, y, z);
     case D4EST_HIP_FIELD_CDS_A: return cds_a(F, x, y, z);
     case D4EST_HIP_FIELD_CDS_PSI: return cds_psi(F, x, y, z);
+    case D4EST_HIP_FIELD_OKENDON_U: return okendon_u(F, x, y, z);
+    case D4EST_HIP_FIELD_BY_PSI: return by_psi(F, x, y, z);
+    case D4EST_HIP_FIELD_BY_A: return by_a(F, x, y, z);
+    case D4EST_HIP_FIELD_LORENTZIAN_U: return lorentzian_u(x, y, z);
+    case D4EST_HIP_FIELD_LORENTZIAN_RHS: return lorentzian_rhs(x, y, z);
+    case D4EST_HIP_FIELD_LORENTZIAN_ROBIN: return lorentzian_robin(x, y, z);
+    case D4EST_HIP_FIELD_STAMM_U: return stamm_u(F, x, y, z);
+    case D4EST_HIP_FIELD_STAMM_RHS: return stamm_rhs(F, x, y, z);
     default: return inv_r(x, y, z);
   }
 }
@@ -168,7 +256,7 @@ struct BucketList {
 };
 
 // one workgroup per element, one thread per node; mode 0: coordinates (x | y | z, `total` apart) into out_a; mode 1: the puncture
-// term's a and b; mode 2: the star term's a
+// term's a and b; mode 2: the star term's a; mode 3: the Okendon term's a; mode 4: the Boyen-York term's a
 __global__ __launch_bounds__(128) void node_kernel(int mode, CoordSrc S, BucketList B, const int* __restrict__ elem_ids,
                                                    const int* __restrict__ s_list, const double* __restrict__ nodes, FieldParams F,
                                                    double* __restrict__ out_a, double* __restrict__ out_b, size_t total) {
@@ -195,8 +283,12 @@ __global__ __launch_bounds__(128) void node_kernel(int mode, CoordSrc S, BucketL
       } else if (mode == 1) {
         out_a[s0 + n] = puncture_a(F, x[0], x[1], x[2]);
         out_b[s0 + n] = puncture_b(F, x[0], x[1], x[2]);
-      } else {
+      } else if (mode == 2) {
         out_a[s0 + n] = cds_a(F, x[0], x[1], x[2]);
+      } else if (mode == 3) {
+        out_a[s0 + n] = 1.;   // okendon_build_residual adds + V^T W J |u|^p to A u (okendon_fcns.h:377-403)
+      } else {
+        out_a[s0 + n] = by_a(F, x[0], x[1], x[2]);
       }
     }
   }
@@ -241,6 +333,8 @@ __global__ __launch_bounds__(64) void boundary_kernel(int mode, int coeff_id, in
         const double r2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
         const double xa = dir == 0 ? x[0] : dir == 1 ? x[1] : x[2];
         c = (((un.face & 1) ? 1.0 : -1.0) * xa) / r2;
+      } else if (coeff_id == D4EST_HIP_ROBIN_COEFF_LORENTZIAN) {
+        c = lorentzian_robin(x[0], x[1], x[2]);
       } else {
         c = inv_r(x[0], x[1], x[2]);
       }
@@ -254,10 +348,17 @@ __global__ __launch_bounds__(64) void boundary_kernel(int mode, int coeff_id, in
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 static FieldParams field_params(int field_id, const double* params, int n_params, const char* who) {
   FieldParams F = {};
-  if (field_id < D4EST_HIP_FIELD_PUNCTURE_K2 || field_id > D4EST_HIP_FIELD_INV_R) D4EST_HIP_ABORT("%s: unknown field id %d", who, field_id);
-  if (field_id == D4EST_HIP_FIELD_INV_R) return F;
+  if (field_id < D4EST_HIP_FIELD_PUNCTURE_K2 || field_id > D4EST_HIP_FIELD_STAMM_RHS) D4EST_HIP_ABORT("%s: unknown field id %d", who, field_id);
+  if (field_id == D4EST_HIP_FIELD_INV_R || (field_id >= D4EST_HIP_FIELD_LORENTZIAN_U && field_id <= D4EST_HIP_FIELD_LORENTZIAN_ROBIN)) return F;
   if (!params) D4EST_HIP_ABORT("%s: params is NULL", who);
-  if (field_id <= D4EST_HIP_FIELD_PUNCTURE_B) {
+  if (field_id == D4EST_HIP_FIELD_OKENDON_U) {
+    if (n_params != 1 || !(params[0] > 0. && params[0] < 1.))   // okendon_params_init asserts the range (okendon_fcns.h:65)
+      D4EST_HIP_ABORT("%s: the Okendon field takes the 1 param {p}, 0 < p < 1; n_params = %d", who, n_params);
+  } else if (field_id == D4EST_HIP_FIELD_BY_PSI || field_id == D4EST_HIP_FIELD_BY_A) {
+    if (n_params != 2) D4EST_HIP_ABORT("%s: the Boyen-York fields take the 2 params {a, P}, n_params = %d", who, n_params);
+  } else if (field_id >= D4EST_HIP_FIELD_STAMM_U) {
+    if (n_params != 3) D4EST_HIP_ABORT("%s: the Stamm fields take the 3 params {c2x, c2y, c2z}, n_params = %d", who, n_params);
+  } else if (field_id <= D4EST_HIP_FIELD_PUNCTURE_B) {
     if (n_params < 2) D4EST_HIP_ABORT("%s: the puncture fields take {num_punctures, puncture_eps, per puncture C[3], P[3], S[3], M}", who);
     if (!(params[0] >= 1. && params[0] < (double)D4EST_HIP_MAX_PUNCTURES) || params[0] != std::floor(params[0]))
       D4EST_HIP_ABORT("%s: num_punctures = %g (1 .. %d)", who, params[0], D4EST_HIP_MAX_PUNCTURES - 1);
@@ -342,18 +443,24 @@ static void launch_nodes(d4est_hip_plan* plan, int mode, CoordSrc S, const NodeT
   HIP_CHECK(hipGetLastError());
 }
 
-static void set_term(d4est_hip_plan* plan, bool puncture, const double* params, int n_params, CoordSrc S,
+// the problem families with a term setter: node_kernel's mode
+enum Term { kTermPuncture = 1, kTermCds = 2, kTermOkendon = 3, kTermBoyenYork = 4 };
+
+static void set_term(d4est_hip_plan* plan, Term term, const double* params, int n_params, CoordSrc S,
                      const std::vector<CellDesc>* cells, const char* who) {
-  const FieldParams F = field_params(puncture ? D4EST_HIP_FIELD_PUNCTURE_A : D4EST_HIP_FIELD_CDS_A, params, n_params, who);
+  const int field = term == kTermPuncture ? D4EST_HIP_FIELD_PUNCTURE_A : term == kTermCds ? D4EST_HIP_FIELD_CDS_A
+                  : term == kTermOkendon ? D4EST_HIP_FIELD_OKENDON_U : D4EST_HIP_FIELD_BY_A;
+  const FieldParams F = field_params(field, params, n_params, who);
   double *a = nullptr, *b = nullptr;
-  nonlinear_term_arrays(plan, puncture ? -7 : 5, puncture, &a, &b);
+  if (term == kTermOkendon) nonlinear_term_arrays_real(plan, params[0], false, &a, &b);   // |u|^p: s = p
+  else nonlinear_term_arrays(plan, term == kTermCds ? 5 : -7, term == kTermPuncture, &a, &b);
   if (plan->n_elements == 0) return;
   if (cells) {
     const NodeTables nt = stage_cells_and_nodes(plan, *cells);
     S.cells = nt.d_cells;
-    launch_nodes(plan, puncture ? 1 : 2, S, &nt, 1, F, a, b);
+    launch_nodes(plan, term, S, &nt, 1, F, a, b);
   } else {
-    launch_nodes(plan, puncture ? 1 : 2, S, nullptr, 1, F, a, b);
+    launch_nodes(plan, term, S, nullptr, 1, F, a, b);
   }
 }
 
@@ -373,7 +480,8 @@ static void boundary_launch(d4est_hip_plan* plan, int mode, int coeff_id, int rh
   const double* sj = nullptr;
   double *out_a = xyz_out, *out_b = nullptr;
   if (mode == 1) {
-    if (coeff_id != D4EST_HIP_ROBIN_COEFF_INV_R && coeff_id != D4EST_HIP_ROBIN_COEFF_BRICK) D4EST_HIP_ABORT("%s: unknown coeff_id %d", who, coeff_id);
+    if (coeff_id != D4EST_HIP_ROBIN_COEFF_INV_R && coeff_id != D4EST_HIP_ROBIN_COEFF_BRICK && coeff_id != D4EST_HIP_ROBIN_COEFF_LORENTZIAN)
+      D4EST_HIP_ABORT("%s: unknown coeff_id %d", who, coeff_id);
     if (rhs_id != D4EST_HIP_ROBIN_RHS_ZERO && rhs_id != D4EST_HIP_ROBIN_RHS_INV_R) D4EST_HIP_ABORT("%s: unknown rhs_id %d", who, rhs_id);
     if (coeff_id == D4EST_HIP_ROBIN_COEFF_BRICK && S.kind != 0)
       D4EST_HIP_ABORT("%s: ROBIN_COEFF_BRICK needs the brick source (the face normal is +-e_axis on a brick only)", who);
@@ -409,6 +517,90 @@ static void boundary_launch(d4est_hip_plan* plan, int mode, int coeff_id, int rh
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(plan->stream));
   HIP_CHECK(hipFree(d_units));
+}
+
+// ---- the load vector V^T W J f(x_quad) of a field id ----------------------------------------------------------------------------------
+// The pointwise function of nonlin_body (d4est_hip_pointwise.h) without a forward half: the node's point from the element's cell
+// description and the bucket's quadrature abscissae (or the caller's coordinates), then the field.  elem_ids and nodes are the
+// launch's bucket's: entry ei of its element lists, NQ abscissae
+struct LoadField {
+  static constexpr bool kForward = false;
+  int beta;
+  int id;
+  const int* elem_ids;
+  const double* nodes;
+  CoordSrc S;
+  FieldParams F;
+  __device__ __forceinline__ double term(int ei, int q, int a, int b, int kq, double) const {
+    double x[3];
+    if (S.kind == 2) {
+      x[0] = S.xyz[q]; x[1] = S.xyz[S.total + q]; x[2] = S.xyz[2 * S.total + q];
+    } else {
+      const CellDesc cell = S.cells[elem_ids[ei]];
+      const double r[3] = {nodes[a], nodes[b], nodes[kq]};
+      cell_point(S, cell, r, x);
+    }
+    return field_value(id, F, x[0], x[1], x[2]);
+  }
+};
+
+// out = beta out + V^T W J f(x_quad): one kernel per bucket where d4est_hip_apply_galerkin_integral has a one-kernel path (every
+// bucket a built pair: plan_pairs_built, the nonlinear term's own condition), else coordinates, field_eval and the integral through
+// plan-owned temporaries
+static void build_load(d4est_hip_plan* plan, int field_id, const double* params, int n_params, CoordSrc S,
+                       const std::vector<CellDesc>* cells, int beta, double* out, const char* who) {
+  const FieldParams F = field_params(field_id, params, n_params, who);
+  if (beta != 0 && beta != 1) D4EST_HIP_ABORT("%s: beta = %d (0 or 1)", who, beta);
+  if (!out && plan->local_nodes > 0) D4EST_HIP_ABORT("%s: out_dev is NULL", who);
+  if (!plan->has_geometry) D4EST_HIP_ABORT("%s: d4est_hip_plan_set_geometry was not called", who);
+  if (plan->n_elements == 0 || plan->local_nodes == 0) return;
+  NodeTables nt = {};
+  if (cells) {
+    nt = stage_cells_and_nodes(plan, *cells);
+    S.cells = nt.d_cells;
+  }
+  if (plan_pairs_built(plan)) {
+    for (size_t bi = 0; bi < plan->buckets.size(); ++bi) {
+      const Bucket& bk = plan->buckets[bi];
+      if (bk.n_elem == 0) continue;
+      LoadField P = {};
+      P.beta = beta;
+      P.id = field_id;
+      P.elem_ids = plan->d_elem_ids + bk.elem_offset;
+      P.nodes = cells ? nt.d_nodes + (2 * bi + 1) * (size_t)nt.stride : nullptr;
+      P.S = S;
+      P.F = F;
+      for_built_pair(bk.N, bk.NQ, [&](auto n, auto nq) {
+        constexpr int N = decltype(n)::value, NQ = decltype(nq)::value;
+        using C = WaveCfg<N, NQ>;
+        set_lds_limit(nonlin_kernel<N, NQ, false, LoadField>, C::LDS_BYTES);
+        hipLaunchKernelGGL((nonlin_kernel<N, NQ, false, LoadField>), dim3((bk.n_elem + C::EPB - 1) / C::EPB), dim3(C::THREADS), C::LDS_BYTES,
+                           plan->stream, nullptr, out, plan->d_J, plan->d_ns_list + bk.elem_offset, plan->d_qs_list + bk.elem_offset, bk.n_elem,
+                           bk.d_EBb, bk.d_EBf, bk.d_w, P, nullptr, nullptr);
+      });
+    }
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  // composed: the three calls a caller would make, through plan-owned temporaries (no allocation after the first call, no
+  // synchronisation: the load is rebuilt on every AMR level)
+  const size_t nq = (size_t)plan->local_nodes_quad, n = (size_t)plan->local_nodes;
+  double *d_f = nullptr, *d_xyz = nullptr;
+  nonlinear_load_scratch(plan, S.kind != 2, &d_f, &d_xyz);
+  const double* xyz = S.xyz;
+  if (S.kind != 2) {
+    launch_nodes(plan, 0, S, &nt, 1, F, d_xyz, nullptr);
+    xyz = d_xyz;
+  }
+  hipLaunchKernelGGL(field_eval_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, plan->stream, field_id, F, xyz, (long long)nq, d_f);
+  if (!beta) {
+    launch_mass_like(plan, 1, d_f, out);
+  } else {
+    if (!plan->d_work_m) HIP_CHECK(hipMalloc(&plan->d_work_m, n * sizeof(double)));
+    launch_mass_like(plan, 1, d_f, plan->d_work_m);
+    launch_add(plan, (int)n, plan->d_work_m, out);
+  }
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace d4est_hip
@@ -449,7 +641,7 @@ void d4est_hip_plan_set_puncture_term_brick(d4est_hip_plan_t* plan, const double
   const char* who = "plan_set_puncture_term_brick";
   if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
   const std::vector<CellDesc> cells = brick_cells(plan, elem_q, elem_dq, root_len, extents, who);
-  set_term(plan, true, params, n_params, brick_src(root_len, extents), &cells, who);
+  set_term(plan, kTermPuncture, params, n_params, brick_src(root_len, extents), &cells, who);
 }
 
 void d4est_hip_plan_set_puncture_term_analytic(d4est_hip_plan_t* plan, const double* params, int n_params, int geom_type,
@@ -459,13 +651,13 @@ void d4est_hip_plan_set_puncture_term_analytic(d4est_hip_plan_t* plan, const dou
   if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
   const CoordSrc S = analytic_src(geom_type, geom_params, root_len, who);
   const std::vector<CellDesc> cells = analytic_cells(plan, geom_type, elem_tree, elem_q, elem_dq, root_len, who);
-  set_term(plan, true, params, n_params, S, &cells, who);
+  set_term(plan, kTermPuncture, params, n_params, S, &cells, who);
 }
 
 void d4est_hip_plan_set_puncture_term_xyz(d4est_hip_plan_t* plan, const double* params, int n_params, const double* xyz_quad_dev) {
   const char* who = "plan_set_puncture_term_xyz";
   if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
-  set_term(plan, true, params, n_params, xyz_src(plan, xyz_quad_dev, who), nullptr, who);
+  set_term(plan, kTermPuncture, params, n_params, xyz_src(plan, xyz_quad_dev, who), nullptr, who);
 }
 
 void d4est_hip_plan_set_cds_term_brick(d4est_hip_plan_t* plan, const double* params, int n_params, const int* elem_q, const int* elem_dq,
@@ -473,7 +665,7 @@ void d4est_hip_plan_set_cds_term_brick(d4est_hip_plan_t* plan, const double* par
   const char* who = "plan_set_cds_term_brick";
   if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
   const std::vector<CellDesc> cells = brick_cells(plan, elem_q, elem_dq, root_len, extents, who);
-  set_term(plan, false, params, n_params, brick_src(root_len, extents), &cells, who);
+  set_term(plan, kTermCds, params, n_params, brick_src(root_len, extents), &cells, who);
 }
 
 void d4est_hip_plan_set_cds_term_analytic(d4est_hip_plan_t* plan, const double* params, int n_params, int geom_type,
@@ -483,13 +675,86 @@ void d4est_hip_plan_set_cds_term_analytic(d4est_hip_plan_t* plan, const double* 
   if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
   const CoordSrc S = analytic_src(geom_type, geom_params, root_len, who);
   const std::vector<CellDesc> cells = analytic_cells(plan, geom_type, elem_tree, elem_q, elem_dq, root_len, who);
-  set_term(plan, false, params, n_params, S, &cells, who);
+  set_term(plan, kTermCds, params, n_params, S, &cells, who);
 }
 
 void d4est_hip_plan_set_cds_term_xyz(d4est_hip_plan_t* plan, const double* params, int n_params, const double* xyz_quad_dev) {
   const char* who = "plan_set_cds_term_xyz";
   if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
-  set_term(plan, false, params, n_params, xyz_src(plan, xyz_quad_dev, who), nullptr, who);
+  set_term(plan, kTermCds, params, n_params, xyz_src(plan, xyz_quad_dev, who), nullptr, who);
+}
+
+void d4est_hip_plan_set_okendon_term_brick(d4est_hip_plan_t* plan, const double* params, int n_params, const int* elem_q,
+                                           const int* elem_dq, double root_len, const double* extents) {
+  const char* who = "plan_set_okendon_term_brick";
+  if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
+  const std::vector<CellDesc> cells = brick_cells(plan, elem_q, elem_dq, root_len, extents, who);
+  set_term(plan, kTermOkendon, params, n_params, brick_src(root_len, extents), &cells, who);
+}
+
+void d4est_hip_plan_set_okendon_term_analytic(d4est_hip_plan_t* plan, const double* params, int n_params, int geom_type,
+                                              const double* geom_params, const int* elem_tree, const int* elem_q, const int* elem_dq,
+                                              double root_len) {
+  const char* who = "plan_set_okendon_term_analytic";
+  if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
+  const CoordSrc S = analytic_src(geom_type, geom_params, root_len, who);
+  const std::vector<CellDesc> cells = analytic_cells(plan, geom_type, elem_tree, elem_q, elem_dq, root_len, who);
+  set_term(plan, kTermOkendon, params, n_params, S, &cells, who);
+}
+
+void d4est_hip_plan_set_okendon_term_xyz(d4est_hip_plan_t* plan, const double* params, int n_params, const double* xyz_quad_dev) {
+  const char* who = "plan_set_okendon_term_xyz";
+  if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
+  set_term(plan, kTermOkendon, params, n_params, xyz_src(plan, xyz_quad_dev, who), nullptr, who);
+}
+
+void d4est_hip_plan_set_boyen_york_term_brick(d4est_hip_plan_t* plan, const double* params, int n_params, const int* elem_q,
+                                              const int* elem_dq, double root_len, const double* extents) {
+  const char* who = "plan_set_boyen_york_term_brick";
+  if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
+  const std::vector<CellDesc> cells = brick_cells(plan, elem_q, elem_dq, root_len, extents, who);
+  set_term(plan, kTermBoyenYork, params, n_params, brick_src(root_len, extents), &cells, who);
+}
+
+void d4est_hip_plan_set_boyen_york_term_analytic(d4est_hip_plan_t* plan, const double* params, int n_params, int geom_type,
+                                                 const double* geom_params, const int* elem_tree, const int* elem_q, const int* elem_dq,
+                                                 double root_len) {
+  const char* who = "plan_set_boyen_york_term_analytic";
+  if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
+  const CoordSrc S = analytic_src(geom_type, geom_params, root_len, who);
+  const std::vector<CellDesc> cells = analytic_cells(plan, geom_type, elem_tree, elem_q, elem_dq, root_len, who);
+  set_term(plan, kTermBoyenYork, params, n_params, S, &cells, who);
+}
+
+void d4est_hip_plan_set_boyen_york_term_xyz(d4est_hip_plan_t* plan, const double* params, int n_params, const double* xyz_quad_dev) {
+  const char* who = "plan_set_boyen_york_term_xyz";
+  if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
+  set_term(plan, kTermBoyenYork, params, n_params, xyz_src(plan, xyz_quad_dev, who), nullptr, who);
+}
+
+void d4est_hip_plan_build_load_by_id_brick(d4est_hip_plan_t* plan, int field_id, const double* params, int n_params, const int* elem_q,
+                                           const int* elem_dq, double root_len, const double* extents, int beta, double* out_dev) {
+  const char* who = "plan_build_load_by_id_brick";
+  if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
+  const std::vector<CellDesc> cells = brick_cells(plan, elem_q, elem_dq, root_len, extents, who);
+  build_load(plan, field_id, params, n_params, brick_src(root_len, extents), &cells, beta, out_dev, who);
+}
+
+void d4est_hip_plan_build_load_by_id_analytic(d4est_hip_plan_t* plan, int field_id, const double* params, int n_params, int geom_type,
+                                              const double* geom_params, const int* elem_tree, const int* elem_q, const int* elem_dq,
+                                              double root_len, int beta, double* out_dev) {
+  const char* who = "plan_build_load_by_id_analytic";
+  if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
+  const CoordSrc S = analytic_src(geom_type, geom_params, root_len, who);
+  const std::vector<CellDesc> cells = analytic_cells(plan, geom_type, elem_tree, elem_q, elem_dq, root_len, who);
+  build_load(plan, field_id, params, n_params, S, &cells, beta, out_dev, who);
+}
+
+void d4est_hip_plan_build_load_by_id_xyz(d4est_hip_plan_t* plan, int field_id, const double* params, int n_params,
+                                         const double* xyz_quad_dev, int beta, double* out_dev) {
+  const char* who = "plan_build_load_by_id_xyz";
+  if (!plan) D4EST_HIP_ABORT("%s: NULL plan", who);
+  build_load(plan, field_id, params, n_params, xyz_src(plan, xyz_quad_dev, who), nullptr, beta, out_dev, who);
 }
 
 void d4est_hip_plan_compute_boundary_xyz_brick(d4est_hip_plan_t* plan, const int* elem_q, const int* elem_dq, double root_len,

@@ -633,6 +633,15 @@ int d4est_hip_fcg_solve(d4est_hip_plan_t* plan, double* u_dev, const double* rhs
  * The power is |k| multiplications (k < 0: one division of 1 by the product), never pow: the ConstantDensityStar callbacks multiply out,
  * and TwoPunctures' pow(psi^2, 3.5) differs from the product in the last bits only. */
 void d4est_hip_plan_set_nonlinear_power(d4est_hip_plan_t* plan, const double* a_quad_dev, const double* b_quad_dev, int k);
+/* The real form f(x, u) = a |b + u|^s with Jacobian s a |b + u|^(s-1): Okendon's callbacks pow(u*u, .5*p) and p / pow(u*u, .5*(1.-p)),
+ * 0 < p < 1 (src/Problems/Okendon/okendon_fcns.h:114-145).  Capture semantics as set_nonlinear_power (plan-owned copies, b == NULL: 0,
+ * a == NULL: the term is off).  Evaluated the reference's way with t = b + V u: a * pow(t*t, 0.5*s) and s * a / pow(t*t, 0.5*(1.-s));
+ * nothing is clamped at t = 0, the IEEE result stands (s < 1: the Jacobian is +-inf there, as in the reference).  Setting either form
+ * clears the other.  d4est_hip_apply_nonlinear_term, _plan_linearise, _plan_nonlinear_fused, _build_residual and _newton_solve take
+ * whichever form is set, with the same one-kernel instances, mixed-degree launch and three-call fallback.  s must be finite. */
+void d4est_hip_plan_set_nonlinear_abs_power(d4est_hip_plan_t* plan, const double* a_quad_dev, const double* b_quad_dev, double s);
+/* returns 1 and writes s (s may be NULL) when the real form is set, else 0 */
+int d4est_hip_plan_nonlinear_exponent(const d4est_hip_plan_t* plan, double* s);
 /* out = beta out + V^T W J f(x, V u) per element, beta = 0 or 1: the loop of d4est_quadrature_apply_fofufofvlj followed by axpy 1.0
  * (constant_density_star_fcns.h:360-437 with src/Quadrature/d4est_quadrature.c:776-936).  ONE kernel -- interpolate, pointwise,
  * integrate, no quadrature-sized temporary -- for every (deg, deg_quad) pair d4est_hip_apply_galerkin_integral serves with a one-kernel
@@ -1124,6 +1133,16 @@ void d4est_hip_probe_xyz(d4est_hip_probe_t* probe, double* xyz_host);
  *                boundary function (:303-330)
  *   INV_R        1 / sqrt(x^2 + y^2 + z^2): two_punctures_robin_coeff_sphere_fcn (two_punctures_fcns.h:640-655),
  *                constant_density_star_robin_coeff_sphere_fcn and _robin_bc_rhs_for_res_fcn (constant_density_star_fcns.h:9-24, :42-57)
+ *   OKENDON_U    okendon_analytic_solution, DIM == 3 (src/Problems/Okendon/okendon_fcns.h:70-96): M r2^(1/(1-p)),
+ *                M = 1 / pow((2/(1-p)) (1 + 2/(1-p)), 1/(1-p)); also its boundary function (:99-111)
+ *   BY_PSI       boyen_york_model_analytic_solution (src/Problems/BoyenYorkModel/boyen_york_model_fcns.h:67-95):
+ *                pow(1 + 2E/r + 6a^2/r^2 + 2a^2E/r^3 + a^4/r^4, .25), E = sqrt(P^2 + 4a^2); also its boundary function (:97-108)
+ *   BY_A         boyen_york_model_helmholtz_fcn (:110-128): .75 (P^2/r^4) (1 - a^2/r^2)^2, the `a` of the residual callback (:131-149)
+ *   LORENTZIAN_U      poisson_lorentzian_analytic_solution (src/Problems/Poisson/poisson_lorentzian_fcns.h:55-67): 1 / sqrt(1 + r^2)
+ *   LORENTZIAN_RHS    poisson_lorentzian_rhs_fcn (:71-82): 3 / pow(1 + r^2, 2.5)
+ *   LORENTZIAN_ROBIN  poisson_lorentzian_robin_coeff_fcn (:22-36): sqrt(r2) / (1 + r2)
+ *   STAMM_U      stamm_analytic_solution, DIM == 3 (src/Problems/Stamm/stamm_fcns.h:78-114): x(1-x) y(1-y) z(1-z) |x - c2|^3
+ *   STAMM_RHS    stamm_rhs_fcn, DIM == 3 (:149-208), its thirteen terms in the reference's order; exactly 0.0 at x = c2
  * Two behaviours of the reference are kept:
  *   (a) compute_confAij moves a point that lies exactly on a puncture to r = puncture_eps (:202-203): n = 0 there, the puncture
  *       contributes nothing and K2 is finite;
@@ -1133,7 +1152,8 @@ void d4est_hip_probe_xyz(d4est_hip_probe_t* probe, double* xyz_host);
  * params (host doubles): the puncture fields take {num_punctures, puncture_eps, then per puncture C[3], P[3], S[3], M}, n_params =
  * 2 + 10 num_punctures, 1 <= num_punctures <= 9 (the reference's num_punctures < MAX_PUNCTURES = 10); the star fields take {cx, cy, cz,
  * R, rho0, C0, alpha, beta}, n_params = 8 (alpha from the reference's bisection, constant_density_star_fcns.h:151-243, which stays on the
- * host); INV_R takes none (params may be NULL).  A bad id or count aborts.
+ * host); INV_R and the three Lorentzian fields take none (params may be NULL); OKENDON_U takes {p}, 0 < p < 1 (the range
+ * okendon_params_init asserts); BY_PSI and BY_A take {a, P}; STAMM_U and STAMM_RHS take {c2x, c2y, c2z}.  A bad id or count aborts.
  *
  * d4est_hip_field_eval: out_dev[i] = field(xyz_dev[i], xyz_dev[n + i], xyz_dev[2 n + i]), the x | y | z layout of
  * d4est_hip_plan_compute_xyz_analytic; one thread per point on hip_stream (a hipStream_t, NULL = the default stream), no host
@@ -1144,6 +1164,14 @@ void d4est_hip_probe_xyz(d4est_hip_probe_t* probe, double* xyz_host);
 #define D4EST_HIP_FIELD_CDS_A 3
 #define D4EST_HIP_FIELD_CDS_PSI 4
 #define D4EST_HIP_FIELD_INV_R 5
+#define D4EST_HIP_FIELD_OKENDON_U 6
+#define D4EST_HIP_FIELD_BY_PSI 7
+#define D4EST_HIP_FIELD_BY_A 8
+#define D4EST_HIP_FIELD_LORENTZIAN_U 9
+#define D4EST_HIP_FIELD_LORENTZIAN_RHS 10
+#define D4EST_HIP_FIELD_LORENTZIAN_ROBIN 11
+#define D4EST_HIP_FIELD_STAMM_U 12
+#define D4EST_HIP_FIELD_STAMM_RHS 13
 #define D4EST_HIP_MAX_PUNCTURES 10
 void d4est_hip_field_eval(void* hip_stream, int field_id, const double* params, int n_params, const double* xyz_dev, long long n,
                           double* out_dev);
@@ -1177,8 +1205,41 @@ void d4est_hip_plan_set_cds_term_analytic(d4est_hip_plan_t* plan, const double* 
                                           const double* geom_params, const int* elem_tree, const int* elem_q, const int* elem_dq,
                                           double root_len);
 void d4est_hip_plan_set_cds_term_xyz(d4est_hip_plan_t* plan, const double* params, int n_params, const double* xyz_quad_dev);
-/* the plan-owned a and b (device, local_nodes_quad doubles; *b_dev NULL: b = 0) and k of the power term that is set; returns 0 and
- * writes nothing when the term is off.  Any output may be NULL.  The arrays live until the term is switched off or the plan destroyed. */
+/* The same for the two remaining nonlinear families, by the same kernel:
+ *   Okendon     f = |u|^p as okendon_build_residual adds it to A u (okendon_fcns.h:328-406): a = +1, b = NULL, the REAL form with s = p
+ *               (params = {p}); afterwards the plan is as d4est_hip_plan_set_nonlinear_abs_power(a, NULL, p) leaves it
+ *   Boyen-York  f = BY_A u^-7 as boyen_york_model_build_residual adds it (boyen_york_model_fcns.h:239-332): a = BY_A, b = NULL, the
+ *               integer form with k = -7 (params = {a, P}).  The reference's 1 / pow(u*u, 3.5) is u^-7 for the positive u it assumes
+ *               (:142), the decision TwoPunctures' pow(psi^2, 3.5) got. */
+void d4est_hip_plan_set_okendon_term_brick(d4est_hip_plan_t* plan, const double* params, int n_params, const int* elem_q,
+                                           const int* elem_dq, double root_len, const double* extents);
+void d4est_hip_plan_set_okendon_term_analytic(d4est_hip_plan_t* plan, const double* params, int n_params, int geom_type,
+                                              const double* geom_params, const int* elem_tree, const int* elem_q, const int* elem_dq,
+                                              double root_len);
+void d4est_hip_plan_set_okendon_term_xyz(d4est_hip_plan_t* plan, const double* params, int n_params, const double* xyz_quad_dev);
+void d4est_hip_plan_set_boyen_york_term_brick(d4est_hip_plan_t* plan, const double* params, int n_params, const int* elem_q,
+                                              const int* elem_dq, double root_len, const double* extents);
+void d4est_hip_plan_set_boyen_york_term_analytic(d4est_hip_plan_t* plan, const double* params, int n_params, int geom_type,
+                                                 const double* geom_params, const int* elem_tree, const int* elem_q, const int* elem_dq,
+                                                 double root_len);
+void d4est_hip_plan_set_boyen_york_term_xyz(d4est_hip_plan_t* plan, const double* params, int n_params, const double* xyz_quad_dev);
+/* The load vector of a linear problem from a field id: out = beta out + V^T W J f(x_quad) per element, beta = 0 or 1 -- what the
+ * Poisson and Stamm drivers build with d4est_mesh_init_field on the quadrature nodes followed by
+ * d4est_quadrature_apply_galerkin_integral (src/Quadrature/d4est_quadrature.c:142-213).  ONE kernel per degree bucket (map, field,
+ * integrate; no coordinate or quadrature-sized temporary) when every element's (deg, deg_quad) is a pair
+ * d4est_hip_apply_galerkin_integral serves with a one-kernel path; else d4est_hip_plan_compute_xyz_*, d4est_hip_field_eval and
+ * d4est_hip_apply_galerkin_integral through plan-owned temporaries (allocated on first use, no synchronisation).  The one-kernel path
+ * integrates with the even-odd contractions: its bits equal the three-call composition's while D4EST_HIP_TUNE_STIFFNESS_EO has its
+ * default (on); with the key off the two agree to rounding.  Any field id, sources as for the term entries; needs plan_set_geometry (J). */
+void d4est_hip_plan_build_load_by_id_brick(d4est_hip_plan_t* plan, int field_id, const double* params, int n_params, const int* elem_q,
+                                           const int* elem_dq, double root_len, const double* extents, int beta, double* out_dev);
+void d4est_hip_plan_build_load_by_id_analytic(d4est_hip_plan_t* plan, int field_id, const double* params, int n_params, int geom_type,
+                                              const double* geom_params, const int* elem_tree, const int* elem_q, const int* elem_dq,
+                                              double root_len, int beta, double* out_dev);
+void d4est_hip_plan_build_load_by_id_xyz(d4est_hip_plan_t* plan, int field_id, const double* params, int n_params,
+                                         const double* xyz_quad_dev, int beta, double* out_dev);
+/* the plan-owned a and b (device, local_nodes_quad doubles; *b_dev NULL: b = 0) and k of the power term that is set (k = 0 while the
+ * real form is set: d4est_hip_plan_nonlinear_exponent); returns 0 and writes nothing when the term is off.  Any output may be NULL.  The arrays live until the term is switched off or the plan destroyed. */
 int d4est_hip_plan_nonlinear_coefficients(const d4est_hip_plan_t* plan, const double** a_dev, const double** b_dev, int* k);
 /* xyz_m_mortar_quad of the boundary faces (src/Mesh/d4est_mesh.c:514-640, consumed at src/dGMath/d4est_laplacian_flux.c:47-112,
  * :200-204): x | y | z at the mortar quadrature nodes of every boundary side, indexed like sj -- side_mortar_stride[s] + k, the
@@ -1194,7 +1255,8 @@ void d4est_hip_plan_compute_boundary_xyz_analytic(d4est_hip_plan_t* plan, int ge
                                                   const int* elem_q, const int* elem_dq, double root_len, double* xyz_mortar_dev);
 /* Robin data from callback ids: one kernel over the boundary sides' mortar nodes evaluates the map, the coefficient and the right-hand
  * side and writes sj coeff and sj rhs into the plan's Robin arrays -- the state d4est_hip_plan_set_robin_values leaves, without a
- * coordinate array in between.  coeff_id: ROBIN_COEFF_INV_R (the sphere callbacks cited at INV_R) or ROBIN_COEFF_BRICK
+ * coordinate array in between.  coeff_id: ROBIN_COEFF_INV_R (the sphere callbacks cited at INV_R), ROBIN_COEFF_LORENTZIAN
+ * (LORENTZIAN_ROBIN above, with ROBIN_RHS_ZERO: poisson_lorentzian_robin_bc_rhs_fcn, poisson_lorentzian_fcns.h:38-52) or ROBIN_COEFF_BRICK
  * (two_punctures_robin_coeff_brick_fcn, two_punctures_fcns.h:612-638: n_axis x_axis / r^2; on a brick the normal of face f is
  * +-e_axis, so the coefficient is sign(f) x_axis / r^2 and no normal array is read); rhs_id: ROBIN_RHS_ZERO (two_punctures_robin_bc_rhs_fcn
  * :659-673, constant_density_star_robin_bc_rhs_for_jac_fcn :26-40) or ROBIN_RHS_INV_R (constant_density_star_robin_bc_rhs_for_res_fcn
@@ -1202,9 +1264,10 @@ void d4est_hip_plan_compute_boundary_xyz_analytic(d4est_hip_plan_t* plan, int ge
  * d4est_hip_plan_set_robin_values(plan, NULL, ...) still switches back to Dirichlet.
  * Dirichlet data needs no entry of its own: d4est_hip_field_eval(CDS_PSI) on the three d4est_hip_plan_boundary_gather'ed Lobatto
  * coordinate vectors (stored x | y | z) gives the array d4est_hip_plan_set_dirichlet_values(on_device = 1) takes.
- * Not built: the Lorentzian and Stamm problem functions, the Cactus-data variants, the alpha bisection. */
+ * Not built: the Cactus-data variants and the alpha bisection. */
 #define D4EST_HIP_ROBIN_COEFF_INV_R 0
 #define D4EST_HIP_ROBIN_COEFF_BRICK 1
+#define D4EST_HIP_ROBIN_COEFF_LORENTZIAN 2
 #define D4EST_HIP_ROBIN_RHS_ZERO 0
 #define D4EST_HIP_ROBIN_RHS_INV_R 1
 void d4est_hip_plan_set_robin_by_id_brick(d4est_hip_plan_t* plan, int coeff_id, int rhs_id, const int* elem_q, const int* elem_dq,

@@ -9,7 +9,9 @@ with the TwoPunctures-shaped power k = -7 and a, b given at the quadrature nodes
   (d4est_hip_apply_weighted_mass_matrix on the separate path does not read w J c, so the composed row times the pass by the difference
   between the first apply_lhs after set_lhs_coefficient and a second one; both rows are printed).
 Event-timed on the plan's stream after warm-up, 50 repetitions, median / min / max; the two forms alternate.  The composed rows use only
-entry points the library had before the fused ones, so the script gives the baseline on an older checkout (fused rows are skipped)."""
+entry points the library had before the fused ones, so the script gives the baseline on an older checkout (fused rows are skipped).
+Where the library has the real form a |b + u|^s (d4est_hip_plan_set_nonlinear_abs_power, s = 0.5) the same two comparisons are timed
+for it: the rows term_abs_* and linearise_abs_*."""
 import json
 import os
 import statistics
@@ -22,7 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from disco4est_amd import Plan, mesh as M  # noqa: E402
 
 dev = torch.device("cuda:0")
-REPS, WARM, K = 50, 5, -7
+REPS, WARM, K, S_ABS = 50, 5, -7, 0.5
 
 
 def timed_pair(fns, stream):
@@ -84,6 +86,32 @@ def case(name, degs, stream):
             plan.apply_lhs(u, out2)
         lin["linearise_fused_plus_apply_lhs"] = lin_fused
     res.update(timed_pair(lin, stream))
+    if hasattr(plan, "set_nonlinear_abs_power"):
+        def term_abs_composed():
+            plan.interpolate(u, uq)
+            t = b + uq
+            plan.apply_galerkin_integral(a * torch.pow(t * t, 0.5 * S_ABS), out)
+
+        def lin_abs_composed():
+            plan.interpolate(u, uq)
+            t = b + uq
+            plan.set_lhs_coefficient((S_ABS * a) / torch.pow(t * t, 0.5 * (1.0 - S_ABS)))
+            plan.apply_lhs(u, out)
+
+        def lin_abs_fused():
+            plan.linearise(u)
+            plan.apply_lhs(u, out2)
+        plan.set_nonlinear_abs_power(a, b, S_ABS)
+        res.update(timed_pair({"term_abs_composed": term_abs_composed,
+                               "term_abs_fused": lambda: plan.apply_nonlinear_term(u, out2, 0)}, stream))
+        res.update(timed_pair({"linearise_abs_composed_plus_apply_lhs": lin_abs_composed,
+                               "linearise_abs_fused_plus_apply_lhs": lin_abs_fused}, stream))
+        with torch.cuda.stream(stream):
+            term_abs_composed()
+            plan.apply_nonlinear_term(u, out2, 0)
+        stream.synchronize()
+        res["term_abs_rel_inf_difference"] = float((out - out2).abs().max() / out.abs().max())
+        plan.set_nonlinear_power(a, b, K)
     if fused:
         with torch.cuda.stream(stream):   # (the torch expression must run on the plan's stream)
             term_composed()

@@ -1,7 +1,9 @@
 """Times the one-kernel puncture-term set-up (Plan.set_puncture_term, csrc/d4est_hip_problem.hip) against the path it replaces:
 compute_xyz_analytic, a download, the numpy evaluation of a and b (tests/dense_problem.py, the reference's loop order), an upload and
 set_nonlinear_power.  Mesh: the 13-tree cubed sphere at level 3, p = 7, two punctures (init_two_punctures_data's values).
-Writes profiles/time_problem.json (or --out).  Usage: python tools/time_problem.py [--level 3] [--deg 7] [--reps 20] [--out FILE]"""
+Also times the load vector by id (Plan.build_load, STAMM_RHS and LORENTZIAN_RHS) against the three calls it replaces -- compute_xyz_analytic,
+field_eval, apply_galerkin_integral -- and the Boyen-York / Okendon term setters (rows load_* and set_*_term_s; the geometric factors are
+set for them).  Writes profiles/time_problem.json (or --out).  Usage: python tools/time_problem.py [--level 3] [--deg 7] [--reps 20] [--out FILE]"""
 import argparse
 import json
 import os
@@ -87,6 +89,34 @@ def main():
         capi.field_eval("PUNCTURE_A", params, xyz, o)
     sync()
     t_field = (time.perf_counter() - t0) / args.reps
+    # the load vector by id against its three-call composition, and the two new term setters
+    more = {}
+    plan.set_geometry_analytic(2, mp.params, tree, q, dq, m.nf)
+    n = plan.local_nodes
+    fq = torch.empty(nq, dtype=torch.float64, device=gpu)
+    load, load3 = torch.empty(n, dtype=torch.float64, device=gpu), torch.empty(n, dtype=torch.float64, device=gpu)
+
+    def timed(fn):
+        fn()
+        sync()
+        ts = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            fn()
+            sync()
+            ts.append(time.perf_counter() - t0)
+        return {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))}
+    for fid, pr in (("STAMM_RHS", capi.stamm_params(0.25, 0.3, 0.35)), ("LORENTZIAN_RHS", None)):
+        def three_calls():
+            plan.compute_xyz_analytic(*src, xyz_quad=xyz)
+            capi.field_eval(fid, pr, xyz, fq, getattr(plan, "_stream_handle", 0))
+            plan.apply_galerkin_integral(fq, load3)
+        more["load_%s_one_kernel_s" % fid] = timed(lambda: plan.build_load(fid, pr, load, analytic=src))
+        more["load_%s_three_calls_s" % fid] = timed(three_calls)
+        more["load_%s_bit_equal" % fid] = bool(torch.equal(load, load3))
+    more["load_one_kernel_path"] = bool(plan.nonlinear_fused())
+    more["set_boyen_york_term_s"] = timed(lambda: plan.set_boyen_york_term(capi.boyen_york_params(0.7, 1.3), analytic=src))
+    more["set_okendon_term_s"] = timed(lambda: plan.set_okendon_term(capi.okendon_params(0.5), analytic=src))
     scale = float(a_new.abs().max())
     res = {
         "tool": "tools/time_problem.py", "device": torch.cuda.get_device_name(0), "mesh": "cubed_sphere 13 trees, level %d, p = %d" % (args.level, args.deg),
@@ -98,6 +128,7 @@ def main():
         "max_abs_a_difference_between_paths": float((a_new - da).abs().max()), "max_abs_a": scale,
         "max_abs_b_difference_between_paths": float((b_new - db)[torch.isfinite(db)].abs().max()),
     }
+    res.update(more)
     plan.destroy()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
