@@ -63,7 +63,9 @@ def _check_aij(gpu, oracle, m, generic=False, fcn=0, tol=RTOL):
 def test_apply_aij_all_orientations(gpu, hiplib, oracle, deg, generic):
     """Two warped trees glued through each of the 144 (f_m, f_p, orientation) triples, both (-) views: apply_aij == oracle.  The
     oracle restates d4est_operators_reorient_face_data verbatim, so this is parity with the reference on ALL triples -- including
-    the 36 whose re-orientation is not geometric in the reference (forest.reference_reorientation_is_consistent)."""
+    the 36 whose re-orientation is not geometric in the reference (forest.reference_reorientation_is_consistent).
+    The two trees differ in degree, so no plan here has the direct tables: these meshes run the two-phase kernels under every _face_path
+    value (tests/test_forest_whole_operator_gpu.py holds the one-kernel forms to the oracle on the same triples, at one degree)."""
     codes = set()
     triples = _triples()
     step = 1 if deg <= 3 else 5            # the larger degrees sample the triples (every code still occurs)
@@ -80,7 +82,9 @@ def test_apply_aij_all_orientations(gpu, hiplib, oracle, deg, generic):
 @pytest.mark.parametrize("deg,generic", [(2, False), (2, True), (4, False), (8, False), (2, "split"), (5, "split")])
 def test_apply_aij_hanging_across_trees(gpu, hiplib, oracle, deg, generic):
     """A hanging (1 <-> 4) face ON the tree boundary, orientation 0..3 (d4est_reference_reorient_face_order), the refined tree on
-    either side, mixed p: record kernels (generic and tiled MFMA) against the oracle."""
+    either side, mixed p: record kernels (generic and tiled MFMA) against the oracle.  Hanging, mixed-degree meshes far below the
+    hybrid operator's default thresholds: the two-phase kernels under every _face_path value (the hanging-aware hybrid form on these
+    meshes: tests/test_forest_whole_operator_gpu.py)."""
     triples = _triples()
     seen_o = set()
     n_nongeometric = 0
