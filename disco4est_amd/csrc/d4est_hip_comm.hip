@@ -97,6 +97,16 @@ struct d4est_hip_rccl_exchange {
   long long n_exchanges = 0;
 };
 
+// per Schwarz handle: the segment starts of its four packed buffers (the handle owns the buffers and both ends' kernels)
+struct d4est_hip_schwarz_rccl_exchange {
+  d4est_hip_comm* comm = nullptr;
+  d4est_hip_schwarz* sz = nullptr;
+  d4est_hip_plan* plan = nullptr;                       // the subdomain plan: its stream orders the rounds
+  std::vector<int> peer;
+  std::vector<long long> send_first[2], recv_first[2];  // per direction
+  long long n_rounds = 0;
+};
+
 namespace {
 
 template <typename T>
@@ -148,6 +158,22 @@ void allreduce_hook(void* ctx, double* scalars_dev, int n) {
   on_comm_stream(x->comm, x->plan->stream, [&](hipStream_t cs) {
     RCCL_CHECK(rccl().AllReduce(scalars_dev, scalars_dev, (size_t)n, ncclDouble, ncclSum, x->comm->comm, cs));
   });
+}
+
+void schwarz_exchange_hook(void* ctx, int direction, const double* send_dev, double* recv_dev) {
+  auto* x = static_cast<d4est_hip_schwarz_rccl_exchange*>(ctx);
+  RcclApi& api = rccl();
+  const std::vector<long long>&sf = x->send_first[direction], &rf = x->recv_first[direction];
+  on_comm_stream(x->comm, x->plan->stream, [&](hipStream_t cs) {
+    RCCL_CHECK(api.GroupStart());
+    for (size_t p = 0; p < x->peer.size(); ++p) {
+      const long long nr = rf[p + 1] - rf[p], ns = sf[p + 1] - sf[p];
+      if (nr > 0) RCCL_CHECK(api.Recv(recv_dev + rf[p], (size_t)nr, ncclDouble, x->peer[p], x->comm->comm, cs));
+      if (ns > 0) RCCL_CHECK(api.Send(send_dev + sf[p], (size_t)ns, ncclDouble, x->peer[p], x->comm->comm, cs));
+    }
+    RCCL_CHECK(api.GroupEnd());
+  });
+  x->n_rounds++;
 }
 
 void comm_streams_create(d4est_hip_comm* c) {
@@ -301,6 +327,39 @@ void d4est_hip_comm_sendrecv(d4est_hip_comm_t* comm, d4est_hip_plan_t* plan, int
     RCCL_CHECK(api.GroupEnd());
   });
 }
+
+// ---- the Schwarz smoother's whole-element exchanges (d4est_hip_schwarz_set_element_exchange) over the communicator.  The handle packs and
+// unpacks; a direction is one grouped round on the communicator's stream between its event in and its event out, as comm_sendrecv.
+// NOT RUN ON HARDWARE YET: it needs two devices (tests/test_schwarz_rccl_gpu.py skips on one).
+d4est_hip_schwarz_rccl_exchange_t* d4est_hip_schwarz_set_rccl_exchange(d4est_hip_schwarz_t* sz, d4est_hip_comm_t* comm, int n_own_elements,
+                                                                       int n_peers, const int* peer_rank, const int* send_first,
+                                                                       const int* send_elem, const int* recv_first, const int* recv_elem) {
+  if (!sz || !comm) D4EST_HIP_ABORT("schwarz_set_rccl_exchange: NULL handle / communicator");
+  for (int p = 0; p < n_peers; ++p)
+    if (!peer_rank || peer_rank[p] < 0 || peer_rank[p] >= comm->world || peer_rank[p] == comm->rank)
+      D4EST_HIP_ABORT("schwarz_set_rccl_exchange: peer entry %d is not another rank of the communicator of %d ranks", p, comm->world);
+  auto* x = new d4est_hip_schwarz_rccl_exchange();
+  x->comm = comm;
+  x->sz = sz;
+  x->plan = d4est_hip::schwarz_subdomain_plan(sz);
+  d4est_hip_schwarz_set_element_exchange(sz, n_own_elements, n_peers, peer_rank, send_first, send_elem, recv_first, recv_elem, schwarz_exchange_hook, x);
+  x->peer.assign(peer_rank, peer_rank + n_peers);
+  for (int dir = 0; dir < 2; ++dir)
+    for (int p = 0; p <= n_peers; ++p) {
+      x->send_first[dir].push_back(d4est_hip_schwarz_exchange_first(sz, dir, 0, p));
+      x->recv_first[dir].push_back(d4est_hip_schwarz_exchange_first(sz, dir, 1, p));
+    }
+  return x;
+}
+
+void d4est_hip_schwarz_rccl_exchange_destroy(d4est_hip_schwarz_rccl_exchange_t* x) {
+  if (!x) return;
+  if (x->comm && x->comm->stream) (void)hipStreamSynchronize(x->comm->stream);
+  if (x->sz) d4est_hip_schwarz_set_element_exchange(x->sz, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  delete x;
+}
+
+long long d4est_hip_schwarz_rccl_exchange_count(const d4est_hip_schwarz_rccl_exchange_t* x) { return x ? x->n_rounds : 0; }
 
 void d4est_hip_comm_allreduce_sum(d4est_hip_comm_t* comm, d4est_hip_plan_t* plan, double* scalars_dev, int n) {
   if (!comm || !plan) D4EST_HIP_ABORT("comm_allreduce_sum: NULL argument");

@@ -486,9 +486,11 @@ void krylov_destroy(d4est_hip_plan* plan);
 
 // d4est_hip_schwarz.hip: the smoother loop behind the V-cycle object's Smoother interface and the Schwarz preconditioner's loop (the
 // handle's layout is private to that file).  check: 0 ok, 1 NULL, 2 the handle's mesh node count is not the plan's, 3 the subdomain plan
-// is not on the plan's stream, 4 the plan has ghost sides (or no faces).  Neither loop synchronises at the end of an iterate.
+// is not on the plan's stream, 4 the plan has ghost sides (or no faces).  A handle with an element exchange (a sharded handle): 2 compares
+// with its own node count and 4 only means "no faces".  Neither loop synchronises at the end of an iterate.
 int schwarz_smoother_check(const d4est_hip_schwarz* sz, const d4est_hip_plan* mesh_plan);
 bool schwarz_fused_residual(const d4est_hip_schwarz* sz);
+d4est_hip_plan* schwarz_subdomain_plan(const d4est_hip_schwarz* sz);   // (d4est_hip_comm.hip orders its rounds on that plan's stream)
 void schwarz_smoother_run(d4est_hip_schwarz* sz, d4est_hip_plan* mesh_plan, double* u, const double* rhs, double* r,
                           int smoother_iterations, int subdomain_iter, double subdomain_atol, double subdomain_rtol);
 void schwarz_pc_run(d4est_hip_schwarz* sz, d4est_hip_plan* mesh_plan, const double* rhs, double* z, double* Au, double* residual,

@@ -353,7 +353,7 @@ int d4est_hip_multigrid_set_smoother_schwarz(d4est_hip_multigrid_t* mg, d4est_hi
     if (!schwarz_on_level[l]) return 1;                 // (level 0 may be NULL: only the reuse_smoother bottom solver smooths there)
   for (int l = 0; l < mg->n_levels; ++l) {
     if (!schwarz_on_level[l]) continue;
-    // 2: node counts, 3: streams, 4: ghost sides -- schwarz_iterate is a one-rank entry, the whole-element exchanges are the host's
+    // 2: node counts, 3: streams, 4: ghost sides under a handle without an element exchange (or no faces)
     const int code = d4est_hip::schwarz_smoother_check(schwarz_on_level[l], mg->plans[l]);
     if (code != 0) return code;
   }

@@ -76,6 +76,24 @@ struct d4est_hip_schwarz {
   // inside the CG start instead of writing it to a mesh vector first -- same numbers.  Off by default: on the level-4, p = 7 cycle
   // it measured no faster than the two-kernel sequence; D4EST_HIP_SCHWARZ_UNFUSED_RESIDUAL=1 forces it off.
   bool fused_residual = false;
+  long long host_reads = 0;          // blocking reads of the device counters made so far (the "still iterating" looks and the public entry's sweep count)
+  // ---- whole-element exchange of a SHARDED handle (d4est_hip_schwarz_set_element_exchange); ex_fn == nullptr: one rank, nothing below is used.
+  // The mesh handed to create() is the rank's extended mesh; u / r of iterate, smooth and the pc are vectors of the own nodes, the prefix.
+  d4est_hip_element_exchange_fn ex_fn = nullptr;
+  void* ex_ctx = nullptr;
+  int n_own = 0, n_peers = 0;
+  long long own_nodes = 0;
+  std::vector<int> ex_peer;
+  std::vector<long long> own_first, ghost_first;   // per peer (+ total): first double of its segment among the own-element / ghost-layer blocks
+  double *d_r_ext = nullptr, *d_u_ext = nullptr;   // residual and correction on the extended mesh
+  // packed buffers: direction 0 sends `own` and receives `ghost`, direction 1 sends `ghost_back` and receives `own_back`
+  double *d_own_pack = nullptr, *d_ghost_pack = nullptr, *d_ghost_back = nullptr, *d_own_back = nullptr;
+  int* d_own_blk_first = nullptr;    // per own element (n_own + 1): its entries of d_own_blk_off, in ascending peer rank
+  int* d_own_blk_off = nullptr;      // offset of the element's block in the own-element packed layout of that peer
+  int n_ghost_blocks = 0;
+  int* d_ghost_blk_elem = nullptr;   // per ghost-layer block, peer after peer: its element ...
+  int* d_ghost_blk_off = nullptr;    // ... and the block's offset in the ghost-layer packed layout
+  std::vector<int> h_mesh_stride, h_mesh_N;
 };
 
 namespace d4est_hip {
@@ -305,6 +323,60 @@ __global__ __launch_bounds__(256) void schwarz_correction_kernel(const VirtDesc*
         }
       }
       u[mesh_stride[e] + n] = acc;
+    }
+  }
+}
+
+// ---- the device ends of the two whole-element exchanges of a sharded handle.  One workgroup per element block (grid-stride over the
+// blocks), plain 8-byte loads and stores: an element block starts at its nodal stride, which is 8-byte aligned and nothing more.
+
+// Step 1 of an iterate: the own part of the extended residual, and in the same pass the own elements' blocks into the forward send buffer
+// (an element that lies in the ghost layer of several peers is written once per peer).  FUSED: r is the right-hand side and Au is A u,
+// the residual is formed here with the one rounded operation of schwarz_cg_init_kernel<true>.
+template <bool FUSED>
+__global__ __launch_bounds__(256) void schwarz_assemble_pack_kernel(int n_own, const int* __restrict__ mesh_stride, const int* __restrict__ mesh_N,
+                                                                    const int* __restrict__ blk_first, const int* __restrict__ blk_off,
+                                                                    const double* __restrict__ r, const double* __restrict__ Au,
+                                                                    double* __restrict__ r_ext, double* __restrict__ send) {
+  for (int e = blockIdx.x; e < n_own; e += gridDim.x) {
+    const int N = mesh_N[e], n3 = N * N * N, base = mesh_stride[e], c0 = blk_first[e], c1 = blk_first[e + 1];
+    for (int n = threadIdx.x; n < n3; n += blockDim.x) {
+      const double val = FUSED ? __dadd_rn(r[base + n], __dmul_rn(-1.0, Au[base + n])) : r[base + n];
+      r_ext[base + n] = val;
+      for (int c = c0; c < c1; ++c) send[blk_off[c] + n] = val;
+    }
+  }
+}
+
+// Steps 3 and 5: ghost-layer blocks between a packed buffer and the extended vector.  UNPACK: ext <- packed (the received residuals);
+// else packed <- ext (the corrections computed for the ghost layer, on their way back).
+template <bool UNPACK>
+__global__ __launch_bounds__(256) void schwarz_ghost_blocks_kernel(int n_blocks, const int* __restrict__ blk_elem, const int* __restrict__ blk_off,
+                                                                   const int* __restrict__ mesh_stride, const int* __restrict__ mesh_N,
+                                                                   double* __restrict__ ext, double* __restrict__ packed) {
+  for (int b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+    const int e = blk_elem[b], N = mesh_N[e], n3 = N * N * N, base = mesh_stride[e], off = blk_off[b];
+    for (int n = threadIdx.x; n < n3; n += blockDim.x) {
+      if (UNPACK) ext[base + n] = packed[off + n];
+      else packed[off + n] = ext[base + n];
+    }
+  }
+}
+
+// Step 6: per own node, u (+)= the rank's own correction, then the blocks received for its element in ascending peer rank -- the order
+// of SchwarzShard.end_correction_exchange (transfer_ghost_data.c:97-120 adds them in the order of the ghost data), one rounded add
+// each, no atomics.  STORE: the sum starts from 0.0 instead of the value read (the preconditioner's zero start vector).
+template <bool STORE>
+__global__ __launch_bounds__(256) void schwarz_accumulate_kernel(int n_own, const int* __restrict__ mesh_stride, const int* __restrict__ mesh_N,
+                                                                 const int* __restrict__ blk_first, const int* __restrict__ blk_off,
+                                                                 const double* __restrict__ u_ext, const double* __restrict__ recv,
+                                                                 double* __restrict__ u) {
+  for (int e = blockIdx.x; e < n_own; e += gridDim.x) {
+    const int N = mesh_N[e], n3 = N * N * N, base = mesh_stride[e], c0 = blk_first[e], c1 = blk_first[e + 1];
+    for (int n = threadIdx.x; n < n3; n += blockDim.x) {
+      double acc = __dadd_rn(STORE ? 0.0 : u[base + n], u_ext[base + n]);
+      for (int c = c0; c < c1; ++c) acc = __dadd_rn(acc, recv[blk_off[c] + n]);
+      u[base + n] = acc;
     }
   }
 }
@@ -707,11 +779,27 @@ d4est_hip_schwarz_t* d4est_hip_schwarz_create(d4est_hip_plan_t* subdomain_plan, 
   sz->d_mesh_stride = upload(mstride);
   sz->d_mesh_N = upload(mN);
   sz->d_weights = upload(weights);
+  sz->h_mesh_stride = mstride;   // (set_element_exchange sizes the element blocks from these)
+  sz->h_mesh_N = mN;
   return sz;
+}
+
+static void release_element_exchange(d4est_hip_schwarz* sz) {
+  void* ptrs[] = {sz->d_r_ext, sz->d_u_ext, sz->d_own_pack, sz->d_ghost_pack, sz->d_ghost_back, sz->d_own_back,
+                  sz->d_own_blk_first, sz->d_own_blk_off, sz->d_ghost_blk_elem, sz->d_ghost_blk_off};
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+  sz->d_r_ext = sz->d_u_ext = sz->d_own_pack = sz->d_ghost_pack = sz->d_ghost_back = sz->d_own_back = nullptr;
+  sz->d_own_blk_first = sz->d_own_blk_off = sz->d_ghost_blk_elem = sz->d_ghost_blk_off = nullptr;
+  sz->ex_fn = nullptr; sz->ex_ctx = nullptr;
+  sz->n_own = sz->n_peers = sz->n_ghost_blocks = 0;
+  sz->own_nodes = 0;
+  sz->ex_peer.clear(); sz->own_first.clear(); sz->ghost_first.clear();
 }
 
 void d4est_hip_schwarz_destroy(d4est_hip_schwarz_t* sz) {
   if (!sz) return;
+  release_element_exchange(sz);
   void* ptrs[] = {sz->d_vd, sz->d_sub_first, sz->d_mesh_first, sz->d_mesh_contrib, sz->d_mesh_stride, sz->d_mesh_N, sz->d_weights,
                   sz->d_du, sz->d_r, sz->d_d, sz->d_Ad, sz->d_zero_ghost, sz->d_delta, sz->d_tol, sz->d_active, sz->d_final_iter,
                   sz->d_n_active, sz->d_cond, sz->d_cond_blocks, sz->d_keep_list, sz->d_cond_off, sz->d_box_off, sz->d_box_first};
@@ -801,6 +889,7 @@ static int iterate_body(d4est_hip_schwarz_t* sz, double* u_dev, const double* r_
       int n_active = 0;
       HIP_CHECK(hipMemcpyAsync(&n_active, sz->d_n_active, sizeof(int), hipMemcpyDeviceToHost, st));
       HIP_CHECK(hipStreamSynchronize(st));
+      sz->host_reads++;
       if (n_active == 0) break;  // every subdomain has left its loop
     }
     subdomain_operator(sz, sz->d_d, sz->d_Ad);   // (+ the zeroth-order term of a linearised problem: plan_set_lhs_coefficient on the subdomain plan)
@@ -821,7 +910,55 @@ static int iterate_body(d4est_hip_schwarz_t* sz, double* u_dev, const double* r_
   int counters[2] = {0, 0};
   HIP_CHECK(hipMemcpyAsync(counters, sz->d_n_active, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
+  sz->host_reads++;
   return counters[1];
+}
+
+// The same on a sharded handle: u, r (and Au) are vectors of the own nodes; the six steps of include/d4est_hip.h.  The hooks are called
+// once per direction whatever the subdomain solves did (a rank without subdomains, an early break), so the ranks stay in step.
+static int iterate_sharded(d4est_hip_schwarz_t* sz, double* u_dev, const double* r_dev, const double* Au_dev, int subdomain_iter,
+                           double subdomain_atol, double subdomain_rtol, bool store, bool read_sweeps) {
+  hipStream_t st = sz->plan->stream;
+  const dim3 own_grid(std::max(std::min(sz->n_own, 65536), 1)), ghost_grid(std::max(std::min(sz->n_ghost_blocks, 65536), 1)), block(256);
+  if (sz->n_own > 0) {
+    if (Au_dev)
+      hipLaunchKernelGGL(schwarz_assemble_pack_kernel<true>, own_grid, block, 0, st, sz->n_own, sz->d_mesh_stride, sz->d_mesh_N,
+                         sz->d_own_blk_first, sz->d_own_blk_off, r_dev, Au_dev, sz->d_r_ext, sz->d_own_pack);
+    else
+      hipLaunchKernelGGL(schwarz_assemble_pack_kernel<false>, own_grid, block, 0, st, sz->n_own, sz->d_mesh_stride, sz->d_mesh_N,
+                         sz->d_own_blk_first, sz->d_own_blk_off, r_dev, (const double*)nullptr, sz->d_r_ext, sz->d_own_pack);
+    HIP_CHECK(hipGetLastError());
+  }
+  sz->ex_fn(sz->ex_ctx, 0, sz->d_own_pack, sz->d_ghost_pack);
+  if (sz->n_ghost_blocks > 0) {
+    hipLaunchKernelGGL(schwarz_ghost_blocks_kernel<true>, ghost_grid, block, 0, st, sz->n_ghost_blocks, sz->d_ghost_blk_elem, sz->d_ghost_blk_off,
+                       sz->d_mesh_stride, sz->d_mesh_N, sz->d_r_ext, sz->d_ghost_pack);
+    HIP_CHECK(hipGetLastError());
+  }
+  // the correction of the extended mesh, stored: u_ext needs no fill
+  const int sweeps = iterate_body(sz, sz->d_u_ext, sz->d_r_ext, nullptr, subdomain_iter, subdomain_atol, subdomain_rtol, true, read_sweeps);
+  if (sz->n_ghost_blocks > 0) {
+    hipLaunchKernelGGL(schwarz_ghost_blocks_kernel<false>, ghost_grid, block, 0, st, sz->n_ghost_blocks, sz->d_ghost_blk_elem, sz->d_ghost_blk_off,
+                       sz->d_mesh_stride, sz->d_mesh_N, sz->d_u_ext, sz->d_ghost_back);
+    HIP_CHECK(hipGetLastError());
+  }
+  sz->ex_fn(sz->ex_ctx, 1, sz->d_ghost_back, sz->d_own_back);
+  if (sz->n_own > 0) {
+    if (store)
+      hipLaunchKernelGGL(schwarz_accumulate_kernel<true>, own_grid, block, 0, st, sz->n_own, sz->d_mesh_stride, sz->d_mesh_N, sz->d_own_blk_first,
+                         sz->d_own_blk_off, sz->d_u_ext, sz->d_own_back, u_dev);
+    else
+      hipLaunchKernelGGL(schwarz_accumulate_kernel<false>, own_grid, block, 0, st, sz->n_own, sz->d_mesh_stride, sz->d_mesh_N, sz->d_own_blk_first,
+                         sz->d_own_blk_off, sz->d_u_ext, sz->d_own_back, u_dev);
+    HIP_CHECK(hipGetLastError());
+  }
+  return sweeps;
+}
+
+static int iterate_any(d4est_hip_schwarz_t* sz, double* u_dev, const double* r_dev, const double* Au_dev, int subdomain_iter,
+                       double subdomain_atol, double subdomain_rtol, bool store, bool read_sweeps) {
+  if (sz->ex_fn) return iterate_sharded(sz, u_dev, r_dev, Au_dev, subdomain_iter, subdomain_atol, subdomain_rtol, store, read_sweeps);
+  return iterate_body(sz, u_dev, r_dev, Au_dev, subdomain_iter, subdomain_atol, subdomain_rtol, store, read_sweeps);
 }
 
 int d4est_hip_schwarz_iterate(d4est_hip_schwarz_t* sz, double* u_dev, const double* r_dev, int subdomain_iter, double subdomain_atol,
@@ -829,14 +966,113 @@ int d4est_hip_schwarz_iterate(d4est_hip_schwarz_t* sz, double* u_dev, const doub
   check_schwarz(sz, "schwarz_iterate");
   // d4est_solver_schwarz_subdomain_solver_cg.c:86-92
   if (subdomain_iter <= 0 || !(subdomain_rtol > 0) || !(subdomain_atol > 0)) D4EST_HIP_ABORT("schwarz_iterate: some subdomain solver options are <= 0");
-  return iterate_body(sz, u_dev, r_dev, nullptr, subdomain_iter, subdomain_atol, subdomain_rtol, false, true);
+  return iterate_any(sz, u_dev, r_dev, nullptr, subdomain_iter, subdomain_atol, subdomain_rtol, false, true);
 }
+
+void d4est_hip_schwarz_set_element_exchange(d4est_hip_schwarz_t* sz, int n_own_elements, int n_peers, const int* peer_rank,
+                                            const int* send_first, const int* send_elem, const int* recv_first, const int* recv_elem,
+                                            d4est_hip_element_exchange_fn fn, void* ctx) {
+  check_schwarz(sz, "schwarz_set_element_exchange");
+  release_element_exchange(sz);
+  if (!fn) return;
+  const int ne = sz->n_mesh;
+  if (n_own_elements < 0 || n_own_elements > ne) D4EST_HIP_ABORT("schwarz_set_element_exchange: %d own elements of %d", n_own_elements, ne);
+  if (n_peers < 0 || (n_peers > 0 && (!peer_rank || !send_first || !recv_first))) D4EST_HIP_ABORT("schwarz_set_element_exchange: bad peer lists");
+  if (n_peers > 0 && ((send_first[n_peers] > 0 && !send_elem) || (recv_first[n_peers] > 0 && !recv_elem)))
+    D4EST_HIP_ABORT("schwarz_set_element_exchange: element lists are NULL");
+  if (n_peers > 0 && (send_first[0] != 0 || recv_first[0] != 0)) D4EST_HIP_ABORT("schwarz_set_element_exchange: send_first / recv_first must start at 0");
+  auto n3 = [&](int e) { return (long long)sz->h_mesh_N[e] * sz->h_mesh_N[e] * sz->h_mesh_N[e]; };
+  // own nodes are the prefix of the extended vector: the own elements' blocks fill [0, own_nodes), the ghost layer's lie behind
+  long long own_nodes = 0;
+  for (int e = 0; e < n_own_elements; ++e) own_nodes += n3(e);
+  for (int e = 0; e < ne; ++e) {
+    const long long lo = sz->h_mesh_stride[e], hi = lo + n3(e);
+    if (e < n_own_elements ? (lo < 0 || hi > own_nodes) : (lo < own_nodes || hi > sz->mesh_nodes))
+      D4EST_HIP_ABORT("schwarz_set_element_exchange: element %d does not lie on its side of the own nodes [0, %lld)", e, own_nodes);
+  }
+  std::vector<std::vector<int>> own_blocks(n_own_elements);   // per own element: packed offsets, peer after peer
+  std::vector<int> ghost_elem, ghost_off, ghost_owner(ne, -1);
+  std::vector<long long> own_first(1, 0), ghost_first(1, 0);
+  for (int p = 0; p < n_peers; ++p) {
+    if (peer_rank[p] < 0 || (p > 0 && peer_rank[p] <= peer_rank[p - 1])) D4EST_HIP_ABORT("schwarz_set_element_exchange: peers must be ascending (entry %d)", p);
+    if (send_first[p + 1] < send_first[p] || recv_first[p + 1] < recv_first[p]) D4EST_HIP_ABORT("schwarz_set_element_exchange: decreasing first[] at peer entry %d", p);
+    long long at = own_first.back();
+    for (int k = send_first[p]; k < send_first[p + 1]; ++k) {
+      const int e = send_elem[k];
+      if (e < 0 || e >= n_own_elements) D4EST_HIP_ABORT("schwarz_set_element_exchange: send element %d is not an own element (%d own)", e, n_own_elements);
+      if (!own_blocks[e].empty() && own_blocks[e].back() >= own_first.back()) D4EST_HIP_ABORT("schwarz_set_element_exchange: own element %d listed twice for rank %d", e, peer_rank[p]);
+      own_blocks[e].push_back((int)at);
+      at += n3(e);
+    }
+    own_first.push_back(at);
+    at = ghost_first.back();
+    for (int k = recv_first[p]; k < recv_first[p + 1]; ++k) {
+      const int e = recv_elem[k];
+      if (e < n_own_elements || e >= ne) D4EST_HIP_ABORT("schwarz_set_element_exchange: receive element %d is not in the ghost layer [%d, %d)", e, n_own_elements, ne);
+      if (ghost_owner[e] >= 0) D4EST_HIP_ABORT("schwarz_set_element_exchange: ghost-layer element %d is owned by ranks %d and %d", e, ghost_owner[e], peer_rank[p]);
+      ghost_owner[e] = peer_rank[p];
+      ghost_elem.push_back(e);
+      ghost_off.push_back((int)at);
+      at += n3(e);
+    }
+    ghost_first.push_back(at);
+    if (own_first.back() > 0x7fffffffLL || ghost_first.back() > 0x7fffffffLL) D4EST_HIP_ABORT("schwarz_set_element_exchange: packed buffers exceed 32-bit offsets");
+  }
+  for (int e = n_own_elements; e < ne; ++e)
+    if (ghost_owner[e] < 0) D4EST_HIP_ABORT("schwarz_set_element_exchange: no peer owns ghost-layer element %d", e);
+  std::vector<int> blk_first(n_own_elements + 1, 0), blk_off;
+  for (int e = 0; e < n_own_elements; ++e) {
+    blk_off.insert(blk_off.end(), own_blocks[e].begin(), own_blocks[e].end());
+    blk_first[e + 1] = (int)blk_off.size();
+  }
+  sz->n_own = n_own_elements;
+  sz->own_nodes = own_nodes;
+  sz->n_peers = n_peers;
+  sz->ex_peer.assign(peer_rank, peer_rank + n_peers);
+  sz->own_first = own_first;
+  sz->ghost_first = ghost_first;
+  sz->n_ghost_blocks = (int)ghost_elem.size();
+  sz->d_own_blk_first = upload(blk_first);
+  sz->d_own_blk_off = upload(blk_off);
+  sz->d_ghost_blk_elem = upload(ghost_elem);
+  sz->d_ghost_blk_off = upload(ghost_off);
+  auto alloc = [](long long n) {
+    double* d = nullptr;
+    HIP_CHECK(hipMalloc(&d, std::max<size_t>((size_t)n, 1) * sizeof(double)));
+    return d;
+  };
+  sz->d_r_ext = alloc(sz->mesh_nodes);
+  sz->d_u_ext = alloc(sz->mesh_nodes);
+  sz->d_own_pack = alloc(own_first.back());
+  sz->d_own_back = alloc(own_first.back());
+  sz->d_ghost_pack = alloc(ghost_first.back());
+  sz->d_ghost_back = alloc(ghost_first.back());
+  sz->ex_fn = fn;
+  sz->ex_ctx = ctx;
+}
+
+long long d4est_hip_schwarz_own_nodes(const d4est_hip_schwarz_t* sz) {
+  check_schwarz(sz, "schwarz_own_nodes");
+  return sz->ex_fn ? sz->own_nodes : sz->mesh_nodes;
+}
+
+long long d4est_hip_schwarz_exchange_first(const d4est_hip_schwarz_t* sz, int direction, int send_or_recv, int peer) {
+  check_schwarz(sz, "schwarz_exchange_first");
+  if (!sz->ex_fn) D4EST_HIP_ABORT("schwarz_exchange_first: no element exchange is set");
+  if ((direction != 0 && direction != 1) || (send_or_recv != 0 && send_or_recv != 1) || peer < 0 || peer > sz->n_peers)
+    D4EST_HIP_ABORT("schwarz_exchange_first: direction %d, send_or_recv %d, peer entry %d of %d", direction, send_or_recv, peer, sz->n_peers);
+  // direction 0 sends the own elements' blocks and receives the ghost layer's; direction 1 the other way round
+  return (direction == send_or_recv ? sz->own_first : sz->ghost_first)[peer];
+}
+
+long long d4est_hip_schwarz_host_reads(const d4est_hip_schwarz_t* sz) { check_schwarz(sz, "schwarz_host_reads"); return sz->host_reads; }
 
 void d4est_hip_schwarz_smooth(d4est_hip_schwarz_t* sz, d4est_hip_plan_t* mesh_plan, double* u_dev, const double* rhs_dev, double* r_dev,
                               int smoother_iterations, int subdomain_iter, double subdomain_atol, double subdomain_rtol) {
   check_schwarz(sz, "schwarz_smooth");
   if (!mesh_plan || !mesh_plan->has_faces) D4EST_HIP_ABORT("schwarz_smooth: the mesh plan needs its faces (plan_set_faces)");
-  if (mesh_plan->local_nodes != sz->mesh_nodes) D4EST_HIP_ABORT("schwarz_smooth: mesh plan has %d nodes, the smoother's mesh %d", mesh_plan->local_nodes, sz->mesh_nodes);
+  const long long handle_nodes = sz->ex_fn ? sz->own_nodes : (long long)sz->mesh_nodes;
+  if (mesh_plan->local_nodes != handle_nodes) D4EST_HIP_ABORT("schwarz_smooth: mesh plan has %d nodes, the smoother's mesh %lld", mesh_plan->local_nodes, handle_nodes);
   if (mesh_plan->stream != sz->plan->stream) D4EST_HIP_ABORT("schwarz_smooth: the mesh plan and the subdomain plan must use the same stream");
   // d4est_solver_multigrid_smoother_schwarz, src/Solver/d4est_solver_multigrid_smoother_schwarz.c:98-196; r doubles as the Au scratch
   for (int i = 0; i < smoother_iterations; ++i) {
@@ -871,13 +1107,20 @@ namespace d4est_hip {
 
 int schwarz_smoother_check(const d4est_hip_schwarz* sz, const d4est_hip_plan* mesh_plan) {
   if (!sz || !sz->plan || !mesh_plan) return 1;
-  if (mesh_plan->n_ghost > 0 || !mesh_plan->has_faces) return 4;   // (first: no handle makes such a plan acceptable)
+  if (sz->ex_fn) {   // a sharded handle: the plan is the rank's own, ghost sides and all; its vectors are the own nodes
+    if (!mesh_plan->has_faces) return 4;
+    if (mesh_plan->local_nodes != sz->own_nodes) return 2;
+    if (mesh_plan->stream != sz->plan->stream) return 3;
+    return 0;
+  }
+  if (mesh_plan->n_ghost > 0 || !mesh_plan->has_faces) return 4;   // (first: no handle without an exchange makes such a plan acceptable)
   if (mesh_plan->local_nodes != sz->mesh_nodes) return 2;
   if (mesh_plan->stream != sz->plan->stream) return 3;
   return 0;
 }
 
 bool schwarz_fused_residual(const d4est_hip_schwarz* sz) { return sz->fused_residual; }
+d4est_hip_plan* schwarz_subdomain_plan(const d4est_hip_schwarz* sz) { return sz ? sz->plan : nullptr; }
 
 // d4est_solver_multigrid_smoother_schwarz (src/Solver/d4est_solver_multigrid_smoother_schwarz.c:89-204).  As in the reference
 // (vecs->Au = r, :112-113, :154-155) r is the operator's output vector, so the cycle's own Au is not touched.
@@ -890,10 +1133,10 @@ void schwarz_smoother_run(d4est_hip_schwarz* sz, d4est_hip_plan* mesh_plan, doub
     apply_operator(mesh_plan, u, r);                                                // :112-126 (Au = r)
     if (sz->fused_residual) {
       // :128 (r = rhs - r) node by node inside the CG start, :136-146
-      iterate_body(sz, u, rhs, r, subdomain_iter, subdomain_atol, subdomain_rtol, false, false);
+      iterate_any(sz, u, rhs, r, subdomain_iter, subdomain_atol, subdomain_rtol, false, false);
     } else {
       launch_residual_inplace(mesh_plan, n, rhs, r);                                // :128
-      iterate_body(sz, u, r, nullptr, subdomain_iter, subdomain_atol, subdomain_rtol, false, false);   // :136-146
+      iterate_any(sz, u, r, nullptr, subdomain_iter, subdomain_atol, subdomain_rtol, false, false);   // :136-146
     }
   }
   apply_operator(mesh_plan, u, r);                                                  // :154-168
@@ -914,15 +1157,15 @@ void schwarz_pc_run(d4est_hip_schwarz* sz, d4est_hip_plan* mesh_plan, const doub
   if (!zero_start || iterations <= 0) HIP_CHECK(hipMemsetAsync(z, 0, std::max<size_t>((size_t)n, 1) * sizeof(double), mesh_plan->stream));   // :69
   for (int i = 0; i < iterations; ++i) {                                            // :81
     if (i == 0 && zero_start) {
-      iterate_body(sz, z, rhs, nullptr, subdomain_iter, subdomain_atol, subdomain_rtol, true, false);
+      iterate_any(sz, z, rhs, nullptr, subdomain_iter, subdomain_atol, subdomain_rtol, true, false);
       continue;
     }
     apply_operator(mesh_plan, z, Au);                                               // :83-94
     if (sz->fused_residual) {
-      iterate_body(sz, z, rhs, Au, subdomain_iter, subdomain_atol, subdomain_rtol, false, false);       // :97, :99-110
+      iterate_any(sz, z, rhs, Au, subdomain_iter, subdomain_atol, subdomain_rtol, false, false);       // :97, :99-110
     } else {
       launch_residual(mesh_plan, n, rhs, Au, residual);                             // :97
-      iterate_body(sz, z, residual, nullptr, subdomain_iter, subdomain_atol, subdomain_rtol, false, false);   // :99-110
+      iterate_any(sz, z, residual, nullptr, subdomain_iter, subdomain_atol, subdomain_rtol, false, false);   // :99-110
     }
   }
 }

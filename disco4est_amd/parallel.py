@@ -198,6 +198,10 @@ class DistTransport:
         for r in reqs or []:
             r.wait()
 
+    def round(self, send_buf, recv_buf):
+        """one complete exchange: post, wait, fill (the Schwarz smoother's whole-element exchanges, attach_schwarz)"""
+        self.finish(self.start(send_buf, recv_buf))
+
     def allreduce_sum(self, t):
         self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group)
 
@@ -378,4 +382,89 @@ def attach_rccl(plan, mesh, sides, parts, comm):
     x.send_doubles = plan.lib.d4est_hip_rccl_exchange_send_doubles(h)
     x.recv_doubles = plan.lib.d4est_hip_rccl_exchange_recv_doubles(h)
     x.destroy = lambda: plan.lib.d4est_hip_rccl_exchange_destroy(h)
+    return x
+
+
+# ---- the Schwarz smoother's whole-element exchanges inside the library (d4est_hip_schwarz_set_element_exchange) --------------------------
+def element_exchange_lists(sched, nodal_stride):
+    """(peer_rank, send_first, send_elem, recv_first, recv_elem) of an ElementSchedule as d4est_hip_schwarz_set_element_exchange takes
+    them: the schedule's blocks start at element strides of the extended mesh, so a block's offset names its element"""
+    stride = np.asarray(nodal_stride, dtype=np.int64)
+    peers = np.asarray(sched.peers, dtype=np.int32)
+    sf, rf, se, re_ = [0], [0], [], []
+    for p in sched.peers:
+        for blocks, first, elem in ((sched.send[p], sf, se), (sched.recv[p], rf, re_)):
+            e = np.searchsorted(stride, blocks[:, 0])
+            assert np.array_equal(stride[e], blocks[:, 0]), "a block of the schedule does not start at an element"
+            elem.append(e)
+            first.append(first[-1] + len(e))
+    cat = lambda a: np.ascontiguousarray(np.concatenate(a) if a else np.zeros(0), dtype=np.int32)
+    return peers, np.asarray(sf, dtype=np.int32), cat(se), np.asarray(rf, dtype=np.int32), cat(re_)
+
+
+def exchange_round(transport, send_buf, recv_buf):
+    """one complete round of a transport: post, wait, fill (``transport.round`` where it has one, else start + finish)"""
+    if hasattr(transport, "round"):
+        transport.round(send_buf, recv_buf)
+    else:
+        transport.finish(transport.start(send_buf, recv_buf))
+
+
+def attach_schwarz(shard, transport, device):
+    """Wire a schwarz.SchwarzShardNative to a transport (DistTransport or an in-process one): installs the element-exchange hook.  Per
+    direction the hook hands the transport views of the handle's packed buffers, one per peer, and makes one complete round."""
+    import contextlib
+    import torch
+    sz = shard.schwarz
+
+    def view(ptr, n):
+        class _Holder:
+            pass
+        h = _Holder()
+        h.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (int(ptr), False), "version": 2}
+        return torch.as_tensor(h, device=device)
+
+    firsts = {}
+
+    def hook(direction, send_ptr, recv_ptr):
+        ts = getattr(sz.plan, "torch_stream", None)          # the collectives order themselves behind torch's CURRENT stream
+        with (torch.cuda.stream(ts) if ts is not None else contextlib.nullcontext()):
+            sf, rf = firsts[direction]
+            send = view(send_ptr, sf[-1]) if sf[-1] else torch.empty(0, dtype=torch.float64, device=device)
+            recv = view(recv_ptr, rf[-1]) if rf[-1] else torch.empty(0, dtype=torch.float64, device=device)
+            peers = sz.exchange_peers
+            exchange_round(transport, {p: send[sf[i]:sf[i + 1]] for i, p in enumerate(peers)},
+                           {p: recv[rf[i]:rf[i + 1]] for i, p in enumerate(peers)})
+
+    sz.set_element_exchange(shard.n_own, shard.schedule, hook)
+    for d in (0, 1):
+        firsts[d] = (sz.exchange_first(d, 0), sz.exchange_first(d, 1))
+    shard.exchange = hook
+    return hook
+
+
+def attach_schwarz_rccl(shard, comm):
+    """Wire a schwarz.SchwarzShardNative to the RCCL transport in C: d4est_hip_schwarz_set_rccl_exchange (no Python per iterate)."""
+    import ctypes
+    sz = shard.schwarz
+    lists = element_exchange_lists(shard.schedule, shard.mesh.nodal_stride)
+    peers, sf, se, rf, re_ = lists
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    h = sz.lib.d4est_hip_schwarz_set_rccl_exchange(sz.handle, comm.handle, shard.n_own, len(peers), vp(peers), vp(sf), vp(se), vp(rf), vp(re_))
+    sz.exchange_peers = [int(p) for p in peers]
+    sz.local_nodes = int(sz.lib.d4est_hip_schwarz_own_nodes(sz.handle))
+
+    class _Exchange:
+        pass
+    x = _Exchange()
+    x.handle, x.lists, x.lib = h, lists, sz.lib
+    x.count = lambda: sz.lib.d4est_hip_schwarz_rccl_exchange_count(h)
+
+    def destroy():
+        if x.handle:
+            sz.lib.d4est_hip_schwarz_rccl_exchange_destroy(x.handle)
+            x.handle = None
+            sz.local_nodes = int(sz.lib.d4est_hip_schwarz_own_nodes(sz.handle))
+    x.destroy = destroy
+    shard.exchange = x
     return x

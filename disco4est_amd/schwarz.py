@@ -325,7 +325,10 @@ class Schwarz:
         self.nodal_size = self.lib.d4est_hip_schwarz_nodal_size(self.handle)
         self.restricted_nodal_size = self.lib.d4est_hip_schwarz_restricted_nodal_size(self.handle)
         assert self.nodal_size == md.nodal_size and self.restricted_nodal_size == md.restricted_nodal_size
-        self.local_nodes = mesh.local_nodes
+        self.local_nodes = mesh.local_nodes                  # what iterate / smooth take: the own nodes once an element exchange is set
+        self.mesh_nodes = mesh.local_nodes                   # the (extended) mesh the handle was built on
+        self._mesh_stride = np.asarray(mesh.nodal_stride, dtype=np.int64)
+        self._cb_elem, self.exchange_peers = None, []
 
     def set_lhs_element_blocks(self, blocks, mesh):
         """the zeroth-order term of a coarse multigrid level (dense element blocks, consecutive in the MESH's element order) as part of
@@ -339,7 +342,7 @@ class Schwarz:
         return int(self.lib.d4est_hip_schwarz_condensed_copies(self.handle))
 
     def restrict_field(self, field, out):
-        assert field.numel() == self.local_nodes and out.numel() == self.nodal_size
+        assert field.numel() == self.mesh_nodes and out.numel() == self.nodal_size
         self.lib.d4est_hip_schwarz_restrict_field(self.handle, capi._ptr(field), capi._ptr(out))
 
     def apply_over_subdomains(self, x, out):
@@ -347,7 +350,7 @@ class Schwarz:
         self.lib.d4est_hip_schwarz_apply_over_subdomains(self.handle, capi._ptr(x), capi._ptr(out))
 
     def add_correction(self, du, u):
-        assert du.numel() == self.nodal_size and u.numel() == self.local_nodes
+        assert du.numel() == self.nodal_size and u.numel() == self.mesh_nodes
         self.lib.d4est_hip_schwarz_add_correction(self.handle, capi._ptr(du), capi._ptr(u))
 
     def iterate(self, u, r):
@@ -362,6 +365,48 @@ class Schwarz:
             assert t.numel() == self.local_nodes
         self.lib.d4est_hip_schwarz_smooth(self.handle, mesh_plan.handle, capi._ptr(u), capi._ptr(rhs), capi._ptr(r), int(smoother_iterations),
                                           self.subdomain_iter, self.subdomain_atol, self.subdomain_rtol)
+
+    ELEMENT_EXCHANGE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
+
+    def set_element_exchange(self, n_own, schedule, hook):
+        """Make this handle (built on a rank's extended mesh: ``n_own`` own elements, then the ghost layer) a SHARDED one:
+        d4est_hip_schwarz_set_element_exchange with the lists of ``schedule`` (parallel.ElementSchedule, or the flat tuple of
+        ``element_exchange_lists``).  hook(direction, send_ptr, recv_ptr) is a python callable (pointers are ints) that moves the packed
+        buffers, 0: residuals owners -> ghost copies, 1: corrections ghost copies -> owners; None removes the exchange.  From then on
+        iterate / smooth take vectors of the own nodes.  An exception inside the hook aborts the process, as in Plan.set_comm."""
+        if hook is None:
+            self.lib.d4est_hip_schwarz_set_element_exchange(self.handle, 0, 0, None, None, None, None, None, None, None)
+            self._cb_elem, self.local_nodes = None, int(self.lib.d4est_hip_schwarz_own_nodes(self.handle))
+            return
+        from .parallel import element_exchange_lists
+        lists = schedule if isinstance(schedule, tuple) else element_exchange_lists(schedule, self._mesh_stride)
+
+        def call(ctx, direction, send_ptr, recv_ptr):
+            try:
+                hook(direction, send_ptr, recv_ptr)
+            except BaseException:   # (ctypes would print and drop it: the C caller would go on with a stale buffer)
+                import os
+                import sys
+                import traceback
+                sys.stderr.write("[D4EST_HIP_ABORT] exception in the Schwarz element exchange callback:\n")
+                traceback.print_exc()
+                sys.stderr.flush()
+                os.abort()
+
+        self._cb_elem = self.ELEMENT_EXCHANGE_FN(call)
+        peers, sf, se, rf, re_ = [capi._iarr(a) for a in lists]
+        self.lib.d4est_hip_schwarz_set_element_exchange(self.handle, int(n_own), len(peers[0]), peers[1], sf[1], se[1], rf[1], re_[1],
+                                                        ctypes.cast(self._cb_elem, ctypes.c_void_p), None)
+        self.exchange_peers = [int(p) for p in peers[0]]
+        self.local_nodes = int(self.lib.d4est_hip_schwarz_own_nodes(self.handle))
+
+    def exchange_first(self, direction, send_or_recv):
+        """segment starts (doubles, one per peer + the total) of the packed send (0) / receive (1) buffer of a direction"""
+        return [int(self.lib.d4est_hip_schwarz_exchange_first(self.handle, direction, send_or_recv, p)) for p in range(len(self.exchange_peers) + 1)]
+
+    def host_reads(self):
+        """blocking reads of device counters made so far (d4est_hip_schwarz_host_reads)"""
+        return int(self.lib.d4est_hip_schwarz_host_reads(self.handle))
 
     def info(self):
         it = np.zeros(self.metadata.num_subdomains, dtype=np.int32)
@@ -505,3 +550,45 @@ class SchwarzShard:
         sweeps = self.solve_and_begin_correction_exchange()
         self.end_correction_exchange(u_own)
         return sweeps
+
+
+class SchwarzShardNative:
+    """SchwarzShard with both whole-element exchanges inside the library (d4est_hip_schwarz_set_element_exchange): the same extended
+    mesh, handle and ElementSchedule, but ``iterate(u_own, r_own)`` is ONE library call -- assemble / pack kernel, hook, unpack kernel,
+    the subdomain solves, pack kernel, hook, one accumulate kernel that adds the own correction and then the peers' in ascending rank
+    (SchwarzShard's order: the two give the same bits).  The handle (``.schwarz``) also serves d4est_hip_schwarz_smooth, the V-cycle
+    object and PcSchwarz with the rank's own plan.  Wire a transport with parallel.attach_schwarz / attach_schwarz_rccl before use."""
+
+    def __init__(self, level, deg_global, parts, rank, mapping, num_nodes_overlap, subdomain_iter, subdomain_atol, subdomain_rtol,
+                 penalty_prefactor=10.0, penalty_fcn=0, deg_quad_inc=0, quad_type=0, refine=None, stream=None):
+        from .mesh import BrickMesh, HangingBrickMesh
+        from .parallel import ElementSchedule
+        if refine is not None:
+            own, ghosts, needed_by = ghost_layer_hanging(level, refine, parts, rank)
+            self.mesh = m = HangingBrickMesh(level, refine, deg_global, deg_quad_inc=deg_quad_inc, quad_type=quad_type,
+                                             elements=np.concatenate([own, ghosts]))
+        else:
+            own, ghosts, needed_by = ghost_layer(level, parts, rank)
+            self.mesh = m = BrickMesh(level, deg_global, deg_quad_inc=deg_quad_inc, quad_type=quad_type, elements=np.concatenate([own, ghosts]))
+        self.n_own = int(own.size)
+        self.rank = int(rank)
+        J, rst = m.geometry(mapping)
+        sides = m.build_sides(mapping)
+        self.schwarz = Schwarz(m, sides, J, rst, num_nodes_overlap, subdomain_iter, subdomain_atol, subdomain_rtol, penalty_prefactor,
+                               penalty_fcn, stream=stream, cores=np.arange(self.n_own), sort_key=m.elements)
+        self.own_nodes = int(((m.deg[:self.n_own].astype(np.int64) + 1) ** 3).sum())
+        self.schedule = ElementSchedule(m, self.n_own, parts, needed_by)
+        self.exchange = None                                  # what attach_schwarz / attach_schwarz_rccl returned (kept alive)
+
+    def iterate(self, u_own, r_own):
+        """one d4est_solver_schwarz_iterate on this rank (collective: every rank calls it); returns this rank's CG sweeps"""
+        if self.exchange is None:
+            raise RuntimeError("SchwarzShardNative: no transport attached (parallel.attach_schwarz)")
+        assert u_own.numel() == self.own_nodes and r_own.numel() == self.own_nodes
+        return self.schwarz.iterate(u_own, r_own)
+
+    def destroy(self):
+        if self.exchange is not None and hasattr(self.exchange, "destroy"):
+            self.exchange.destroy()
+        self.exchange = None
+        self.schwarz.destroy()

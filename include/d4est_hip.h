@@ -839,8 +839,8 @@ void d4est_hip_transfer_galerkin_blocks(d4est_hip_transfer_t* t, const double* f
  * those of its two plans.
  * The smoother is the Chebyshev driver or the Schwarz smoother (d4est_solver_multigrid_smoother_schwarz.c:89-204, the caller's Schwarz
  * handle per level); the bottom solver is CG, Chebyshev or reuse_smoother (d4est_solver_multigrid_bottom_solver_reuse_smoother.c:20-39).
- * Not part of the object: the Schwarz smoother on plans with ghost sides (the whole-element exchanges around an iterate are the
- * host's), the PETSc bottom solver, the reference-named compat entry points, hierarchies coarsened across ranks (every level's hooks
+ * On plans with ghost sides the Schwarz handles must carry an element exchange (d4est_hip_schwarz_set_element_exchange).
+ * Not part of the object: the PETSc bottom solver, the reference-named compat entry points, hierarchies coarsened across ranks (every level's hooks
  * are simply used).  The object never changes a plan's tuning: a caller may set D4EST_HIP_TUNE_GRAPH (key 9) on launch-bound coarse
  * plans itself. */
 typedef struct d4est_hip_multigrid d4est_hip_multigrid_t;
@@ -871,8 +871,8 @@ int d4est_hip_multigrid_set_smoother_cheby(d4est_hip_multigrid_t* mg, int cheby_
  * faster; D4EST_HIP_SCHWARZ_UNFUSED_RESIDUAL=1 forces the two kernels).
  * d4est_hip_schwarz_get_info works after a cycle.  The smoother has no eigenvalue state: d4est_hip_multigrid_get_info reports -1.
  * Returns 0, or -- leaving the object without a smoother -- 1 for a NULL entry on a level >= 1, 2 for a handle whose mesh node count is
- * not plans[l]'s, 3 for a handle whose subdomain plan is not on the hierarchy's stream, 4 for a plan with ghost sides (or without
- * faces), 5 for subdomain options <= 0 (d4est_solver_schwarz_subdomain_solver_cg.c:86-92) or a negative smoother_iterations. */
+ * not plans[l]'s (a sharded handle: its own node count), 3 for a handle whose subdomain plan is not on the hierarchy's stream, 4 for a
+ * plan with ghost sides and a handle without an element exchange (or a plan without faces), 5 for subdomain options <= 0 (d4est_solver_schwarz_subdomain_solver_cg.c:86-92) or a negative smoother_iterations. */
 int d4est_hip_multigrid_set_smoother_schwarz(d4est_hip_multigrid_t* mg, d4est_hip_schwarz_t* const* schwarz_on_level, int smoother_iterations,
                                              int subdomain_iter, double subdomain_atol, double subdomain_rtol);
 /* One call of the current smoother on one level, as the V-cycle makes it: smooth A_level u = rhs, r = rhs - A u of the final iterate on
@@ -934,8 +934,10 @@ void d4est_hip_multigrid_get_info(const d4est_hip_multigrid_t* mg, double* eigs_
  * Dirichlet data).  disco4est_amd/schwarz.py builds it; the plan stays owned by the caller and must outlive the handle.
  * Hanging 1 <-> 4 faces: the copies carry the mesh's plan_set_hanging arrays, group / neighbour entries remapped the same way.
  * Several ranks: the mesh handed over is the rank's EXTENDED mesh (own elements followed by the ghost layer, P4EST_CONNECT_FULL), subdomains
- * exist for the own elements only; the residual of the ghost-layer elements arrives by a whole-element exchange before schwarz_iterate and
- * their part of u (the corrections) is sent back to the owners afterwards (disco4est_amd/schwarz.py: SchwarzShard, parallel.ElementSchedule). */
+ * exist for the own elements only; the residual of the ghost-layer elements arrives by a whole-element exchange before the subdomain solves
+ * and their part of u (the corrections) is sent back to the owners afterwards.  With d4est_hip_schwarz_set_element_exchange (below) the
+ * handle makes both exchanges itself and every entry that takes mesh vectors works on the rank's OWN nodes; without it the entries are
+ * extended-mesh entries and the exchanges are the host's (disco4est_amd/schwarz.py: SchwarzShard, parallel.ElementSchedule). */
 d4est_hip_schwarz_t* d4est_hip_schwarz_create(d4est_hip_plan_t* subdomain_plan, int n_subdomains, const int* sub_first,
                                               const int* sub_elem, const int* sub_faces, const int* sub_core_faces,
                                               int num_nodes_overlap, int n_mesh_elements, const int* mesh_deg,
@@ -959,17 +961,70 @@ void d4est_hip_schwarz_apply_over_subdomains(d4est_hip_schwarz_t* sz, const doub
  * u += sum over subdomains of weights * du, added in ascending subdomain order */
 void d4est_hip_schwarz_add_correction(d4est_hip_schwarz_t* sz, const double* du_over_subdomains_dev, double* u_dev);
 /* d4est_solver_schwarz_iterate: u += correction of the residual r = rhs - A u (both mesh vectors on the device); the three
- * [d4est_solver_schwarz] CG options as arguments.  Returns the number of batched CG sweeps (= the largest iteration count). */
+ * [d4est_solver_schwarz] CG options as arguments.  Returns the number of batched CG sweeps (= the largest iteration count) of this
+ * rank.  On a sharded handle (element exchange set) u and r are vectors of the rank's OWN nodes and the call is collective. */
 int d4est_hip_schwarz_iterate(d4est_hip_schwarz_t* sz, double* u_dev, const double* r_dev, int subdomain_iter, double subdomain_atol,
                               double subdomain_rtol);
 /* The multigrid smoother built on it, d4est_solver_multigrid_smoother_schwarz (src/Solver/d4est_solver_multigrid_smoother_schwarz.c:98-196):
  * smoother_iterations times { r = rhs - A u; schwarz_iterate(u, r) }, then r = rhs - A u.  mesh_plan is the plan of the mesh itself (faces
- * set, homogeneous Dirichlet data, same stream as the subdomain plan); on several ranks its apply_lhs hooks do the trace exchange, the
- * whole-element exchanges around schwarz_iterate are the host's (SchwarzShard), so this entry is for one rank. */
+ * set, homogeneous Dirichlet data, same stream as the subdomain plan).  On several ranks mesh_plan is the rank's own plan -- its
+ * apply_lhs hooks do the trace exchange -- and the handle must carry an element exchange for the whole-element exchanges around the
+ * subdomain solves (without one this entry is for one rank). */
 void d4est_hip_schwarz_smooth(d4est_hip_schwarz_t* sz, d4est_hip_plan_t* mesh_plan, double* u_dev, const double* rhs_dev, double* r_dev,
                               int smoother_iterations, int subdomain_iter, double subdomain_atol, double subdomain_rtol);
 /* schwarz->subdomain_solve_iterations / _residuals of the last iterate (d4est_solver_schwarz.c:259-260), host arrays of n_subdomains */
 void d4est_hip_schwarz_get_info(d4est_hip_schwarz_t* sz, int* final_iter_host, double* final_res_host);
+/* blocking host reads of device counters the handle has made so far: the look at the "still iterating" counter before the first and then
+ * every 8th subdomain sweep, and the sweep count the public d4est_hip_schwarz_iterate returns.  The exchange ends add none. */
+long long d4est_hip_schwarz_host_reads(const d4est_hip_schwarz_t* sz);
+
+/* ---- the smoother on N ranks: the two whole-element exchanges of an iterate inside the handle --------------------------------------------
+ * d4est_ghost_data_exchange of the residual before the subdomain solves (src/Solver/d4est_solver_schwarz.c:197-203; direction 0, owners
+ * -> ghost copies) and d4est_solver_schwarz_transfer_ghost_data_and_add_corrections afterwards
+ * (src/Solver/d4est_solver_schwarz_transfer_ghost_data.c:60-176; direction 1, ghost copies -> owners).
+ *
+ * sz was created on the rank's extended mesh: elements [0, n_own_elements) are the rank's own, the rest its ghost layer; subdomains exist
+ * for the own elements only.  peer_rank is ascending.  send_elem[send_first[p] .. send_first[p+1]) are the own elements that lie in peer
+ * p's ghost layer, recv_elem[recv_first[p] .. recv_first[p+1]) the ghost-layer elements that peer p owns, both in ascending global id on
+ * both ends (parallel.ElementSchedule), so no metadata is exchanged; the block of an element is its (deg + 1)^3 doubles at its
+ * mesh_nodal_stride, as create() copied them.  All arrays are HOST arrays, copied.  Aborts on an index on the wrong side of
+ * n_own_elements, a ghost-layer element that no peer or more than one peer owns, an own element listed twice for one peer, and peers
+ * that are not strictly ascending.
+ *
+ * Buffers: in direction 0 send_dev holds the send_elem blocks, peer after peer, and recv_dev the recv_elem blocks; in direction 1 the
+ * roles swap (send_dev: the recv_elem blocks, recv_dev: the send_elem blocks).  d4est_hip_schwarz_exchange_first(sz, direction,
+ * send_or_recv (0 send, 1 recv), p) is the first double of peer p's segment in that buffer, p = n_peers its total length.
+ * Hook contract: on entry send_dev is complete as far as the subdomain plan's stream is concerned; on return recv_dev must be filled
+ * as far as that stream is concerned (stream-ordered work or a blocking wait, the transport's choice; a collective must not wait on the
+ * host without a time limit).  Every iterate calls the hook exactly once per direction on every rank, also on a rank without
+ * subdomains and whatever the subdomain solves did.  fn == NULL removes the exchange (and frees its buffers).
+ *
+ * With an exchange set: d4est_hip_schwarz_iterate, _smooth, the V-cycle's Schwarz smoother, the reuse_smoother bottom solver and
+ * d4est_hip_pc_schwarz_* take vectors of the OWN nodes (the prefix of the extended vector) and the rank's own plan as mesh_plan (ghost
+ * sides, trace exchange hooks set); the codes of d4est_hip_multigrid_set_smoother_schwarz then read: 2 the plan's local_nodes is not the
+ * handle's own node count, 4 the plan has no faces.  _restrict_field, _apply_over_subdomains and _add_correction stay extended-mesh
+ * entries.  One iterate on the device: (1) one kernel sets the own part of the extended residual and writes the send blocks -- under
+ * D4EST_HIP_SCHWARZ_FUSED_RESIDUAL=1 the smoother and pc loops form rhs - A u in this kernel, the same rounded operation -- (2) hook 0,
+ * (3) one kernel unpacks the ghost-layer part, (4) the subdomain solves, the correction STORED to the extended vector, (5) one kernel
+ * packs its ghost-layer part, hook 1, (6) one kernel adds, per own node, the own correction and then the received blocks in ascending
+ * peer rank (a fixed order, no atomics) -- or stores that sum, for the preconditioner's zero start vector.  Nothing is allocated per
+ * iterate and the exchange ends read nothing on the host. */
+typedef void (*d4est_hip_element_exchange_fn)(void* ctx, int direction, const double* send_dev, double* recv_dev);
+void d4est_hip_schwarz_set_element_exchange(d4est_hip_schwarz_t* sz, int n_own_elements, int n_peers, const int* peer_rank,
+                                            const int* send_first, const int* send_elem, const int* recv_first, const int* recv_elem,
+                                            d4est_hip_element_exchange_fn fn, void* ctx);
+/* nodes of the own elements; the mesh's node count when no exchange is set */
+long long d4est_hip_schwarz_own_nodes(const d4est_hip_schwarz_t* sz);
+long long d4est_hip_schwarz_exchange_first(const d4est_hip_schwarz_t* sz, int direction, int send_or_recv, int peer);
+/* the RCCL transport of the two exchanges, in C (no callback into the host language): per direction one grouped ncclSend / ncclRecv round
+ * on the communicator's stream, with the communicator's event in from and event out to the subdomain plan's stream (as
+ * d4est_hip_comm_sendrecv).  Same lists as above; installs the hook on sz.  Destroy the returned object before sz and comm. */
+typedef struct d4est_hip_schwarz_rccl_exchange d4est_hip_schwarz_rccl_exchange_t;
+d4est_hip_schwarz_rccl_exchange_t* d4est_hip_schwarz_set_rccl_exchange(d4est_hip_schwarz_t* sz, d4est_hip_comm_t* comm, int n_own_elements,
+                                                                       int n_peers, const int* peer_rank, const int* send_first,
+                                                                       const int* send_elem, const int* recv_first, const int* recv_elem);
+void d4est_hip_schwarz_rccl_exchange_destroy(d4est_hip_schwarz_rccl_exchange_t* x);
+long long d4est_hip_schwarz_rccl_exchange_count(const d4est_hip_schwarz_rccl_exchange_t* x);   /* rounds posted so far (two per iterate) */
 
 /* ---- the Chebyshev and Schwarz Krylov preconditioners (csrc/d4est_hip_pc.hip) --------------------------------------------------------
  * d4est_krylov_pc_cheby_apply (src/Solver/d4est_krylov_pc_cheby.c:92-171) and d4est_krylov_pc_schwarz_apply
@@ -993,7 +1048,8 @@ void d4est_hip_pc_cheby_reset_eig(d4est_hip_pc_cheby_t* pc);
 /* Schwarz, [schwarz_pc] schwarz_pc_iterations and the three [d4est_solver_schwarz] CG options: z = 0, then schwarz_pc_iterations times
  * { residual = r - A z; schwarz_iterate(z, residual) }.  In the first pass z is zero, so on a plan with homogeneous boundary data the
  * residual is r itself and the correction is stored into z (no fill, no apply, no read of z; the same numbers).  mesh_plan is the
- * plan of the mesh itself, as for d4est_hip_schwarz_smooth: one rank, the subdomain plan's stream.  create aborts on a mismatch. */
+ * plan of the mesh itself, as for d4est_hip_schwarz_smooth: the subdomain plan's stream; on several ranks the rank's own plan and a
+ * handle with an element exchange (z and r then are vectors of the own nodes).  create aborts on a mismatch. */
 typedef struct d4est_hip_pc_schwarz d4est_hip_pc_schwarz_t;
 d4est_hip_pc_schwarz_t* d4est_hip_pc_schwarz_create(d4est_hip_schwarz_t* schwarz, d4est_hip_plan_t* mesh_plan, int schwarz_pc_iterations,
                                                     int subdomain_iter, double subdomain_atol, double subdomain_rtol);
