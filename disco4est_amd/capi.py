@@ -236,6 +236,10 @@ SIGNATURES = {
     "d4est_hip_amr_interpolate_field": (None, [_vp, _vp, _vp]),
     "d4est_hip_amr_describe": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int]),
     "d4est_hip_amr_advance": (None, [_vp]),
+    "d4est_hip_par_amr_set_comm": (None, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    "d4est_hip_par_amr_stats_global": (None, [_vp, _vp, ctypes.c_int, _vp]),
+    "d4est_hip_par_amr_repartition": (ctypes.c_longlong, [_vp, _vp, _vp]),
+    "d4est_hip_par_amr_repartition_field": (None, [_vp, _vp, _vp]),
     "d4est_hip_probe_create": (_vp, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_int]),
     "d4est_hip_probe_destroy": (None, [_vp]),
     "d4est_hip_probe_n_points": (ctypes.c_int, [_vp]),
@@ -1322,6 +1326,8 @@ class Amr:
         self.lib = load_library()
         d = _iarr(deg)
         self.handle = self.lib.d4est_hip_amr_create(len(d[0]), d[1], int(max_degree), float(initial_pred))
+        self.torch_stream = stream
+        self.rank, self.world = 0, 1
         if stream is not None:
             self.lib.d4est_hip_amr_set_stream(self.handle, ctypes.c_void_p(stream.cuda_stream))
 
@@ -1388,6 +1394,54 @@ class Amr:
 
     def advance(self):
         self.lib.d4est_hip_amr_advance(self.handle)
+
+    # ---- several ranks
+    SENDRECV_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, _c_int_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong),
+                                   ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong))
+
+    def set_comm(self, rank, world, allreduce=None, sendrecv=None):
+        """allreduce(scalars_ptr, n): in-place SUM over ranks of n device doubles; sendrecv(peers, send_ptr, send_first, recv_ptr,
+        recv_first): one grouped point-to-point round (peers and the two first lists are python lists, pointers are ints).  An exception
+        inside a hook aborts the process, as in Plan.set_comm."""
+        def guarded(fn):
+            def call(*args):
+                try:
+                    fn(*args)
+                except BaseException:
+                    import os
+                    import sys
+                    import traceback
+                    sys.stderr.write("[D4EST_HIP_ABORT] exception in a communication callback:\n")
+                    traceback.print_exc()
+                    sys.stderr.flush()
+                    os.abort()
+            return call
+
+        def sr(ctx, n, peers, send, sf, recv, rf):
+            sendrecv([peers[i] for i in range(n)], send or 0, [sf[i] for i in range(n + 1)], recv or 0, [rf[i] for i in range(n + 1)])
+
+        self._cb_ar = Plan.ALLREDUCE_FN(guarded(lambda ctx, p, n: allreduce(p, n))) if allreduce else None
+        self._cb_sr = self.SENDRECV_FN(guarded(sr)) if sendrecv else None
+        self.lib.d4est_hip_par_amr_set_comm(self.handle, int(rank), int(world), ctypes.cast(self._cb_ar, ctypes.c_void_p) if self._cb_ar else None,
+                                        ctypes.cast(self._cb_sr, ctypes.c_void_p) if self._cb_sr else None, None)
+        self.rank, self.world = int(rank), int(world)
+
+    def stats_global(self, eta2, percentile, stats):
+        """stats (4 doubles on the device) <- total, mean, max and estimator_at_percentile over ALL ranks (d4est_hip_par_amr_stats_global)"""
+        assert eta2.numel() == self.n_elements and stats.numel() == 4
+        self.lib.d4est_hip_par_amr_stats_global(self.handle, _ptr(eta2), int(percentile), _ptr(stats))
+
+    def repartition(self, old_first, new_first):
+        """moves degrees and predictor to the partition new_first (global_first_quadrant, world + 1 entries); returns the new local_nodes"""
+        o = np.ascontiguousarray(old_first, dtype=np.int64)
+        n = np.ascontiguousarray(new_first, dtype=np.int64)
+        assert len(o) == self.world + 1 and len(n) == self.world + 1
+        return self.lib.d4est_hip_par_amr_repartition(self.handle, o.ctypes.data_as(ctypes.c_void_p), n.ctypes.data_as(ctypes.c_void_p))
+
+    def repartition_field(self, field_old, field_new):
+        """one nodal field from the old partition to the new one (after repartition)"""
+        assert field_new.numel() == self.local_nodes
+        self.lib.d4est_hip_par_amr_repartition_field(self.handle, _ptr(field_old), _ptr(field_new))
 
     def destroy(self):
         if self.handle:

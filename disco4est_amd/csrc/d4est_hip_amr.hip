@@ -3,6 +3,8 @@
 //
 // Replaces, of the reference's adaptive loop (d4est_amr_step, src/hpAMR/d4est_amr.c:852-1035):
 //   d4est_estimator_stats_compute_aux, single-rank branch          (src/Estimators/d4est_estimator_stats.c:219-251)
+//   ... its mpisize > 1 branch with the global percentile           (:252-274, :350-425), a radix select over ranks, no distributed sort
+//   d4est_amr_load_balance: the transfer to a new partition         (src/hpAMR/d4est_amr.c:773-864; p4est_partition_ext stays on the host)
 //   d4est_amr_smooth_pred_pre_refine_callback (fill, no checkpoint) (src/hpAMR/d4est_amr_smooth_pred.c:23-71)
 //   d4est_amr_smooth_pred_mark_elements                             (:215-268)
 //   the p-balance update of the log and of the predictor            (d4est_amr.c:973-981, d4est_amr_smooth_pred.c:132-168)
@@ -89,6 +91,25 @@ struct d4est_hip_amr {
   d4est_hip_transfer_t* t1 = nullptr;
   d4est_hip_transfer_t* t2 = nullptr;
   double* d_aux_field = nullptr;
+  // ---- several ranks (d4est_hip_par_amr_set_comm); world = 1 calls no hook
+  int rank = 0, world = 1;
+  d4est_hip_allreduce_fn allreduce = nullptr;
+  d4est_hip_amr_sendrecv_fn sendrecv = nullptr;
+  void* comm_ctx = nullptr;
+  // the radix select of stats_global: the (prefix, remaining rank) state, the integer bins and the doubles the allreduce hook sums
+  unsigned long long* d_sel = nullptr;   // [0], [1] key prefix of the percentile / the maximum; [2], [3] remaining rank; [4], [5] target valid
+  unsigned int* d_bins = nullptr;        // two histograms of kSelBins
+  double* d_red = nullptr;               // the bins as doubles, then the local sum and the local n
+  // ---- the state of one repartition, for repartition_field
+  struct Repart {
+    bool valid = false, exchange = false;
+    std::vector<int> peers;
+    std::vector<long long> send_first, recv_first;   // per peer, in nodes: the send buffer is the old field without the part that stays
+    long long old_nodes = 0, new_nodes = 0, n_send = 0, n_recv = 0;
+    long long self_old = 0, self_new = 0, self_len = 0;   // the part that stays: offsets in the old and the new field, length
+    double* d_send = nullptr;
+    double* d_recv = nullptr;
+  } rp;
 };
 
 namespace d4est_hip {
@@ -117,6 +138,171 @@ __global__ __launch_bounds__(1024) void amr_stats_kernel(const double* __restric
       stats[0] = 0.0;
       stats[1] = stats[2] = stats[3] = -1.0;
     }
+  }
+}
+
+// ---- statistics over ranks: radix select ------------------------------------------------------------------------------------------------
+// The k-th smallest of all ranks' eta2 without a distributed sort.  A double maps to a 64-bit key of the same order (negatives: all bits
+// flipped; non-negatives: sign bit set); kSelPasses digit passes from the most significant digit down.  Per pass: a histogram of the digit
+// over the local keys that carry the prefix chosen so far (LDS integer atomics per workgroup, integer atomics into the global bins), the
+// bins as doubles (exact below 2^53) through the allreduce hook, and a one-wavefront pick that chooses the digit and updates (prefix,
+// remaining rank) on the device.  Two targets ride the same passes: rank G - k (the percentile) and rank G - 1 (the maximum).
+constexpr int kSelBits = 8;
+constexpr int kSelBins = 1 << kSelBits;
+constexpr int kSelPasses = 64 / kSelBits;
+constexpr int kSelRed = 2 * kSelBins + 2;   // doubles of the first round: two histograms, the local sum, the local n
+constexpr unsigned long long kSignBit = 0x8000000000000000ull;
+
+__device__ __forceinline__ unsigned long long amr_key(double x) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+  return (b & kSignBit) ? ~b : (b | kSignBit);
+}
+__device__ __forceinline__ double amr_unkey(unsigned long long k) {
+  return __longlong_as_double((long long)((k & kSignBit) ? (k ^ kSignBit) : ~k));
+}
+
+// the fixed-order local sum of amr_stats_kernel (thread t: entries t, t + 1024, ...; then a binary tree) and the local n
+__global__ __launch_bounds__(1024) void amr_local_sum_kernel(const double* __restrict__ eta2, int n, double* __restrict__ red) {
+  __shared__ double s[1024];
+  const int t = threadIdx.x;
+  double acc = 0.0;
+  for (int i = t; i < n; i += 1024) acc = __dadd_rn(acc, eta2[i]);
+  s[t] = acc;
+  __syncthreads();
+  for (int w = 512; w > 0; w >>= 1) {
+    if (t < w) s[t] = __dadd_rn(s[t], s[t + w]);
+    __syncthreads();
+  }
+  if (t == 0) {
+    red[2 * kSelBins] = s[0];
+    red[2 * kSelBins + 1] = (double)n;
+  }
+}
+
+// grid-stride over n, kSelBins threads: bins[d] += keys with the percentile target's prefix and digit d, bins[kSelBins + d] likewise for
+// the maximum's prefix.  Pass 0 has no prefix: sel is not read through the mask.
+__global__ __launch_bounds__(kSelBins) void amr_sel_hist_kernel(const double* __restrict__ eta2, int n, int pass,
+                                                                const unsigned long long* __restrict__ sel, unsigned int* __restrict__ bins) {
+  __shared__ unsigned int h[2 * kSelBins];
+  const int t = threadIdx.x;
+  h[t] = 0u;
+  h[kSelBins + t] = 0u;
+  __syncthreads();
+  const int shift = 64 - kSelBits * (pass + 1);
+  const unsigned long long mask = pass == 0 ? 0ull : ~0ull << (shift + kSelBits);
+  const unsigned long long p0 = sel[0], p1 = sel[1];
+  for (long long i = (long long)blockIdx.x * kSelBins + t; i < n; i += (long long)gridDim.x * kSelBins) {
+    const unsigned long long key = amr_key(eta2[i]);
+    const int d = (int)((key >> shift) & (kSelBins - 1));
+    if (((key ^ p0) & mask) == 0ull) atomicAdd(&h[d], 1u);
+    if (((key ^ p1) & mask) == 0ull) atomicAdd(&h[kSelBins + d], 1u);
+  }
+  __syncthreads();
+  if (h[t]) atomicAdd(&bins[t], h[t]);
+  if (h[kSelBins + t]) atomicAdd(&bins[kSelBins + t], h[kSelBins + t]);
+}
+
+// the bins as doubles for the allreduce hook; the integer bins are zero again for the next pass
+__global__ __launch_bounds__(2 * kSelBins) void amr_sel_convert_kernel(unsigned int* __restrict__ bins, double* __restrict__ red) {
+  const int t = threadIdx.x;
+  red[t] = (double)bins[t];
+  bins[t] = 0u;
+}
+
+// One wavefront.  Pass 0 sets the targets from the global n and total (d4est_estimator_stats.c:379: k = (int)((double)(G * percentile) /
+// 100.0), the percentile is entry G - k of the ascending order; k = 0 has no entry, the reference aborts at :396) and writes total and mean;
+// every pass scans the summed bins (lane l: bins 4 l .. 4 l + 3, an exclusive prefix over the lanes through LDS), the lane that holds the
+// target's rank appends the digit to the prefix; the last pass turns the keys back into doubles.
+__global__ __launch_bounds__(64) void amr_sel_pick_kernel(const double* __restrict__ red, int pass, int percentile,
+                                                          unsigned long long* __restrict__ sel, double* __restrict__ stats) {
+  __shared__ unsigned long long s[64];
+  const int t = threadIdx.x;
+  constexpr int PER = kSelBins / 64;
+  const int shift = 64 - kSelBits * (pass + 1);
+  unsigned long long prefix[2], rank[2], valid[2];
+  if (pass == 0) {
+    const long long G = (long long)red[2 * kSelBins + 1];
+    const long long k = (long long)((double)(G * (long long)percentile) / 100.0);
+    prefix[0] = prefix[1] = 0ull;
+    rank[0] = (unsigned long long)(G - k);
+    rank[1] = (unsigned long long)(G - 1);
+    valid[0] = (G > 0 && k > 0) ? 1ull : 0ull;
+    valid[1] = G > 0 ? 1ull : 0ull;
+    if (t == 0) {
+      stats[0] = G > 0 ? red[2 * kSelBins] : 0.0;   // d4est_estimator_stats.c:234-238 where there is no element at all
+      stats[1] = G > 0 ? __ddiv_rn(red[2 * kSelBins], (double)G) : -1.0;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      prefix[j] = sel[j];
+      rank[j] = sel[2 + j];
+      valid[j] = sel[4 + j];
+    }
+  }
+  const bool last = pass == kSelPasses - 1;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    unsigned long long c[PER], own = 0ull;
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      c[q] = (unsigned long long)red[j * kSelBins + t * PER + q];
+      own += c[q];
+    }
+    s[t] = own;
+    __syncthreads();   // (also: every lane has read sel before a lane writes it)
+    unsigned long long before = 0ull;
+    for (int l = 0; l < t; ++l) before += s[l];
+    __syncthreads();
+    double* out = stats + (j == 0 ? 3 : 2);
+    if (!valid[j]) {
+      if (t == 0) {
+        sel[j] = 0ull; sel[2 + j] = 0ull; sel[4 + j] = 0ull;
+        if (last) *out = -1.0;
+      }
+    } else if (rank[j] >= before && rank[j] < before + own) {   // exactly one lane: the counts of the prefix sum up to more than the rank
+      unsigned long long r = rank[j] - before;
+      int q = 0;
+#pragma unroll
+      for (int u = 0; u < PER - 1; ++u)
+        if (q == u && r >= c[u]) { r -= c[u]; q = u + 1; }
+      const unsigned long long np = prefix[j] | ((unsigned long long)(t * PER + q) << shift);
+      sel[j] = np; sel[2 + j] = r; sel[4 + j] = 1ull;
+      if (last) *out = amr_unkey(np);
+    }
+  }
+}
+
+// ---- the load-balance transfer ------------------------------------------------------------------------------------------------------------
+// A rank's elements all go somewhere: what is sent, in peer order, is the old array WITHOUT the part that stays (a gap of gap_len entries
+// at gap_at), and what arrives is the new array without that part.  Degrees travel as doubles next to the predictor.
+__device__ __forceinline__ long long amr_gap(long long i, long long gap_at, long long gap_len) { return i < gap_at ? i : i + gap_len; }
+
+__global__ __launch_bounds__(256) void amr_state_pack_kernel(const int* __restrict__ deg, const double* __restrict__ pred, long long n_send,
+                                                             long long gap_at, long long gap_len, double* __restrict__ buf) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_send; i += (long long)gridDim.x * 256) {
+    const long long e = amr_gap(i, gap_at, gap_len);
+    buf[2 * i] = (double)deg[e];
+    buf[2 * i + 1] = pred[e];
+  }
+}
+
+__global__ __launch_bounds__(256) void amr_state_unpack_kernel(const double* __restrict__ buf, long long n_recv, long long gap_at,
+                                                               long long gap_len, int* __restrict__ deg, double* __restrict__ pred) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_recv; i += (long long)gridDim.x * 256) {
+    const long long e = amr_gap(i, gap_at, gap_len);
+    deg[e] = (int)buf[2 * i];
+    pred[e] = buf[2 * i + 1];
+  }
+}
+
+// unpack = 0: dst[i] = src[gap(i)] (the send buffer from the old field); 1: dst[gap(i)] = src[i] (the new field from the receive buffer)
+__global__ __launch_bounds__(256) void amr_gap_copy_kernel(const double* __restrict__ src, double* __restrict__ dst, long long n,
+                                                           long long gap_at, long long gap_len, int unpack) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const long long j = amr_gap(i, gap_at, gap_len);
+    if (unpack) dst[j] = src[i];
+    else dst[i] = src[j];
   }
 }
 
@@ -344,6 +530,11 @@ static void balance_free(d4est_hip_amr* A) {
   A->balanced = false;
 }
 
+static void repart_free(d4est_hip_amr* A) {
+  (void)hipFree(A->rp.d_send); (void)hipFree(A->rp.d_recv);
+  A->rp = d4est_hip_amr::Repart();
+}
+
 // d4est_amr.c:374-392: a code is -deg' (h-refine into children of degree deg' >= deg) or deg' >= deg
 static void check_log(const d4est_hip_amr* A, const int* log, const char* who) {
   const int limit = amr_degree_limit();
@@ -390,6 +581,9 @@ d4est_hip_amr_t* d4est_hip_amr_create(int n_elements, const int* deg, int max_de
   const char* ts = std::getenv("D4EST_HIP_AMR_TWO_STAGE");
   A->two_stage = ts && ts[0] && ts[0] != '0';
   level_alloc(A->cur, std::vector<int>(deg, deg + n_elements));
+  A->d_sel = dev_upload(std::vector<unsigned long long>(8, 0ull));
+  A->d_bins = dev_upload(std::vector<unsigned int>(2 * kSelBins, 0u));
+  A->d_red = dev_upload(std::vector<double>(kSelRed, 0.0));
   if (n_elements > 0) {
     hipLaunchKernelGGL(amr_fill_kernel, grid_for(n_elements), dim3(256), 0, A->stream, A->cur.d_pred, initial_pred, n_elements);
     HIP_CHECK(hipGetLastError());
@@ -401,8 +595,10 @@ d4est_hip_amr_t* d4est_hip_amr_create(int n_elements, const int* deg, int max_de
 void d4est_hip_amr_destroy(d4est_hip_amr_t* A) {
   if (!A) return;
   balance_free(A);
+  repart_free(A);
   level_free(A->cur);
   level_free(A->next);
+  (void)hipFree(A->d_sel); (void)hipFree(A->d_bins); (void)hipFree(A->d_red);
   delete A;
 }
 
@@ -689,9 +885,169 @@ void d4est_hip_amr_advance(d4est_hip_amr_t* A) {
   HIP_CHECK(hipStreamSynchronize(A->stream));
   std::swap(A->cur, A->next);
   balance_free(A);
+  repart_free(A);
   level_free(A->next);
   A->h_log.clear();
   A->log_valid = false;
+}
+
+// ---- several ranks ------------------------------------------------------------------------------------------------------------------------
+void d4est_hip_par_amr_set_comm(d4est_hip_amr_t* A, int rank, int world, d4est_hip_allreduce_fn allreduce, d4est_hip_amr_sendrecv_fn sendrecv,
+                            void* ctx) {
+  if (!A) D4EST_HIP_ABORT("amr_set_comm: NULL amr");
+  if (world < 1 || rank < 0 || rank >= world) D4EST_HIP_ABORT("amr_set_comm: rank %d outside 0 .. world - 1 = %d", rank, world - 1);
+  A->rank = rank;
+  A->world = world;
+  A->allreduce = allreduce;
+  A->sendrecv = sendrecv;
+  A->comm_ctx = ctx;
+  repart_free(A);
+}
+
+void d4est_hip_par_amr_stats_global(d4est_hip_amr_t* A, const double* eta2_dev, int percentile, double* stats_dev) {
+  if (!A || !stats_dev) D4EST_HIP_ABORT("amr_stats_global: NULL argument");
+  if (percentile < 0 || percentile > 100) D4EST_HIP_ABORT("amr_stats_global: percentile %d outside 0 .. 100", percentile);
+  const int n = A->cur.n;
+  if (n > 0 && !eta2_dev) D4EST_HIP_ABORT("amr_stats_global: NULL eta2");
+  if (A->world > 1 && !A->allreduce) D4EST_HIP_ABORT("amr_stats_global: world = %d, but no allreduce hook is set", A->world);
+  hipLaunchKernelGGL(amr_local_sum_kernel, dim3(1), dim3(1024), 0, A->stream, eta2_dev, n, A->d_red);
+  const unsigned blocks = (unsigned)std::min(std::max((n + kSelBins - 1) / kSelBins, 1), 1024);
+  for (int pass = 0; pass < kSelPasses; ++pass) {
+    hipLaunchKernelGGL(amr_sel_hist_kernel, dim3(blocks), dim3(kSelBins), 0, A->stream, eta2_dev, n, pass, A->d_sel, A->d_bins);
+    hipLaunchKernelGGL(amr_sel_convert_kernel, dim3(1), dim3(2 * kSelBins), 0, A->stream, A->d_bins, A->d_red);
+    HIP_CHECK(hipGetLastError());
+    // one round per pass; the first also carries the local sum and the local n
+    if (A->world > 1) A->allreduce(A->comm_ctx, A->d_red, pass == 0 ? kSelRed : 2 * kSelBins);
+    hipLaunchKernelGGL(amr_sel_pick_kernel, dim3(1), dim3(64), 0, A->stream, A->d_red, pass, percentile, A->d_sel, stats_dev);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+long long d4est_hip_par_amr_repartition(d4est_hip_amr_t* A, const long long* old_first, const long long* new_first) {
+  if (!A || !old_first || !new_first) D4EST_HIP_ABORT("amr_repartition: NULL argument");
+  if (A->balanced) D4EST_HIP_ABORT("amr_repartition: a balance log is set: repartition the level after d4est_hip_amr_advance");
+  const int W = A->world, me = A->rank;
+  if (old_first[0] != new_first[0] || old_first[W] != new_first[W])
+    D4EST_HIP_ABORT("amr_repartition: the partitions cover different totals: old %lld .. %lld, new %lld .. %lld", old_first[0], old_first[W],
+                    new_first[0], new_first[W]);
+  for (int p = 0; p < W; ++p)
+    if (old_first[p + 1] < old_first[p] || new_first[p + 1] < new_first[p])
+      D4EST_HIP_ABORT("amr_repartition: the first-element arrays must be monotone (rank %d)", p);
+  const long long olo = old_first[me], ohi = old_first[me + 1], nlo = new_first[me], nhi = new_first[me + 1];
+  if (ohi - olo != (long long)A->cur.n)
+    D4EST_HIP_ABORT("amr_repartition: the old partition gives rank %d %lld elements, the object holds %d", me, ohi - olo, A->cur.n);
+  if (nhi - nlo > 0x7fffffffLL) D4EST_HIP_ABORT("amr_repartition: %lld elements on one rank", nhi - nlo);
+  const int n_old = A->cur.n, n_new = (int)(nhi - nlo);
+  const bool same = std::equal(old_first, old_first + W + 1, new_first);
+  if (!same && !A->sendrecv) D4EST_HIP_ABORT("amr_repartition: world = %d, but no sendrecv hook is set", W);
+  repart_free(A);
+  d4est_hip_amr::Repart& R = A->rp;
+
+  // rank me sends rank p the intersection of its old range with p's new range, and receives its new range's intersection with p's old one
+  auto overlap = [](long long a0, long long a1, long long b0, long long b1) { return std::max(0LL, std::min(a1, b1) - std::max(a0, b0)); };
+  std::vector<long long> se(1, 0), re(1, 0);   // per peer, in elements
+  for (int p = 0; p < W; ++p) {
+    if (p == me) continue;
+    const long long ns = overlap(olo, ohi, new_first[p], new_first[p + 1]), nr = overlap(nlo, nhi, old_first[p], old_first[p + 1]);
+    if (ns == 0 && nr == 0) continue;
+    R.peers.push_back(p);
+    se.push_back(se.back() + ns);
+    re.push_back(re.back() + nr);
+  }
+  const long long self_n = overlap(olo, ohi, nlo, nhi);
+  const long long self_old = self_n > 0 ? std::max(olo, nlo) - olo : 0, self_new = self_n > 0 ? std::max(olo, nlo) - nlo : 0;
+  const long long n_send = n_old - self_n, n_recv = n_new - self_n;
+  if (se.back() != n_send || re.back() != n_recv) D4EST_HIP_ABORT("amr_repartition: internal element count mismatch");
+  const int np = (int)R.peers.size();
+
+  // 1. degree and predictor to the new owner: one pack kernel, one round, one unpack kernel
+  double* d_sbuf = dev_alloc<double>((size_t)2 * n_send);
+  double* d_rbuf = dev_alloc<double>((size_t)2 * n_recv);
+  int* d_ndeg = dev_alloc<int>((size_t)n_new);
+  double* d_npred = dev_alloc<double>((size_t)n_new);
+  auto grid_ll = [](long long n) { return dim3((unsigned)std::min<long long>(std::max<long long>((n + 255) / 256, 1), 65536)); };
+  if (n_send > 0)
+    hipLaunchKernelGGL(amr_state_pack_kernel, grid_ll(n_send), dim3(256), 0, A->stream, A->cur.d_deg, A->cur.d_pred, n_send, self_old, self_n,
+                       d_sbuf);
+  HIP_CHECK(hipGetLastError());
+  if (!same) {   // every rank makes the round, also one without a peer: the hook may be a collective of the transport
+    std::vector<long long> sf(se), rf(re);
+    for (long long& v : sf) v *= 2;
+    for (long long& v : rf) v *= 2;
+    A->sendrecv(A->comm_ctx, np, R.peers.data(), d_sbuf, sf.data(), d_rbuf, rf.data());
+  }
+  if (n_recv > 0)
+    hipLaunchKernelGGL(amr_state_unpack_kernel, grid_ll(n_recv), dim3(256), 0, A->stream, d_rbuf, n_recv, self_new, self_n, d_ndeg, d_npred);
+  HIP_CHECK(hipGetLastError());
+  if (self_n > 0) {
+    HIP_CHECK(hipMemcpyAsync(d_ndeg + self_new, A->cur.d_deg + self_old, (size_t)self_n * sizeof(int), hipMemcpyDeviceToDevice, A->stream));
+    HIP_CHECK(hipMemcpyAsync(d_npred + self_new, A->cur.d_pred + self_old, (size_t)self_n * sizeof(double), hipMemcpyDeviceToDevice, A->stream));
+  }
+  // 2. the received degrees
+  std::vector<int> ndeg((size_t)n_new);
+  if (n_new > 0) HIP_CHECK(hipMemcpyAsync(ndeg.data(), d_ndeg, (size_t)n_new * sizeof(int), hipMemcpyDeviceToHost, A->stream));
+  HIP_CHECK(hipStreamSynchronize(A->stream));
+  const int limit = amr_degree_limit();
+  for (int e = 0; e < n_new; ++e)
+    if (ndeg[e] < 1 || ndeg[e] > limit) D4EST_HIP_ABORT("amr_repartition: received degree %d for new element %d (outside 1 .. %d)", ndeg[e], e, limit);
+
+  // node offsets of both element lists, for repartition_field
+  auto nodes_of = [](int d) { return (long long)(d + 1) * (d + 1) * (d + 1); };
+  std::vector<long long> opre((size_t)n_old + 1, 0), npre((size_t)n_new + 1, 0);
+  for (int e = 0; e < n_old; ++e) opre[e + 1] = opre[e] + nodes_of(A->cur.deg[e]);
+  for (int e = 0; e < n_new; ++e) npre[e + 1] = npre[e] + nodes_of(ndeg[e]);
+  auto gap_e = [](long long i, long long at, long long len) { return i < at ? i : i + len; };   // buffer element -> local element
+  R.send_first.assign(1, 0);
+  R.recv_first.assign(1, 0);
+  for (int i = 0; i < np; ++i) {
+    long long ns = 0, nr = 0;
+    if (se[i + 1] > se[i]) { const long long a = gap_e(se[i], self_old, self_n); ns = opre[a + (se[i + 1] - se[i])] - opre[a]; }
+    if (re[i + 1] > re[i]) { const long long a = gap_e(re[i], self_new, self_n); nr = npre[a + (re[i + 1] - re[i])] - npre[a]; }
+    R.send_first.push_back(R.send_first.back() + ns);
+    R.recv_first.push_back(R.recv_first.back() + nr);
+  }
+  R.old_nodes = opre[n_old];
+  R.new_nodes = npre[n_new];
+  R.self_old = opre[self_old];
+  R.self_new = npre[self_new];
+  R.self_len = opre[self_old + self_n] - opre[self_old];
+  if (R.self_len != npre[self_new + self_n] - npre[self_new]) D4EST_HIP_ABORT("amr_repartition: the part that stays changed its node count");
+  R.n_send = R.old_nodes - R.self_len;
+  R.n_recv = R.new_nodes - R.self_len;
+  if (R.send_first.back() != R.n_send || R.recv_first.back() != R.n_recv) D4EST_HIP_ABORT("amr_repartition: internal node count mismatch");
+  R.exchange = !same;
+  R.d_send = dev_alloc<double>((size_t)R.n_send);
+  R.d_recv = dev_alloc<double>((size_t)R.n_recv);
+
+  // 3. the new local list becomes the current level
+  level_alloc(A->next, ndeg);
+  if (n_new > 0) HIP_CHECK(hipMemcpyAsync(A->next.d_pred, d_npred, (size_t)n_new * sizeof(double), hipMemcpyDeviceToDevice, A->stream));
+  HIP_CHECK(hipStreamSynchronize(A->stream));
+  std::swap(A->cur, A->next);
+  level_free(A->next);
+  (void)hipFree(d_sbuf); (void)hipFree(d_rbuf); (void)hipFree(d_ndeg); (void)hipFree(d_npred);
+  A->h_log.clear();
+  A->log_valid = false;
+  R.valid = true;
+  return A->cur.nodes;
+}
+
+void d4est_hip_par_amr_repartition_field(d4est_hip_amr_t* A, const double* field_old_dev, double* field_new_dev) {
+  if (!A || !A->rp.valid) D4EST_HIP_ABORT("amr_repartition_field: no repartition since the last advance");
+  const d4est_hip_amr::Repart& R = A->rp;
+  if ((R.old_nodes > 0 && !field_old_dev) || (R.new_nodes > 0 && !field_new_dev)) D4EST_HIP_ABORT("amr_repartition_field: NULL field");
+  auto grid_ll = [](long long n) { return dim3((unsigned)std::min<long long>(std::max<long long>((n + 255) / 256, 1), 65536)); };
+  if (R.n_send > 0)
+    hipLaunchKernelGGL(amr_gap_copy_kernel, grid_ll(R.n_send), dim3(256), 0, A->stream, field_old_dev, R.d_send, R.n_send, R.self_old, R.self_len, 0);
+  HIP_CHECK(hipGetLastError());
+  if (R.exchange)
+    A->sendrecv(A->comm_ctx, (int)R.peers.size(), R.peers.data(), R.d_send, R.send_first.data(), R.d_recv, R.recv_first.data());
+  if (R.n_recv > 0)
+    hipLaunchKernelGGL(amr_gap_copy_kernel, grid_ll(R.n_recv), dim3(256), 0, A->stream, R.d_recv, field_new_dev, R.n_recv, R.self_new, R.self_len, 1);
+  HIP_CHECK(hipGetLastError());
+  if (R.self_len > 0)
+    HIP_CHECK(hipMemcpyAsync(field_new_dev + R.self_new, field_old_dev + R.self_old, (size_t)R.self_len * sizeof(double), hipMemcpyDeviceToDevice,
+                             A->stream));
 }
 
 }  // extern "C"

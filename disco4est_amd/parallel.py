@@ -468,3 +468,47 @@ def attach_schwarz_rccl(shard, comm):
     x.destroy = destroy
     shard.exchange = x
     return x
+
+
+# ---- the hp-AMR step on several ranks (d4est_hip_par_amr_set_comm) ------------------------------------------------------------------------------
+def first_of(parts):
+    """global_first_quadrant (world + 1 entries) of a list of (first, count) ranges, the form d4est_hip_par_amr_repartition takes"""
+    return np.asarray([f for f, _ in parts] + [parts[-1][0] + parts[-1][1]], dtype=np.int64)
+
+
+def attach_amr(amr, transport, device, rank=None, world=None):
+    """Wire a capi.Amr to a transport (DistTransport or an in-process one with allreduce_sum and round / start + finish): installs the
+    allreduce hook of stats_global and the sendrecv hook of repartition / repartition_field.  rank and world default to the transport's
+    (``rank`` / ``world`` attributes) or to torch.distributed's.  Both hooks order themselves behind the Amr's stream."""
+    import contextlib
+    import torch
+    if rank is None:
+        rank = transport.rank if hasattr(transport, "rank") else transport.dist.get_rank(transport.group)
+    if world is None:
+        world = transport.world if hasattr(transport, "world") else transport.dist.get_world_size(transport.group)
+
+    def view(ptr, n):
+        class _Holder:
+            pass
+        h = _Holder()
+        h.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (int(ptr), False), "version": 2}
+        return torch.as_tensor(h, device=device)
+
+    def on_amr_stream():
+        ts = getattr(amr, "torch_stream", None)              # the collectives order themselves behind torch's CURRENT stream
+        return torch.cuda.stream(ts) if ts is not None else contextlib.nullcontext()
+
+    def allreduce(ptr, n):
+        with on_amr_stream():
+            transport.allreduce_sum(view(ptr, n))
+
+    def sendrecv(peers, send_ptr, send_first, recv_ptr, recv_first):
+        with on_amr_stream():
+            empty = torch.empty(0, dtype=torch.float64, device=device)
+            send = view(send_ptr, send_first[-1]) if send_first[-1] else empty
+            recv = view(recv_ptr, recv_first[-1]) if recv_first[-1] else empty
+            exchange_round(transport, {p: send[send_first[i]:send_first[i + 1]] for i, p in enumerate(peers) if send_first[i + 1] > send_first[i]},
+                           {p: recv[recv_first[i]:recv_first[i + 1]] for i, p in enumerate(peers) if recv_first[i + 1] > recv_first[i]})
+
+    amr.set_comm(rank, world, allreduce, sendrecv)
+    return allreduce, sendrecv

@@ -1062,7 +1062,9 @@ void d4est_hip_pc_schwarz_apply(void* pc, const double* r_dev, double* z_dev);
  * p4est_refine_ext, p4est_balance_ext and the p-balance face walk (d4est_amr.c:923-958) stay on the host; they exchange the refinement
  * log, the balance log and the p_balance array -- one int per element -- with this object.  Everything runs on the object's stream
  * (default: the null stream); nothing allocates after create / set_balance; no floating-point atomics and fixed reduction orders, so
- * results are bit-identical from call to call.  One rank: reductions over ranks stay with the caller, as for the norms.
+ * results are bit-identical from call to call.  One rank: reductions over ranks stay with the caller, as for the norms -- except through
+ * the entries under "the hp-AMR step on several ranks" below, which take two communication hooks; of those, d4est_hip_par_amr_repartition may
+ * allocate (it rebuilds the level), as create and set_balance do.
  *
  * create: the per-element degrees (1 .. 20, the limit of d4est_hip_transfer_create's kernels: two (deg + 1)^3 fields in the 160 KB LDS;
  * aborts above it), amr->max_degree, and the predictor filled with initial_pred as d4est_amr_smooth_pred_pre_refine_callback does
@@ -1077,7 +1079,8 @@ long long d4est_hip_amr_local_nodes(const d4est_hip_amr_t* amr);
  * stats_dev[0] estimator_total (a fixed-order sum of eta2), [1] estimator_mean = total / n, [2] estimator_max, [3] estimator_at_percentile
  * = entry (int)(((double)n)*(1.-((double)percentile/100.0))) of the ascending-sorted eta2 (:249; the index is evaluated on the host in that
  * arithmetic; the sort is a device radix sort, eta2_dev is left as it is).  percentile 1 .. 100; with percentile = 0 the reference reads
- * one past the end of the array: here stats_dev[3] = -1.  n = 0 writes 0, -1, -1, -1 (:234-238). */
+ * one past the end of the array: here stats_dev[3] = -1.  n = 0 writes 0, -1, -1, -1 (:234-238).  This entry keeps the ONE-RANK index of
+ * :249 whatever d4est_hip_par_amr_set_comm says; the index of the reference's mpisize > 1 branch differs: d4est_hip_par_amr_stats_global. */
 void d4est_hip_amr_stats(d4est_hip_amr_t* amr, const double* eta2_dev, int percentile, double* stats_dev);
 /* d4est_amr_smooth_pred_mark_elements (src/hpAMR/d4est_amr_smooth_pred.c:215-268) for every element, with the marker
  * eta2 >= factor * (*threshold_dev): sigma * mean as in Problems/Stamm/stamm_multigrid_pc.c:35-50 (stats_dev + 1, sigma) and the
@@ -1118,6 +1121,48 @@ int d4est_hip_amr_describe(const d4est_hip_amr_t* amr, char* buf, int len);
  * predictor, children of a balance split get 0.125 * gamma_h * 0.5^(2 |balance_log|) * aux (gamma_h of the last mark call); then the new
  * degrees become current and the object is ready for the next level (the balance state is dropped; synchronises the stream). */
 void d4est_hip_amr_advance(d4est_hip_amr_t* amr);
+
+/* ---- the hp-AMR step on several ranks (csrc/d4est_hip_amr.hip) ------------------------------------------------------------------------
+ * The two places of d4est_amr_step that talk to other ranks: the estimator statistics over all ranks and the load balance after the
+ * refinement.  The object reaches the other ranks through two hooks of the caller.  allreduce: the contract of d4est_hip_plan_set_comm --
+ * an in-place SUM over ranks of n device doubles -- here ordered on the AMR object's stream.  sendrecv: ONE grouped point-to-point round on
+ * contiguous device ranges, the shape of d4est_hip_comm_sendrecv: to peer_rank[p] go the doubles [send_first[p], send_first[p + 1]) of
+ * send_dev, from it arrive [recv_first[p], recv_first[p + 1]) of recv_dev (peers ascending; the two first arrays are host arrays of
+ * n_peers + 1 entries, valid during the call); ordered on the object's stream too.  Every rank of a repartition whose partitions differ
+ * makes the round, also a rank without a peer (n_peers = 0), so a hook may be a collective of its transport.  Without set_comm the object
+ * is rank 0 of world 1: the entries below work and call no hook.  These entries carry the prefix d4est_hip_par_amr_ ("parallel"): the
+ * d4est_hip_amr_ names above are the one-rank interface, a closed list. */
+typedef void (*d4est_hip_amr_sendrecv_fn)(void* ctx, int n_peers, const int* peer_rank, const double* send_dev, const long long* send_first,
+                                          double* recv_dev, const long long* recv_first);
+void d4est_hip_par_amr_set_comm(d4est_hip_amr_t* amr, int rank, int world, d4est_hip_allreduce_fn allreduce, d4est_hip_amr_sendrecv_fn sendrecv,
+                            void* ctx);
+/* d4est_estimator_stats_compute_aux, the mpisize > 1 branch (src/Estimators/d4est_estimator_stats.c:252-274), results on the device.  With
+ * G the element count of all ranks: stats_dev[0] the SUM over ranks of each rank's fixed-order local sum (:265), [1] total / G (:266), [2] the
+ * maximum over all ranks (:269), [3] what d4est_estimator_stats_get_global_percentile_parallel returns (:350-425): entry G - k of the
+ * ascending order of ALL ranks' eta2 with k = (int)((double)(G * percentile) / 100.0) (:379, :391) -- not the index of the one-rank branch
+ * (:249), which d4est_hip_amr_stats keeps.  k = 0 (the reference aborts, :396) writes -1 to [3]; G = 0 writes 0, -1, -1, -1; a rank without
+ * elements is legal.  Instead of the reference's distributed sort and rank walk (:254, :383-418) a radix select over ranks: a double maps to
+ * an order-preserving 64-bit key, eight passes of eight bits from the top; per pass a histogram of the local keys under the prefix chosen
+ * so far (integer atomics), ONE allreduce call of the bins as doubles (exact below 2^53), and a one-wavefront kernel that picks the digit.
+ * The percentile and the maximum share the passes; the first round also carries the local n and sum: eight hook calls whatever n is.  No
+ * host read anywhere, the selection state stays on the device, eta2_dev is left as it is; the same bits on every call, and [2], [3] are
+ * the bits a sort of the concatenated array gives, on any number of ranks.  d4est_hip_amr_mark_smooth_pred takes its threshold from
+ * stats_dev + 1 or stats_dev + 3 as on one rank. */
+void d4est_hip_par_amr_stats_global(d4est_hip_amr_t* amr, const double* eta2_dev, int percentile, double* stats_dev);
+/* The transfer of d4est_amr_load_balance (src/hpAMR/d4est_amr.c:773-864) once p4est_partition_ext has run on the host: old_first_host and
+ * new_first_host are p4est->global_first_quadrant before and after it (world + 1 entries).  Rank r sends rank p the intersection of its old
+ * range with p's new range -- both partitions are Morton-contiguous, so every message is one contiguous slice and what arrives, in peer
+ * order, is in global order; the part that stays is a device-to-device copy.  Called on the current level, after d4est_hip_amr_advance,
+ * where the reference's drivers balance the load.  Moves every element's degree and predictor to the new owner (one pack kernel, one
+ * sendrecv round, one unpack kernel; degrees travel as doubles), synchronises, reads the received degrees and rebuilds the level: n_elements,
+ * local_nodes, the predictor and every later call see the new local list.  Returns the new local node count.  Allocates.  Equal arrays
+ * call no hook.  A rank may end up without elements.  Aborts on arrays that are not monotone, that cover different totals, or whose old
+ * range of this rank is not n_elements. */
+long long d4est_hip_par_amr_repartition(d4est_hip_amr_t* amr, const long long* old_first_host, const long long* new_first_host);
+/* p4est_transfer_custom's part (d4est_amr.c:803-863): one nodal field from the old partition (the node count before the repartition) to
+ * the new one (the count it returned), node offsets from the old and the new degree lists; one call, one sendrecv round per field.  Valid
+ * from d4est_hip_par_amr_repartition until the next d4est_hip_amr_mark_smooth_pred or d4est_hip_amr_advance. */
+void d4est_hip_par_amr_repartition_field(d4est_hip_amr_t* amr, const double* field_old_dev, double* field_new_dev);
 
 /* ---- point probes: field value and gradient at tree coordinates (csrc/d4est_hip_probe.hip) -----------------------------------------
  * d4est_mesh_interpolate_at_tree_coord (src/Mesh/d4est_mesh.c:3294-3362) with d4est_operators_interpolate
