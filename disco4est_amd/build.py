@@ -19,6 +19,8 @@ SOURCES = [
     "d4est_hip_capi.hip",
     "d4est_hip_volume.hip",
     "d4est_hip_faces.hip",
+    "d4est_hip_faces_setup.hip",
+    "d4est_hip_faces_geometry.hip",
     "d4est_hip_direct.hip",
     "d4est_hip_direct_mw.hip",
     "d4est_hip_direct_mw_hi.hip",

@@ -18,65 +18,18 @@
 //      applies  W_0 + sum_l D_l^T W_l  into Au_e once: race-free and deterministic, no atomics.
 // The reference's 24 doubles of mortar geometry per quadrature node are pre-combined at set-up into 7:
 //   am_i = sum_d sj n_d (dr_i/dx_d)^-,  ap_i = sum_d sj n_d (dr_i/dx_d)^+ (re-ordered to the (-) side),  s3 = sj sigma.
+//
+// This unit holds the trace / flux kernels and their launchers.  The descriptor structs the kernels read and FaceHost, the set-up's
+// findings per plan, are in d4est_hip_faces_host.h; d4est_hip_faces_setup.hip builds them, d4est_hip_faces_geometry.hip fills the
+// geometric factors and the boundary data.
 #include <algorithm>
-#include <map>
-#include <tuple>
 
-#include "d4est_hip_internal.h"
-#include "d4est_hip_topology.h"
+#include "d4est_hip_faces_host.h"
 #include "d4est_hip_maps.h"
 #include "d4est_hip_penalty.h"
-#include "d4est_hip_tables.h"
 #include "d4est_hip_wave.h"
 
 namespace d4est_hip {
-
-struct SideDesc {
-  int kind;           // 0 boundary, 1 interface with local (+), 2 interface with ghost (+)
-  int code;           // flip0 | flip1<<1 | transpose<<2   (dGMath/d4est_operators.c:2031-2081)
-  int NQ;             // mortar quadrature nodes/dir
-  int offC;           // (NQ x N)  side nodes -> mortar quadrature nodes (p-prolong then Lobatto->quadrature)
-  int offCD;          // (NQ x N)  C * D: tangential derivative fused with the interpolation (fast trace kernel)
-  int pad0;
-  int offE;           // (N x NQ)  mortar quadrature -> side operator (P^T I^T W)
-  int geom;           // scalar stride S of the side (face_geom at 7*S; Dirichlet data at S)
-  long long qoff;     // offset of this side's mortar-node trace block (4 T doubles) in the local buffer
-  long long nbr_qoff; // offset of the (+) side's block (local buffer for kind 1, ghost buffer for kind 2)
-};
-
-struct ElemDesc {
-  int N;     // nodes per direction
-  int ns;    // nodal stride
-  int offD;  // offset of the zero-padded 8 x 8 (fast path) or N x N (generic) derivative matrix inside face_ops
-  int pad;
-};
-
-// uniform plans (one degree, one mortar degree, contiguous strides): the trace kernel computes its addresses instead of loading
-// descriptors, which removes one dependent global-load latency from every workgroup (the kernel is latency bound)
-struct TraceUniform {
-  int N, NQ, offC, offCD, offD, ns0, ns_stride, pad;  // N == 0: not uniform
-  long long q0, q_stride;                              // qoff of side s = q0 + s * q_stride
-};
-
-struct GhostSideDesc {
-  int N;       // nodes/dir of the ghost element
-  int f;       // its face
-  int NQ;
-  int offC;    // (NQ x N)
-  int offD;    // N x N
-  int pad;
-  long long u_off;  // offset of the ghost element in the packed ghost vector
-  long long goff;   // offset of the block in the ghost trace buffer
-};
-
-
-// volume index of face node (a,b) of face f (a fastest; tangential axes in increasing order)
-__device__ inline int face_vol_index(int f, int N, int a, int b) {
-  const int dir = f >> 1, fix = face_fix(f, N);
-  if (dir == 0) return fix + N * (a + N * b);
-  if (dir == 1) return a + N * (fix + N * b);
-  return a + N * (b + N * fix);
-}
 
 // value c (0: u, 1..3: du/dr_{c-1}) at face node (a,b) of face f from the element values ue (N^3, x fastest)
 __device__ inline double nodal_trace(const double* ue, const double* D /* row-major, leading dim ldD */, int ldD, int N, int f,
@@ -175,65 +128,6 @@ __global__ __launch_bounds__(256) void ghost_trace_kernel(const double* __restri
   }
 }
 
-// Dirichlet data: Lobatto face nodes -> mortar quadrature nodes (d4est_laplacian_flux_sipg.c:80-107), set-up time
-__global__ __launch_bounds__(64) void bndry_interp_kernel(const double* __restrict__ g_lobatto, double* __restrict__ g_quad,
-                                                          const SideDesc* __restrict__ sd, const ElemDesc* __restrict__ ed,
-                                                          const int* __restrict__ side_bndry_stride,
-                                                          const double* __restrict__ face_ops, int n_sides) {
-  for (int s = blockIdx.x; s < n_sides; s += gridDim.x) {
-    const SideDesc d = sd[s];
-    if (d.kind != 0) continue;
-    const int N = ed[s / 6].N, NQ = d.NQ;
-    const double* C = face_ops + d.offC;
-    const double* g = g_lobatto + side_bndry_stride[s];
-    for (int k = threadIdx.x; k < NQ * NQ; k += blockDim.x) {
-      const int ap = k % NQ, bp = k / NQ;
-      double v = 0.0;
-      for (int b = 0; b < N; ++b) {
-        double r = 0.0;
-        for (int a = 0; a < N; ++a) r = fma(C[ap * N + a], g[a + N * b], r);
-        v = fma(C[bp * N + b], r, v);
-      }
-      g_quad[d.geom + k] = v;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// set-up: 7 combined geometric factors per mortar quadrature node
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void face_geom_kernel(const SideDesc* __restrict__ sd, const int* __restrict__ side_deg_m,
-                                                       const int* __restrict__ side_deg_p, int n_sides,
-                                                       const double* __restrict__ sj, const double* __restrict__ nrm,
-                                                       const double* __restrict__ drst_m, const double* __restrict__ drst_p,
-                                                       const double* __restrict__ hm, const double* __restrict__ hp,
-                                                       double prefactor, int fcn, double* __restrict__ geom) {
-  for (int s = blockIdx.x; s < n_sides; s += gridDim.x) {
-    const SideDesc d = sd[s];
-    const int NQ = d.NQ, T = NQ * NQ;
-    const size_t S = (size_t)d.geom;
-    for (int k = threadIdx.x; k < T; k += blockDim.x) {
-      const int a = k % NQ, b = k / NQ;
-      const int kp = (d.kind == 0) ? k : reorder_index(d.code, NQ - 1, a, b);
-      const double sjk = sj[S + k];
-      double sn[3];
-      for (int x = 0; x < 3; ++x) sn[x] = sjk * nrm[3 * S + (size_t)x * T + k];
-      for (int i = 0; i < 3; ++i) {
-        double am = 0.0, ap = 0.0;
-        for (int x = 0; x < 3; ++x) {
-          am += sn[x] * drst_m[9 * S + (size_t)(i + 3 * x) * T + k];
-          if (d.kind != 0) ap += sn[x] * drst_p[9 * S + (size_t)(i + 3 * x) * T + kp];
-        }
-        geom[7 * S + (size_t)i * T + k] = am;
-        geom[7 * S + (size_t)(3 + i) * T + k] = ap;
-      }
-      const int dm = side_deg_m[s], dp = (d.kind == 0) ? dm : side_deg_p[s];
-      const double hpk = (d.kind == 0) ? hm[S + k] : hp[S + k];
-      geom[7 * S + (size_t)6 * T + k] = sjk * sipg_penalty(fcn, dm, hm[S + k], dp, hpk, prefactor);
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------
 // (2) generic flux kernel: any degree, one 256-thread workgroup per element, sides in sequence
 // ---------------------------------------------------------------------------
@@ -325,28 +219,6 @@ __global__ __launch_bounds__(256) void flux_generic_kernel(const double* __restr
 // element's, hence the factors fm / fp = 1/2 on the big element's gradient and w2 = 1/2 on the big side's term 2
 // (d4est_laplacian_flux.c:905-915, d4est_laplacian_flux_sipg.c:806-808).
 // ---------------------------------------------------------------------------
-struct HpMortar {
-  int elem, face;
-  int kind;          // 0 boundary, 1 interface with a local (+) element, 2 with a ghost (+) element
-  int code;          // reorder code applied when reading the (+) block
-  int N, NQ;         // side nodes / mortar quadrature nodes per direction
-  int offCa, offCb;  // (NQ x N) side -> mortar quadrature nodes along the face axes a, b (hp_ops)
-  int offCDa, offCDb; // C . D: tangential derivative fused with the interpolation (MFMA kernels)
-  int offEa, offEb;  // (N x NQ) mortar quadrature nodes -> side
-  int first, last;   // first / last record of its side
-  int gidx;          // scalar index of the mortar's first node in the precombined geometry / boundary arrays (S + off)
-  int u_shift;       // offset (doubles) from the (+) block to the block whose u field this mortar reads; 0 except on a small side whose
-                     // face pair the reference re-orients non-geometrically (see faces_setup_hp)
-  double fm, fp, w2; // hanging-face factors (set-up only: face_geom_hp_kernel folds them into the geometric factors; w2 = fm)
-  double hang;       // side_hang of the record's side as a number (0 conforming, 1 big, 2 small): lets the tiled kernels serve the hanging sides only (hp split)
-  long long qoff, nbr_qoff;
-};
-
-struct HpGeomSrc {   // where the record's factors sit in the reference-layout arrays (set-up only)
-  int S, off, Ttot, off_p;
-  int deg_m, deg_p, pad0, pad1;
-};
-
 // out (rows x rows) = (opb (x) opa) in (cols x cols): opa contracts the fast face index a, opb the slow index b
 __device__ inline void apply2d_ab(const double* __restrict__ opa, const double* __restrict__ opb, int rows, int cols, const double* in,
                                   double* tmp, double* out, int nfields, int in_stride, int out_stride, int tmp_stride, bool accumulate) {
@@ -398,41 +270,6 @@ __global__ __launch_bounds__(256) void trace_hp_kernel(const double* __restrict_
       apply2d_ab(hp_ops + m.offCa, hp_ops + m.offCb, NQ, N, A, tmp, Q, 4, fld_stride, fld_stride, fld_stride, false);
       for (int idx = threadIdx.x; idx < 4 * T; idx += blockDim.x) qtrace[m.qoff + idx] = Q[(idx / T) * fld_stride + idx % T];
       __syncthreads();
-    }
-  }
-}
-
-__global__ __launch_bounds__(64) void face_geom_hp_kernel(const HpMortar* __restrict__ md, const HpGeomSrc* __restrict__ gs, int n_rec,
-                                                          const double* __restrict__ sj, const double* __restrict__ nrm,
-                                                          const double* __restrict__ drst_m, const double* __restrict__ drst_p,
-                                                          const double* __restrict__ hm, const double* __restrict__ hp,
-                                                          double prefactor, int fcn, double* __restrict__ geom) {
-  for (int r = blockIdx.x; r < n_rec; r += gridDim.x) {
-    const HpMortar m = md[r];
-    const HpGeomSrc g = gs[r];
-    const int NQ = m.NQ, T = NQ * NQ;
-    const size_t S = (size_t)g.S, TT = (size_t)g.Ttot;
-    for (int k = threadIdx.x; k < T; k += blockDim.x) {
-      const int a = k % NQ, b = k / NQ;
-      const int kp = (m.kind == 0) ? k : reorder_index(m.code, NQ - 1, a, b);
-      const double sjk = sj[S + g.off + k];
-      double sn[3];
-      for (int x = 0; x < 3; ++x) sn[x] = sjk * nrm[3 * S + (size_t)x * TT + g.off + k];
-      for (int i = 0; i < 3; ++i) {
-        double am = 0.0, ap = 0.0;
-        for (int x = 0; x < 3; ++x) {
-          am += sn[x] * drst_m[9 * S + (size_t)(i + 3 * x) * TT + g.off + k];
-          // (+) side factors are stored in the (+) side's sub-mortar order and orientation (d4est_laplacian_flux.c:858-900)
-          if (m.kind != 0) ap += sn[x] * drst_p[9 * S + (size_t)(i + 3 * x) * TT + g.off_p + kp];
-        }
-        // the hanging-face factors of the reference (d4est_laplacian_flux.c:907-915: x 0.5 on the big element's gradient and term 2 on
-        // its half-size mortars, x 0.5 on the big element's gradient seen from a small side) are folded in here -- exact scalings --,
-        // so that a record's SIPG terms read like a conforming side's and a small side can go to the conforming flux kernel (hp split)
-        geom[7 * (size_t)m.gidx + (size_t)i * T + k] = m.fm * am;
-        geom[7 * (size_t)m.gidx + (size_t)(3 + i) * T + k] = m.fp * ap;
-      }
-      const double hmk = hm[S + g.off + k], hpk = (m.kind == 0) ? hmk : hp[S + g.off + k];
-      geom[7 * (size_t)m.gidx + (size_t)6 * T + k] = sjk * sipg_penalty(fcn, g.deg_m, hmk, (m.kind == 0) ? g.deg_m : g.deg_p, hpk, prefactor);
     }
   }
 }
@@ -1644,8 +1481,6 @@ __global__ __launch_bounds__(192) void flux_hp_mfma16_kernel(const double* __res
 // (13.8 + 22.7 us per apply at level 4, p = 7, 350 listed elements: pure latency).  Same arithmetic per record; the four sub-mortar
 // contributions of a big side meet in LDS and are summed in record order (deterministic).
 // ---------------------------------------------------------------------------
-struct HangUnit { int e, f, r0, nrec; };
-
 __global__ __launch_bounds__(256) void trace_unit_kernel(const double* __restrict__ u, double* __restrict__ qtrace,
                                                          const HpMortar* __restrict__ md, const HangUnit* __restrict__ units,
                                                          const ElemDesc* __restrict__ ed, const double* __restrict__ face_ops,
@@ -1952,1355 +1787,9 @@ __global__ __launch_bounds__(256) void flux_unit_kernel(const double* __restrict
 }
 
 // ---------------------------------------------------------------------------
-// host side
+// launch section (the host set-up that produces what these launchers read: d4est_hip_faces_setup.hip; the geometry and
+// boundary-data setters: d4est_hip_faces_geometry.hip)
 // ---------------------------------------------------------------------------
-namespace {
-
-struct FaceHost {
-  TraceUniform uni{};            // N == 0: descriptors are loaded
-  // hanging-mesh (mortar record) path
-  bool hp = false;
-  int n_rec = 0;
-  HpMortar* d_rec = nullptr;
-  HpGeomSrc* d_gsrc = nullptr;
-  int* d_elem_first = nullptr;
-  int* d_side_first = nullptr;   // first record of side s (6 n_elements + 1 entries)
-  int hp_max_N = 1, hp_max_NQ = 1;
-  // hp split (deg, deg_quad <= 7): the fast conforming kernels serve every conforming (and small hanging) side of the mesh, the mortar-record
-  // kernels only the hanging sides of the elements that have one (d_hang_elems)
-  bool hp_split = false;
-  bool hp_split_fast = false;    // ... and every degree <= 7: the p <= 7 kernels take every conforming side; else the tiled 16 x 16 kernels (or both
-                                 // families on lists: family_split) do
-  int* d_hang_elems = nullptr;
-  int n_hang_elems = 0;
-  HangUnit* d_units = nullptr;   // the sides of the listed elements that stay with the records, element by element (trace_unit_kernel / flux_unit_kernel)
-  int* d_unit_first = nullptr;   // per listed element: its first unit (n_hang_elems + 1 entries)
-  int n_units = 0;
-  std::vector<HpMortar> rec_host;   // host copy of the records (set-up of the split)
-  std::vector<HpGeomSrc> gsrc_host;  // host copy of the records' factor sources (set-up of the estimator)
-  int* d_is_bndry = nullptr;         // 1 per boundary side (launch_boundary_gather; uploaded on first use)
-  std::vector<SideDesc> sd_host;     // host copy of the side descriptors as faces_setup built them, before the hp split (the same)
-  double* d_hp_ops = nullptr;
-  int hp_fld_stride = 0;
-  size_t hp_lds_doubles = 0;
-  double* d_sj = nullptr;       // raw sj (for Robin data)
-  double* d_robin_c = nullptr;  // sj * coeff, sj * rhs at the mortar nodes of the boundary sides
-  double* d_robin_r = nullptr;
-  bool robin = false;
-  bool dirichlet_nonzero = false;   // non-zero Dirichlet data sits in d_bndry (it survives a Robin on / off cycle)
-  std::vector<int> side_deg_m, side_deg_p;
-  int* d_side_deg_m = nullptr;
-  int* d_side_deg_p = nullptr;
-  int* d_side_bndry_stride = nullptr;
-  GhostSideDesc* d_ghost_sides = nullptr;
-  int n_ghost_sides = 0;
-  int fld_stride = 0;   // generic kernels: doubles per field buffer
-  int max_N = 1, max_NQ = 1;
-  int max_local_N = 1;   // largest deg + 1 among the plan's own elements (sizes the LDS copy of u in trace_mfma16_kernel)
-  ElemDesc* d_elem_desc_generic = nullptr;  // offD -> unpadded N x N matrices
-  // family split (conforming mixed-degree plans with degrees above 7): the elements whose own degree and six mortars all fit 8 x 8 go
-  // through the p <= 7 kernels (trace_mfma_kernel / flux_wave_kernel, 2 - 3 x faster per element than the tiled 16 x 16 kernels), the
-  // rest through the tiled ones; both families write the same trace array and add into the same A u
-  bool family_split = false;
-  int *d_fam_small = nullptr, *d_fam_big = nullptr;
-  int n_fam_small = 0, n_fam_big = 0;
-  // ... and the hybrid operator's ring / dirty lists of such a plan, split the same way (the list launches of the two families; without them
-  // a listed launch sends every listed element through the tiled kernels: level 5, graded p = 3 ... 9, ring traces 396 us)
-  const int *hy_ring = nullptr, *hy_dirty = nullptr;   // the hybrid operator's device lists these belong to (matched by pointer)
-  const int* hy_dirty_any = nullptr;                   // the hybrid operator's dirty list, family split or not (a fused update may ride on it)
-  int *d_ring_small = nullptr, *d_ring_big = nullptr, *d_dirty_small = nullptr, *d_dirty_big = nullptr;
-  int n_ring_small = 0, n_ring_big = 0, n_dirty_small = 0, n_dirty_big = 0;
-};
-std::map<d4est_hip_plan*, FaceHost> g_face_host;
-
-template <typename T>
-T* upload_vec(const std::vector<T>& v) {
-  T* d = nullptr;
-  HIP_CHECK(hipMalloc(&d, std::max<size_t>(v.size(), 1) * sizeof(T)));
-  if (!v.empty()) HIP_CHECK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return d;
-}
-
-}  // namespace
-
-// dGMath/d4est_reference.c:3-12, :84-110: index, in the (+) side's own order, of the sub-face that is i in (-) order
-int reorient_face_order(int f_m, int f_p, int o, int i) {
-  using namespace topo;   // d4est_hip_topology.h: the tables, pinned entry by entry to the reference's own by tests/test_topology_tables.py
-  return d4est_perm_to_order[d4est_code_to_perm[d4est_FToF_code[f_m][f_p]][o]][i];
-}
-
-// The (flip0, flip1, transpose) code d4est_operators_reorient_face_data derives from a tree-boundary face pair
-// (dGMath/d4est_operators.c:2031-2050): p8est's face transform of the pair (lower face number, higher face number, orientation)
-// -- axes of the lower face's tangential directions, the axes they map to, and whether each is reversed
-// (p4est_expand_face_transform: my_axis = ft[0..2], target_axis = ft[3..5], edge_reverse = ft[6..8]).
-int face_reorder_code(int f_m, int f_p, int o) {
-  const auto& refs = topo::face_permutation_refs;
-  const int* ref0 = refs[0];
-  const int lo = f_m <= f_p ? f_m : f_p, hi = f_m <= f_p ? f_p : f_m;
-  int my_axis[2], target_axis[2], edge_reverse[2];
-  my_axis[0] = lo < 2 ? 1 : 0;
-  my_axis[1] = lo < 4 ? 2 : 1;
-  const int swap_axes = ref0[lo] ^ ref0[hi] ^ ((o == 0 || o == 3) ? 1 : 0);
-  target_axis[swap_axes] = hi < 2 ? 1 : 0;
-  target_axis[!swap_axes] = hi < 4 ? 2 : 1;
-  const int swap_rev = (refs[lo][hi] == 1);
-  edge_reverse[swap_rev] = o & 1;
-  edge_reverse[!swap_rev] = o >> 1;
-  const int aligned = (my_axis[1] - my_axis[0]) * (target_axis[1] - target_axis[0]) > 0;
-  return edge_reverse[0] | (edge_reverse[1] << 1) | ((!aligned) << 2);
-}
-
-// Small side of a hanging face, sub-face c in its own (= (-)) order.  The reference slices the WHOLE big face, re-orients it with the
-// (flip0, flip1, transpose) code and hp-prolongs the result onto child c (dGMath/d4est_laplacian_flux.c:575-657): u on sub-mortar c
-// comes from the big element's own child that the code maps onto c.  The gradient comes from the child
-// d4est_reference_reorient_face_order names (:733-830, :858-900).  The two agree whenever the code is the geometric map between the
-// faces; for a transposed pair with exactly one flip seen from the lower-numbered face (codes 5, 6) the reference's re-orientation is
-// not geometric (forest.reference_reorientation_is_consistent) and they differ -- followed here as the reference computes it.
-static int small_side_u_child(int code, int c) {
-  int ha = (code & 4) ? (c >> 1) : (c & 1), hb = (code & 4) ? (c & 1) : (c >> 1);
-  if (code & 2) hb ^= 1;
-  if (code & 1) ha ^= 1;
-  return ha + 2 * hb;
-}
-static const char* kNonGeometricMsg =
-    "the reference's re-orientation of this tree-face pair is not geometric (transposed with one flip, seen from the lower face)";
-
-// Mortar records of a mesh with hanging faces (plan->side_hang etc. set by d4est_hip_plan_set_hanging).
-static void faces_setup_hp(d4est_hip_plan* plan, FaceHost& fh) {
-  const int ne = plan->n_elements;
-  const int qt = plan->quad_type;
-  std::vector<double> ops;
-  std::map<std::tuple<int, int, int, int, int>, int> op_index;
-  // C: side (deg_side) -> mortar quadrature nodes (deg_mq); child = -1: p-prolong, 0/1: hp-prolong onto that half
-  auto get_C = [&](int deg_side, int deg_mq, int child) {
-    auto key = std::make_tuple(0, deg_side, deg_mq, child, 0);
-    auto it = op_index.find(key);
-    if (it != op_index.end()) return it->second;
-    const int nh = deg_mq + 1, nH = deg_side + 1;
-    std::vector<double> P;
-    if (child < 0) P = Tables1D::p_prolong(deg_side, deg_mq);
-    else {
-      std::vector<double> P2 = Tables1D::hp_prolong(deg_side, deg_mq);
-      P.assign(P2.begin() + (size_t)child * nh * nH, P2.begin() + (size_t)(child + 1) * nh * nH);
-    }
-    std::vector<double> I = Tables1D::quad_interp(qt, deg_mq, deg_mq);
-    std::vector<double> C = Tables1D::matmul(I, P, nh, nh, nH);
-    const int off = (int)ops.size();
-    ops.insert(ops.end(), C.begin(), C.end());
-    op_index[key] = off;
-    return off;
-  };
-  auto get_CD = [&](int deg_side, int deg_mq, int child) {
-    auto key = std::make_tuple(2, deg_side, deg_mq, child, 0);
-    auto it = op_index.find(key);
-    if (it != op_index.end()) return it->second;
-    const int offC = get_C(deg_side, deg_mq, child);
-    std::vector<double> C(ops.begin() + offC, ops.begin() + offC + (size_t)(deg_mq + 1) * (deg_side + 1));
-    std::vector<double> CD = Tables1D::matmul(C, Tables1D::dij(deg_side), deg_mq + 1, deg_side + 1, deg_side + 1);
-    const int off = (int)ops.size();
-    ops.insert(ops.end(), CD.begin(), CD.end());
-    op_index[key] = off;
-    return off;
-  };
-  // E: mortar quadrature nodes (deg_mq) -> Lobatto nodes of deg_ml (V^T W) -> side (p- or hp-prolong transposed)
-  auto get_E = [&](int deg_m, int deg_ml, int deg_mq, int child) {
-    auto key = std::make_tuple(1, deg_m, deg_ml, deg_mq, child);
-    auto it = op_index.find(key);
-    if (it != op_index.end()) return it->second;
-    std::vector<double> I = Tables1D::quad_interp(qt, deg_ml, deg_mq);
-    std::vector<double> w = Tables1D::quad_weights(qt, deg_mq);
-    std::vector<double> ItW = Tables1D::transpose(I, deg_mq + 1, deg_ml + 1);
-    for (int r = 0; r <= deg_ml; ++r)
-      for (int c = 0; c <= deg_mq; ++c) ItW[(size_t)r * (deg_mq + 1) + c] *= w[c];
-    const int nh = deg_ml + 1, nH = deg_m + 1;
-    std::vector<double> P;
-    if (child < 0) P = Tables1D::p_prolong(deg_m, deg_ml);
-    else {
-      std::vector<double> P2 = Tables1D::hp_prolong(deg_m, deg_ml);
-      P.assign(P2.begin() + (size_t)child * nh * nH, P2.begin() + (size_t)(child + 1) * nh * nH);
-    }
-    std::vector<double> Pt = Tables1D::transpose(P, nh, nH);
-    std::vector<double> E = Tables1D::matmul(Pt, ItW, nH, nh, deg_mq + 1);
-    const int off = (int)ops.size();
-    ops.insert(ops.end(), E.begin(), E.end());
-    op_index[key] = off;
-    return off;
-  };
-  const size_t ns = 6 * (size_t)ne;
-  // element references: >= 0 local, <= -2 ghost g = -(ref + 2)
-  auto valid_ref = [&](int ref) { return (ref >= 0 && ref < ne) || (ref <= -2 && -(ref + 2) < plan->n_ghost); };
-  auto deg_of = [&](int ref) { return ref >= 0 ? plan->deg[ref] : plan->ghost_deg[-(ref + 2)]; };
-  auto degq_of = [&](int ref) { return ref >= 0 ? plan->deg_quad[ref] : plan->ghost_deg_quad[-(ref + 2)]; };
-  auto degq_mortar = [&](int em, int ep) { return std::max(degq_of(em), degq_of(ep)); };
-  auto nodes2 = [](int deg) { return (deg + 1) * (deg + 1); };
-  std::vector<HpMortar> rec;
-  std::vector<HpGeomSrc> gsrc;
-  std::vector<int> elem_first(ne + 1, 0), side_first(ns, 0);
-  long long qoff = 0;
-  int max_fld = 1, maxN = 1;
-  for (int e = 0; e < ne; ++e) {
-    elem_first[e] = (int)rec.size();
-    const int deg_m = plan->deg[e], degq_m = plan->deg_quad[e];
-    maxN = std::max(maxN, deg_m + 1);
-    for (int f = 0; f < 6; ++f) {
-      const size_t s = 6 * (size_t)e + f;
-      side_first[s] = (int)rec.size();
-      plan->trace_offset[s] = qoff;
-      const int hang = plan->side_hang[s], nbr = plan->side_nbr[s], f_p = plan->side_nbr_face[s], o = plan->side_orientation[s];
-      if (hang < 0 || hang > 2) D4EST_HIP_ABORT("plan_set_hanging: side %zu has side_hang %d", s, hang);
-      if (o < 0 || o > 3) D4EST_HIP_ABORT("plan_set_hanging: side %zu has orientation %d", s, o);
-      const int n_sub = (hang == 1) ? 4 : 1;
-      const int* n4 = &plan->side_nbr4[4 * s];
-      if (hang != 0)
-        for (int i = 0; i < 4; ++i)
-          if (!valid_ref(n4[i])) D4EST_HIP_ABORT("plan_set_hanging: side %zu: side_nbr4[%d] = %d is neither a local nor a ghost element", s, i, n4[i]);
-      if (hang == 2 && !valid_ref(nbr)) D4EST_HIP_ABORT("plan_set_hanging: small side %zu: (+) element %d is neither local nor ghost", s, nbr);
-      // mortar sizes of the whole hanging face, in (-) order and in (+) order
-      int T_m[4] = {0, 0, 0, 0}, T_p[4] = {0, 0, 0, 0};
-      if (hang != 0) {
-        for (int i = 0; i < 4; ++i) {
-          T_m[i] = nodes2(hang == 1 ? degq_mortar(e, n4[i]) : degq_mortar(n4[i], nbr));
-          T_p[reorient_face_order(f, f_p, o, i)] = T_m[i];
-        }
-      }
-      for (int i = 0; i < n_sub; ++i) {
-        HpMortar m{};
-        HpGeomSrc g{};
-        m.elem = e;
-        m.face = f;
-        m.code = plan->side_reorder[s];
-        m.N = deg_m + 1;
-        m.first = (i == 0);
-        m.last = (i == n_sub - 1);
-        m.fm = m.fp = m.w2 = 1.0;
-        m.hang = (double)hang;
-        int ep = -1, sub_m = 0;   // (+) element of this mortar; index of the mortar in the face's (-) order
-        if (hang == 0) {
-          if (nbr != -1 && !valid_ref(nbr)) D4EST_HIP_ABORT("plan_set_faces: side %zu neighbour %d out of range", s, nbr);
-          m.kind = (nbr == -1) ? 0 : 1;
-          ep = nbr;
-        } else if (hang == 1) {
-          m.kind = 1;
-          ep = n4[i];
-          sub_m = i;
-          m.fm = 0.5;   // the big element's gradient on the half-size mortar
-          m.w2 = 0.5;
-        } else {
-          m.kind = 1;
-          ep = nbr;
-          sub_m = plan->side_sub[s];
-          if (sub_m < 0 || sub_m > 3 || n4[sub_m] != e) D4EST_HIP_ABORT("plan_set_hanging: small side %zu: side_sub %d does not point at the element in side_nbr4", s, sub_m);
-          m.fp = 0.5;
-        }
-        if (m.kind != 0 && ep <= -2) m.kind = 2;
-        const int deg_p = (m.kind == 0) ? deg_m : deg_of(ep);
-        const int deg_mq = (m.kind == 0) ? degq_m : degq_mortar(e, ep);
-        const int deg_ml = std::max(deg_m, deg_p);
-        m.NQ = deg_mq + 1;
-        const int ca = (hang == 1) ? (i & 1) : -1, cb = (hang == 1) ? (i >> 1) : -1;
-        m.offCa = get_C(deg_m, deg_mq, ca);
-        m.offCb = get_C(deg_m, deg_mq, cb);
-        m.offCDa = get_CD(deg_m, deg_mq, ca);
-        m.offCDb = get_CD(deg_m, deg_mq, cb);
-        m.offEa = get_E(deg_m, deg_ml, deg_mq, ca);
-        m.offEb = get_E(deg_m, deg_ml, deg_mq, cb);
-        g.S = plan->side_mortar_stride[s];
-        g.off = 0;
-        g.off_p = 0;
-        g.Ttot = nodes2(deg_mq);
-        if (hang != 0) {
-          g.Ttot = T_m[0] + T_m[1] + T_m[2] + T_m[3];
-          for (int j = 0; j < sub_m; ++j) g.off += T_m[j];
-          const int sub_p = reorient_face_order(f, f_p, o, sub_m);
-          for (int j = 0; j < sub_p; ++j) g.off_p += T_p[j];
-        }
-        g.deg_m = deg_m;
-        g.deg_p = deg_p;
-        m.gidx = g.S + g.off;
-        if ((long long)m.gidx + nodes2(deg_mq) > plan->total_mortar_nodes) D4EST_HIP_ABORT("plan_set_faces: side %zu mortar data exceeds total_mortar_nodes", s);
-        m.qoff = qoff;
-        qoff += 4LL * nodes2(deg_mq);
-        max_fld = std::max(max_fld, std::max(m.NQ * m.NQ, m.NQ * m.N));
-        rec.push_back(m);
-        gsrc.push_back(g);
-      }
-    }
-  }
-  elem_first[ne] = (int)rec.size();
-  // (+) blocks: local ones by record lookup; ghost ones get consecutive slots of the ghost trace buffer in record order
-  long long goff = 0;
-  plan->rec_qoff.assign(rec.size(), 0);
-  plan->rec_goff.assign(rec.size(), -1);
-  plan->rec_len.assign(rec.size(), 0);
-  plan->side_first_rec.assign(side_first.begin(), side_first.end());
-  plan->side_first_rec.push_back((int)rec.size());
-  for (size_t r = 0; r < rec.size(); ++r) {
-    HpMortar& m = rec[r];
-    plan->rec_qoff[r] = m.qoff;
-    plan->rec_len[r] = 4 * m.NQ * m.NQ;
-    if (m.kind == 2) {
-      m.nbr_qoff = goff;
-      plan->rec_goff[r] = goff;
-      goff += 4LL * m.NQ * m.NQ;
-      const size_t sg = 6 * (size_t)m.elem + m.face;
-      if (plan->side_hang[sg] == 2 &&
-          small_side_u_child(m.code, plan->side_sub[sg]) != reorient_face_order(m.face, plan->side_nbr_face[sg], plan->side_orientation[sg], plan->side_sub[sg]))
-        D4EST_HIP_ABORT("plan_set_hanging: small side %zu: %s, and the big element is on another rank", sg, kNonGeometricMsg);
-      continue;
-    }
-    if (m.kind == 0) continue;
-    const size_t s = 6 * (size_t)m.elem + m.face;
-    const int hang = plan->side_hang[s], f_p = plan->side_nbr_face[s], o = plan->side_orientation[s];
-    int ep, sub_p = 0;
-    if (hang == 1) ep = plan->side_nbr4[4 * s + (int)(r - side_first[s])];
-    else ep = plan->side_nbr[s];
-    const size_t sp = 6 * (size_t)ep + f_p;
-    const int hang_p = plan->side_hang[sp];
-    if ((hang == 0 && hang_p != 0) || (hang == 1 && hang_p != 2) || (hang == 2 && hang_p != 1))
-      D4EST_HIP_ABORT("plan_set_hanging: sides %zu and %zu disagree about the hanging face", s, sp);
-    if (hang == 2) sub_p = reorient_face_order(m.face, f_p, o, plan->side_sub[s]);   // the big element's own sub-mortar index
-    const HpMortar& mp = rec[side_first[sp] + sub_p];
-    if (mp.NQ != m.NQ) D4EST_HIP_ABORT("plan_set_hanging: sides %zu and %zu disagree on the mortar degree", s, sp);
-    m.nbr_qoff = mp.qoff;
-    if (hang == 2) {
-      const int sub_u = small_side_u_child(m.code, plan->side_sub[s]);
-      if (sub_u != sub_p) {
-        const HpMortar& mu = rec[side_first[sp] + sub_u];
-        if (mu.NQ != m.NQ) D4EST_HIP_ABORT("plan_set_hanging: small side %zu: %s, and its sub-mortars have different quadrature degrees", s, kNonGeometricMsg);
-        m.u_shift = (int)(mu.qoff - mp.qoff);
-      }
-    }
-  }
-  plan->local_trace_doubles = qoff;
-  plan->ghost_trace_doubles = goff;
-  for (size_t s_ = 0; s_ < ns; ++s_) plan->ghost_trace_offset[s_] = plan->rec_goff[side_first[s_]];
-  max_fld = std::max(max_fld, maxN * maxN);
-  fh.hp = true;
-  fh.n_rec = (int)rec.size();
-  fh.hp_fld_stride = max_fld;
-  fh.hp_lds_doubles = (size_t)12 * max_fld + (size_t)maxN * maxN * maxN + (size_t)maxN * maxN;
-  if (fh.hp_lds_doubles * sizeof(double) > 160 * 1024) D4EST_HIP_ABORT("hanging-face kernels need %zu LDS doubles", fh.hp_lds_doubles);
-  fh.d_rec = upload_vec(rec);
-  fh.rec_host = rec;
-  fh.d_gsrc = upload_vec(gsrc);
-  fh.gsrc_host = gsrc;
-  fh.d_elem_first = upload_vec(elem_first);
-  {
-    std::vector<int> sf(side_first.begin(), side_first.end());
-    sf.push_back((int)rec.size());
-    fh.d_side_first = upload_vec(sf);
-  }
-  fh.hp_max_N = maxN;
-  fh.hp_max_NQ = 1;
-  for (const HpMortar& m_ : rec) fh.hp_max_NQ = std::max(fh.hp_max_NQ, m_.NQ);
-  fh.d_hp_ops = upload_vec(ops);
-  plan->face_fast = false;
-}
-
-void faces_setup(d4est_hip_plan* plan) {
-  FaceHost& fh = g_face_host[plan];
-  const int ne = plan->n_elements;
-  const int qt = plan->quad_type;
-  bool hp = false;
-  if (!plan->side_hang.empty())
-    for (int v : plan->side_hang) hp = hp || (v != 0);
-  std::vector<double> ops;
-  std::map<std::tuple<int, int, int, int>, int> op_index;  // (kind, deg_a, deg_b, deg_c) -> offset
-  auto get_C = [&](int deg_side, int deg_mq) {
-    auto key = std::make_tuple(0, deg_side, deg_mq, 0);
-    auto it = op_index.find(key);
-    if (it != op_index.end()) return it->second;
-    // p-prolong to the Lobatto nodes of degree deg_mq, then Lobatto -> quadrature nodes (d4est_laplacian_flux.c:635-694)
-    std::vector<double> P = Tables1D::p_prolong(deg_side, deg_mq);
-    std::vector<double> I = Tables1D::quad_interp(qt, deg_mq, deg_mq);
-    std::vector<double> C = Tables1D::matmul(I, P, deg_mq + 1, deg_mq + 1, deg_side + 1);
-    const int off = (int)ops.size();
-    ops.insert(ops.end(), C.begin(), C.end());
-    op_index[key] = off;
-    return off;
-  };
-  auto get_CD = [&](int deg_side, int deg_mq) {
-    auto key = std::make_tuple(4, deg_side, deg_mq, 0);
-    auto it = op_index.find(key);
-    if (it != op_index.end()) return it->second;
-    const int offC = get_C(deg_side, deg_mq);
-    std::vector<double> C(ops.begin() + offC, ops.begin() + offC + (size_t)(deg_mq + 1) * (deg_side + 1));
-    std::vector<double> CD = Tables1D::matmul(C, Tables1D::dij(deg_side), deg_mq + 1, deg_side + 1, deg_side + 1);
-    const int off = (int)ops.size();
-    ops.insert(ops.end(), CD.begin(), CD.end());
-    op_index[key] = off;
-    return off;
-  };
-  auto get_E = [&](int deg_m, int deg_ml, int deg_mq) {
-    auto key = std::make_tuple(1, deg_m, deg_ml, deg_mq);
-    auto it = op_index.find(key);
-    if (it != op_index.end()) return it->second;
-    // V^T W on the mortar (galerkin integral, deg_ml <- deg_mq) then P^T (deg_m <- deg_ml): sipg.c:641-734
-    std::vector<double> I = Tables1D::quad_interp(qt, deg_ml, deg_mq);              // (mq+1) x (ml+1)
-    std::vector<double> w = Tables1D::quad_weights(qt, deg_mq);
-    std::vector<double> ItW = Tables1D::transpose(I, deg_mq + 1, deg_ml + 1);       // (ml+1) x (mq+1)
-    for (int r = 0; r <= deg_ml; ++r)
-      for (int c = 0; c <= deg_mq; ++c) ItW[(size_t)r * (deg_mq + 1) + c] *= w[c];
-    std::vector<double> P = Tables1D::p_prolong(deg_m, deg_ml);                     // (ml+1) x (m+1)
-    std::vector<double> Pt = Tables1D::transpose(P, deg_ml + 1, deg_m + 1);         // (m+1) x (ml+1)
-    std::vector<double> E = Tables1D::matmul(Pt, ItW, deg_m + 1, deg_ml + 1, deg_mq + 1);
-    const int off = (int)ops.size();
-    ops.insert(ops.end(), E.begin(), E.end());
-    op_index[key] = off;
-    return off;
-  };
-  // derivative matrices: unpadded (generic kernels) and zero-padded 8 x 8 (fast path, degrees <= 7)
-  auto get_D = [&](int deg, bool padded) {
-    auto key = std::make_tuple(padded ? 3 : 2, deg, 0, 0);
-    auto it = op_index.find(key);
-    if (it != op_index.end()) return it->second;
-    std::vector<double> D = Tables1D::dij(deg);
-    const int n = deg + 1;
-    const int off = (int)ops.size();
-    if (!padded) {
-      ops.insert(ops.end(), D.begin(), D.end());
-    } else {
-      std::vector<double> P(64, 0.0);
-      for (int r = 0; r < n; ++r)
-        for (int c = 0; c < n; ++c) P[r * 8 + c] = D[(size_t)r * n + c];
-      ops.insert(ops.end(), P.begin(), P.end());
-    }
-    op_index[key] = off;
-    return off;
-  };
-
-  // per side sizes; the local trace block of side s is 4 T_s doubles in side order
-  const size_t ns = 6 * (size_t)ne;
-  std::vector<SideDesc> sd(ns);
-  fh.side_deg_m.assign(ns, 0);
-  fh.side_deg_p.assign(ns, 0);
-  plan->trace_offset.assign(ns, 0);
-  plan->ghost_trace_offset.assign(ns, -1);
-  std::vector<GhostSideDesc> gsides;
-  std::vector<long long> ghost_u_off(plan->n_ghost, 0);
-  {
-    long long o = 0;
-    for (int g = 0; g < plan->n_ghost; ++g) {
-      ghost_u_off[g] = o;
-      const long long n = plan->ghost_deg[g] + 1;
-      o += n * n * n;
-    }
-  }
-  long long qoff = 0, goff = 0;
-  // D4EST_HIP_TUNE_GHOST_ALIAS: every ghost side reads block 0 (a constant ghost trace, e.g. the zero trace of a Schwarz subdomain plan)
-  const bool ghost_alias = plan->tuning[D4EST_HIP_TUNE_GHOST_ALIAS] > 0 && !hp;
-  long long ghost_alias_len = 0;
-  int maxN = 1, maxNQ = 1, max_fld = 1;
-  bool fast = true;
-  for (int e = 0; e < ne; ++e) maxN = std::max(maxN, plan->deg[e] + 1);
-  for (int g = 0; g < plan->n_ghost; ++g) maxN = std::max(maxN, plan->ghost_deg[g] + 1);
-  // first pass: mortar degrees and offsets
-  std::vector<int> deg_mq_of(ns), deg_p_of(ns);
-  for (int e = 0; e < ne; ++e)
-    for (int f = 0; f < 6; ++f) {
-      const size_t s = 6 * (size_t)e + f;
-      const bool hanging = hp && plan->side_hang[s] != 0;
-      // hanging sides are served by the mortar records (descriptor kind 3); a SMALL side still gets the degrees of its mortar with the
-      // big element, so that the hp split can hand it to the conforming kernels (one mortar, p-prolongation only: it is one of theirs)
-      const int nbr = hanging ? ((plan->side_hang[s] == 2 && plan->side_nbr[s] != -1) ? plan->side_nbr[s] : -1) : plan->side_nbr[s];
-      const int deg_m = plan->deg[e], degq_m = plan->deg_quad[e];
-      int deg_p = deg_m, degq_p = degq_m;
-      if (nbr >= 0) {
-        if (nbr >= ne) D4EST_HIP_ABORT("plan_set_faces: side %zu neighbour %d out of range", s, nbr);
-        deg_p = plan->deg[nbr];
-        degq_p = plan->deg_quad[nbr];
-      } else if (nbr <= -2) {
-        const int g = -(nbr + 2);
-        if (g >= plan->n_ghost) D4EST_HIP_ABORT("plan_set_faces: side %zu ghost %d out of range", s, g);
-        deg_p = plan->ghost_deg[g];
-        degq_p = plan->ghost_deg_quad[g];
-      }
-      deg_mq_of[s] = (nbr == -1) ? degq_m : std::max(degq_m, degq_p);   // (max: also d4est's rule for a hanging face's mortars)
-      deg_p_of[s] = deg_p;
-      const long long T = (long long)(deg_mq_of[s] + 1) * (deg_mq_of[s] + 1);
-      plan->trace_offset[s] = qoff;
-      qoff += 4 * T;
-      maxNQ = std::max(maxNQ, deg_mq_of[s] + 1);
-    }
-  plan->local_trace_doubles = qoff;
-  fast = (maxN <= 8 && maxNQ <= 8);
-  for (int e = 0; e < ne; ++e)
-    for (int f = 0; f < 6; ++f) {
-      const size_t s = 6 * (size_t)e + f;
-      SideDesc d{};
-      const bool hanging = hp && plan->side_hang[s] != 0;
-      const int nbr = hanging ? -1 : plan->side_nbr[s];
-      const int deg_m = plan->deg[e], deg_p = deg_p_of[s], deg_mq = deg_mq_of[s];
-      const int deg_ml = std::max(deg_m, deg_p);
-      d.kind = hanging ? 3 : ((nbr == -1) ? 0 : (nbr >= 0 ? 1 : 2));
-      d.code = plan->side_reorder[s];
-      d.NQ = deg_mq + 1;
-      d.offC = get_C(deg_m, deg_mq);
-      d.offCD = get_CD(deg_m, deg_mq);
-      d.pad0 = 0;
-      d.offE = get_E(deg_m, d.kind == 0 ? deg_m : deg_ml, deg_mq);
-      d.geom = plan->side_mortar_stride[s];
-      d.qoff = plan->trace_offset[s];
-      d.nbr_qoff = 0;
-      if (d.kind == 1 && !hp) {
-        const size_t sp = 6 * (size_t)nbr + plan->side_nbr_face[s];
-        if (deg_mq_of[sp] != deg_mq) D4EST_HIP_ABORT("plan_set_faces: sides %zu and %zu disagree on the mortar degree (non-conforming mortar?)", s, sp);
-        d.nbr_qoff = plan->trace_offset[sp];
-      } else if (d.kind == 2 && !hp) {
-        const int g = -(nbr + 2);
-        plan->ghost_trace_offset[s] = goff;
-        d.nbr_qoff = goff;
-        GhostSideDesc gs{};
-        gs.N = plan->ghost_deg[g] + 1;
-        gs.f = plan->side_nbr_face[s];
-        gs.NQ = deg_mq + 1;
-        gs.offC = get_C(plan->ghost_deg[g], deg_mq);
-        gs.offD = get_D(plan->ghost_deg[g], false);
-        gs.u_off = ghost_u_off[g];
-        gs.goff = goff;
-        gsides.push_back(gs);
-        if (ghost_alias) ghost_alias_len = std::max(ghost_alias_len, 4LL * (deg_mq + 1) * (deg_mq + 1));
-        else goff += 4LL * (deg_mq + 1) * (deg_mq + 1);
-      }
-      sd[s] = d;
-      fh.side_deg_m[s] = deg_m;
-      fh.side_deg_p[s] = deg_p;
-      max_fld = std::max(max_fld, std::max(d.NQ * d.NQ, d.NQ * (deg_m + 1)));
-      max_fld = std::max(max_fld, d.NQ * (deg_p + 1));
-    }
-  plan->ghost_trace_doubles = ghost_alias ? ghost_alias_len : goff;   // (hanging plans: overwritten by faces_setup_hp)
-  max_fld = std::max(max_fld, maxN * maxN);
-  fh.fld_stride = max_fld;
-  fh.max_N = maxN;
-  fh.max_NQ = maxNQ;
-  fh.max_local_N = 1;
-  for (int e = 0; e < ne; ++e) fh.max_local_N = std::max(fh.max_local_N, plan->deg[e] + 1);
-  fh.n_ghost_sides = (int)gsides.size();
-  plan->face_fast = fast;
-  plan->max_face_lds_doubles = 12 * max_fld + maxN * maxN * maxN + maxN * maxN;
-  if ((size_t)plan->max_face_lds_doubles * sizeof(double) > 160 * 1024) D4EST_HIP_ABORT("face kernels need %d LDS doubles", plan->max_face_lds_doubles);
-
-  std::vector<ElemDesc> edv(ne), edg(ne);
-  for (int e = 0; e < ne; ++e) {
-    edv[e].N = edg[e].N = plan->deg[e] + 1;
-    edv[e].ns = edg[e].ns = plan->nodal_stride[e];
-    edg[e].offD = get_D(plan->deg[e], false);
-    edv[e].offD = (fast || plan->deg[e] + 1 <= 8) ? get_D(plan->deg[e], true) : edg[e].offD;
-    edv[e].pad = edg[e].pad = 0;
-  }
-  // uniform plan? (one degree, one mortar degree, contiguous element and trace strides)
-  fh.uni = TraceUniform{};
-  TraceUniform un{};
-  if (ne > 0 && !hp) {
-    bool uniform = true;
-    const int N0 = edv[0].N, n3 = N0 * N0 * N0;
-    for (int e = 0; e < ne && uniform; ++e) uniform = (edv[e].N == N0) && (edv[e].ns == edv[0].ns + e * n3);
-    const long long qs = 4LL * sd[0].NQ * sd[0].NQ;
-    for (size_t s_ = 0; s_ < ns && uniform; ++s_)
-      uniform = (sd[s_].NQ == sd[0].NQ) && (sd[s_].offC == sd[0].offC) && (sd[s_].offCD == sd[0].offCD) && (sd[s_].qoff == sd[0].qoff + (long long)s_ * qs);
-    if (uniform) {
-      un.N = N0; un.NQ = sd[0].NQ; un.offC = sd[0].offC; un.offCD = sd[0].offCD; un.offD = edv[0].offD;
-      un.ns0 = edv[0].ns; un.ns_stride = n3; un.q0 = sd[0].qoff; un.q_stride = qs;
-    }
-  }
-  if (fast) fh.uni = un;   // (the uniform forms of the trace kernels exist for N, NQ <= 8 only)
-  // the direct kernels (d4est_hip_direct.hip: one wavefront per element, deg_quad <= 7; d4est_hip_direct_mw.hip: one multi-wave
-  // workgroup per element, deg = deg_quad = 8 ... 15) take over apply_aij on uniform conforming plans whose sides all see the local degree
-  direct_destroy(plan);
-  if (un.N > 0) {
-    bool same = true;
-    for (size_t s_ = 0; s_ < ns && same; ++s_) same = (sd[s_].offE == sd[0].offE) && (deg_p_of[s_] == plan->deg[0]) && sd[s_].kind != 3;
-    if (same && sd[0].NQ >= un.N && (fast ? sd[0].NQ * sd[0].NQ <= 64 : true))
-      direct_setup(plan, un.N, sd[0].NQ, un.ns0, un.ns_stride, ops.data() + un.offC, ops.data() + un.offCD, ops.data() + sd[0].offE);
-  }
-  ops.resize(ops.size() + 64, 0.0);  // slack: the fast kernels read 64-entry images
-  plan->d_elem_desc = upload_vec(edv);
-  fh.d_elem_desc_generic = upload_vec(edg);
-  HIP_CHECK(hipMalloc(&plan->d_side_desc, std::max<size_t>(sd.size(), 1) * sizeof(SideDesc)));
-  if (!sd.empty()) HIP_CHECK(hipMemcpy(plan->d_side_desc, sd.data(), sd.size() * sizeof(SideDesc), hipMemcpyHostToDevice));
-  fh.sd_host = sd;
-  plan->d_face_ops = upload_vec(ops);
-  fh.d_side_deg_m = upload_vec(fh.side_deg_m);
-  fh.d_side_deg_p = upload_vec(fh.side_deg_p);
-  fh.d_side_bndry_stride = upload_vec(plan->side_bndry_stride);
-  fh.d_ghost_sides = upload_vec(gsides);
-  if (hp) faces_setup_hp(plan, fh);
-  // ---- hp split.  A mesh with hanging faces is mostly conforming (2:1 interfaces of a locally refined forest): where every degree is
-  // <= 7 the conforming sides go to the fast kernels of the conforming path (one wavefront per face, scalar-operand contractions) and
-  // only the hanging sides to the tiled mortar-record kernels, over the list of elements that have one.  Both families write the same
-  // trace array (offsets of the records: a conforming side's block is its single record's) and add into the same A u.  A hanging
-  // side keeps kind 3 in the conforming descriptors: the fast trace kernel fills its block with a pretend-conforming trace that the
-  // record kernel, launched after it, overwrites (the block is at least as long), the fast flux kernel reads zeros for it.
-  fh.hp_split = false;
-  (void)hipFree(fh.d_hang_elems); fh.d_hang_elems = nullptr; fh.n_hang_elems = 0;
-  (void)hipFree(fh.d_units); (void)hipFree(fh.d_unit_first); fh.d_units = nullptr; fh.d_unit_first = nullptr; fh.n_units = 0;
-  // (degrees above 7 -- round 4: the conforming sides then go through the tiled 16 x 16 conforming kernels, or, family split below, through
-  // both conforming families on lists; D4EST_HIP_HP_SPLIT_FAST_ONLY=1 keeps such plans on the record kernels throughout)
-  const bool split_fast = fast && fh.hp_max_N <= 8 && fh.hp_max_NQ <= 8;
-  const bool split_tiled = !split_fast && fh.hp_max_N <= 16 && fh.hp_max_NQ <= 16 && fh.max_N <= 16 && fh.max_NQ <= 16 && !std::getenv("D4EST_HIP_HP_SPLIT_FAST_ONLY");
-  fh.hp_split_fast = false;
-  if (hp && (split_fast || split_tiled) && plan->tuning[D4EST_HIP_TUNE_HP_SPLIT] != 0 &&
-      plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0 && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 1) {
-    std::vector<int> hang_elems;
-    std::vector<HpMortar> rec = fh.rec_host;
-    bool ok = true;
-    for (int e = 0; e < ne && ok; ++e) {
-      bool any = false;
-      for (int f = 0; f < 6; ++f) {
-        const size_t s_ = 6 * (size_t)e + f;
-        SideDesc& d = sd[s_];
-        d.qoff = plan->trace_offset[s_];
-        const int hang = plan->side_hang[s_];
-        if (hang == 2) {
-          // a small side: ONE mortar, its own trace p-prolonged to the mortar nodes, the (+) block = the big element's sub-mortar, the
-          // hanging factor folded into the geometric factors -- to the conforming kernels it is an ordinary interior side (unless
-          // the reference's non-geometric re-orientation shifts the block it reads u from: those stay with the record kernel)
-          HpMortar& m = rec[plan->side_first_rec[s_]];
-          if ((m.kind == 1 || m.kind == 2) && m.u_shift == 0 && m.NQ == d.NQ && plan->side_first_rec[s_ + 1] == plan->side_first_rec[s_] + 1) {
-            d.kind = m.kind;   // (2: the big element is a ghost -- its sub-mortar block arrives in the ghost trace buffer at the record's offset)
-            d.geom = m.gidx;
-            d.nbr_qoff = m.nbr_qoff;
-            m.hang = 0.0;   // (the record kernel skips it)
-            continue;
-          }
-        }
-        if (hang != 0) { any = true; continue; }
-        if (d.kind == 1) {
-          const size_t sp = 6 * (size_t)plan->side_nbr[s_] + plan->side_nbr_face[s_];
-          if (plan->side_hang[sp] != 0 || deg_mq_of[sp] != deg_mq_of[s_]) { ok = false; break; }
-          d.nbr_qoff = plan->trace_offset[sp];
-        } else if (d.kind == 2) {
-          // a conforming side against a ghost: the exchanged block sits where the side's (single) record expects it
-          const HpMortar& m = rec[plan->side_first_rec[s_]];
-          if (m.kind != 2 || m.NQ != d.NQ || m.u_shift != 0) { ok = false; break; }
-          d.nbr_qoff = m.nbr_qoff;
-        }
-      }
-      if (any) hang_elems.push_back(e);
-    }
-    // measured (level-4 brick, p = 7, every 64th / 32nd / 16th / 8th / 3rd octant refined): apply_aij 203 -> 139, 236 -> 170, 292 -> 210,
-    // 402 -> 292, 661 -> 448 us.  The record kernel's cost is per listed element (those with a BIG hanging side, or a small side the
-    // conforming kernels cannot take): should they ever be more than half of the mesh, the split is not taken (tuning value 1 forces it)
-    if (ok && plan->tuning[D4EST_HIP_TUNE_HP_SPLIT] < 0 && 2 * hang_elems.size() > (size_t)ne) ok = false;
-    if (ok) {
-      fh.hp_split = true;
-      fh.hp_split_fast = split_fast;
-      fh.n_hang_elems = (int)hang_elems.size();
-      fh.d_hang_elems = upload_vec(hang_elems);
-      // the units: per listed element its sides with a live record (D4EST_HIP_NO_HANG_UNITS=1 keeps the serial record kernels)
-      if (!std::getenv("D4EST_HIP_NO_HANG_UNITS")) {
-        std::vector<HangUnit> units;
-        std::vector<int> unit_first(1, 0);
-        bool units_ok = true;
-        for (int e : hang_elems) {
-          for (int f = 0; f < 6; ++f) {
-            const size_t s_ = 6 * (size_t)e + f;
-            const int r0 = plan->side_first_rec[s_], r1 = plan->side_first_rec[s_ + 1];
-            int live = 0;
-            for (int r = r0; r < r1; ++r) live += rec[r].hang != 0.0;
-            if (live == 0) continue;
-            if (live != r1 - r0 || r1 - r0 > 4) { units_ok = false; break; }
-            units.push_back(HangUnit{e, f, r0, r1 - r0});
-          }
-          unit_first.push_back((int)units.size());
-        }
-        if (units_ok && !units.empty()) {
-          fh.n_units = (int)units.size();
-          fh.d_units = upload_vec(units);
-          fh.d_unit_first = upload_vec(unit_first);
-        }
-      }
-      if (!sd.empty()) HIP_CHECK(hipMemcpy(plan->d_side_desc, sd.data(), sd.size() * sizeof(SideDesc), hipMemcpyHostToDevice));
-      if (!rec.empty()) HIP_CHECK(hipMemcpy(fh.d_rec, rec.data(), rec.size() * sizeof(HpMortar), hipMemcpyHostToDevice));
-    }
-  }
-  // ---- family split of a conforming mixed-degree plan whose largest degree is above 7 (see FaceHost)
-  fh.family_split = false;
-  (void)hipFree(fh.d_fam_small); (void)hipFree(fh.d_fam_big);
-  fh.d_fam_small = fh.d_fam_big = nullptr; fh.n_fam_small = fh.n_fam_big = 0;
-  if ((!hp || (fh.hp_split && !fh.hp_split_fast)) && !fast && ne > 0 && fh.max_N <= 16 && fh.max_NQ <= 16 && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0 &&
-      plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 1 && plan->tuning[D4EST_HIP_TUNE_GHOST_ALIAS] <= 0 && !std::getenv("D4EST_HIP_NO_FAMILY_SPLIT")) {
-    std::vector<int> small_e, big_e;
-    for (int e = 0; e < ne; ++e) {
-      bool sm = plan->deg[e] + 1 <= 8;
-      for (int f = 0; f < 6 && sm; ++f) {
-        const size_t s_ = 6 * (size_t)e + f;
-        sm = deg_mq_of[s_] + 1 <= 8 && deg_p_of[s_] + 1 <= 8;
-      }
-      (sm ? small_e : big_e).push_back(e);
-    }
-    if (!big_e.empty() && 2 * small_e.size() >= (size_t)ne) {
-      fh.family_split = true;
-      fh.d_fam_small = upload_vec(small_e); fh.n_fam_small = (int)small_e.size();
-      fh.d_fam_big = upload_vec(big_e); fh.n_fam_big = (int)big_e.size();
-    }
-  }
-  // ---- the hybrid operator (d4est_hip_direct.hip): on mixed-degree / locally refined plans the CLEAN elements -- deg_quad = deg with a
-  // one-kernel instance, all six sides conforming against a local element of the same degree or the boundary -- take the trace-free
-  // whole-operator kernels of their degree bucket; plans whose two-phase kernels have list forms.  One rank -- or, tuning value 2, a shard:
-  // ghost-aware form below (a uniform-degree shard, which has the direct tables too, then takes this path instead)
-  hybrid_destroy(plan);
-  (void)hipFree(fh.d_ring_small); (void)hipFree(fh.d_ring_big); (void)hipFree(fh.d_dirty_small); (void)hipFree(fh.d_dirty_big);
-  fh.d_ring_small = fh.d_ring_big = fh.d_dirty_small = fh.d_dirty_big = nullptr;
-  fh.n_ring_small = fh.n_ring_big = fh.n_dirty_small = fh.n_dirty_big = 0;
-  fh.hy_ring = fh.hy_dirty = fh.hy_dirty_any = nullptr;
-  // ghost-aware form (tuning value 2 on a plan with ghost sides; D4EST_HIP_HYBRID_NO_GHOST=1 switches it off): a conforming side against a
-  // ghost element of the same degree does not make a (one-wavefront, N <= 8) element dirty -- the kernel reads the (+) block from the ghost
-  // trace buffer (kind 4 -> kind 2 + DIRECT_KCF_GHOST).  The sender's trace kernel wrote that block at the mortar nodes in the sender's own
-  // face order; the READING kernel re-orients it with the side's side_reorder code, as the two-phase flux kernel and the uniform direct
-  // kernel do with a ghost block.  Race freedom by
-  // construction: such an element is in the ring, so the trace kernel -- never a clean kernel -- writes the block the exchange packs, and
-  // its own launch is queued on the plan's stream only after exchange phase 1 has returned there (apply_operator).  A ghost neighbour of
-  // another degree, a hanging face cut by the shard boundary and every ghost side of a p >= 8 element leave the element dirty.
-  const bool hy_ghost = plan->n_ghost > 0 && plan->tuning[D4EST_HIP_TUNE_HYBRID] == 2 && !std::getenv("D4EST_HIP_HYBRID_NO_GHOST");
-  if ((hy_ghost || (!plan->direct && plan->n_ghost == 0)) && ne > 0 && plan->tuning[D4EST_HIP_TUNE_HYBRID] != 0 && plan->tuning[D4EST_HIP_TUNE_GHOST_ALIAS] <= 0 &&
-      plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 0 && plan->tuning[D4EST_HIP_TUNE_FLUX_FAST] != 1 && (hp ? (fh.hp_split || (fh.hp_max_N <= 16 && fh.hp_max_NQ <= 16)) : (fast || (fh.max_N <= 16 && fh.max_NQ <= 16)))) {
-    std::vector<char> bucket_ok(plan->buckets.size(), 0), clean(ne, 0);
-    std::vector<int> bucket_of(ne, -1);
-    // hanging-aware form (hp split active): a hanging side does not make an element dirty -- the record kernels serve it (kind 3) or,
-    // a small side the split handed to the conforming kernels, the direct kernel reads the big element's sub-mortar block from the trace
-    // array and exports its own (kind 2); D4EST_HIP_HYBRID_NO_HANGING=1 keeps every element with a hanging side dirty
-    // (plans with degrees above 7 under the generalised hp split: the elements of the one-wavefront buckets, N <= 8, only -- the multi-wave
-    // whole-operator kernel has no hanging-aware instance)
-    const bool hang_aware = hp && fh.hp_split && !std::getenv("D4EST_HIP_HYBRID_NO_HANGING") && plan->local_trace_doubles < (1LL << 31);
-    // mixed-aware form: a conforming side against a local element of LOWER degree does not make the (one-wavefront) element dirty either --
-    // the mortar is the element's own (d4est's rule: the larger degree), its operators are the same-degree ones, and the (+) block, which the
-    // lower-degree neighbour's trace kernel interpolates up to that mortar, is read from the trace array like a ghost block (kind 2; the
-    // neighbour itself stays dirty: ITS side sees a mortar above its own degree).  D4EST_HIP_HYBRID_NO_MIXED=1 switches it off
-    const bool mixed_aware = (!hp || fh.hp_split) && !std::getenv("D4EST_HIP_HYBRID_NO_MIXED") && plan->local_trace_doubles < (1LL << 31);
-    std::vector<HybridSideOverride> ov;
-    if (hang_aware || mixed_aware || hy_ghost) ov.assign(ns, HybridSideOverride{-1, 0, 0, 0});
-    bool any_ov = false, any_hang_ov = false, any_mixed_ov = false;
-    for (size_t b = 0; b < plan->buckets.size(); ++b) {
-      const Bucket& bk = plan->buckets[b];
-      bucket_ok[b] = bk.N == bk.NQ && bk.d_EBf && hybrid_pair_built(bk.N, bk.NQ);
-      for (int i = 0; i < bk.n_elem; ++i) bucket_of[plan->elem_ids[bk.elem_offset + i]] = (int)b;
-    }
-    int n_clean = 0;
-    for (int e = 0; e < ne; ++e) {
-      if (bucket_of[e] < 0 || !bucket_ok[bucket_of[e]]) continue;
-      bool ok = true;
-      for (int f = 0; f < 6 && ok; ++f) {
-        const size_t s_ = 6 * (size_t)e + f;
-        if (hp && plan->side_hang[s_] != 0) {
-          if (!hang_aware || plan->buckets[bucket_of[e]].N > 8) { ok = false; break; }
-          // (a hanging face cut by the shard boundary: the two-phase kernels)
-          bool cut = plan->side_nbr[s_] <= -2;
-          if (plan->side_hang[s_] == 1 && !plan->side_nbr4.empty())
-            for (int k = 0; k < 4; ++k) cut = cut || plan->side_nbr4[4 * s_ + k] <= -2;
-          if (cut) { ok = false; break; }
-          const SideDesc& d = sd[s_];
-          if (d.kind == 3) { ov[s_] = HybridSideOverride{3, 0, 0, 0}; continue; }   // (the element is on the record kernels' list)
-          if (d.kind == 1 && plan->side_hang[s_] == 2 && d.NQ == plan->buckets[bucket_of[e]].NQ && deg_p_of[s_] == plan->deg[e]) {
-            ov[s_] = HybridSideOverride{2, d.nbr_qoff, (int)d.qoff, d.geom};
-            continue;
-          }
-          ok = false;
-          break;
-        }
-        const int nbr = plan->side_nbr[s_];
-        if (nbr == -1) continue;                                   // domain boundary
-        if (nbr < 0) {                                             // ghost: the ghost-aware form, or dirty
-          const int g = -(nbr + 2);
-          const Bucket& bk = plan->buckets[bucket_of[e]];
-          if (hy_ghost && bk.N <= 8 && g < plan->n_ghost && plan->ghost_deg[g] == plan->deg[e] && plan->ghost_deg_quad[g] == plan->deg_quad[e] &&
-              deg_mq_of[s_] == plan->deg_quad[e] && sd[s_].kind == 2 && sd[s_].NQ == bk.NQ && plan->ghost_trace_offset[s_] >= 0 &&
-              plan->ghost_trace_offset[s_] + 4LL * bk.NQ * bk.NQ <= plan->ghost_trace_doubles) {
-            ov[s_] = HybridSideOverride{4, plan->ghost_trace_offset[s_], -1, plan->side_mortar_stride[s_]};
-            continue;
-          }
-          ok = false;
-          break;
-        }
-        const size_t sp = 6 * (size_t)nbr + plan->side_nbr_face[s_];
-        if (mixed_aware && plan->buckets[bucket_of[e]].N <= 8 && plan->deg[nbr] < plan->deg[e] && plan->deg_quad[nbr] <= plan->deg_quad[e] &&
-            deg_mq_of[s_] == plan->deg_quad[e] && !(hp && plan->side_hang[sp] != 0) && sd[s_].kind == 1 && sd[s_].NQ == plan->buckets[bucket_of[e]].NQ) {
-          // (no export: the neighbour is dirty, so this element is in the ring and the trace kernel writes its block -- an export from the
-          // clean kernel could race with the dirty flux kernel reading that block on another stream)
-          ov[s_] = HybridSideOverride{2, sd[s_].nbr_qoff, -1, sd[s_].geom};
-          continue;
-        }
-        ok = plan->deg[nbr] == plan->deg[e] && plan->deg_quad[nbr] == plan->deg_quad[e] && deg_mq_of[s_] == plan->deg_quad[e] &&
-             !(hp && plan->side_hang[sp] != 0);
-      }
-      clean[e] = ok;
-      n_clean += ok;
-      if (ok && (hang_aware || mixed_aware || hy_ghost))
-        for (int f = 0; f < 6; ++f) {
-          const size_t s_ = 6 * (size_t)e + f;
-          if (ov[s_].kind < 0) continue;
-          any_ov = true;
-          if (ov[s_].kind == 4) continue;   // (ghost-aware: not part of the form's label)
-          if (hp && plan->side_hang[s_] != 0) any_hang_ov = true;
-          else any_mixed_ov = true;
-        }
-    }
-    // default: only where it was measured to pay -- ONE clean degree bucket holding at least half of the elements (a locally refined mesh of
-    // one degree: level 4, p = 7, every 64th octant refined 144 -> 125 us).  With several clean buckets every bucket is its own launch of
-    // a latency-structured kernel (25 - 40 us for a few hundred elements each, whatever their number): back to back they cost more than
-    // the two-phase kernels save, and on side streams the cross-queue event waits (about 50 us per fork / join on this runtime) eat the
-    // overlap (graded p = 3 ... 9, 4096 elements: 144 us two-phase, 275 us serial, 250 us forked) -- tuning value 1 still forces it
-    // (round 4: with several clean buckets the default keeps the LARGEST one where it holds at least half of the mesh -- a mesh with one
-    // dominant degree -- and leaves the other buckets' elements to the two-phase lists)
-    int clean_buckets = 0;
-    bool all_buckets = false;
-    {
-      std::vector<int> cnt(plan->buckets.size(), 0);
-      for (int e = 0; e < ne; ++e)
-        if (clean[e]) ++cnt[bucket_of[e]];
-      int best = -1;
-      for (size_t b = 0; b < cnt.size(); ++b) {
-        if (cnt[b] > 0) ++clean_buckets;
-        if (best < 0 || cnt[b] > cnt[best]) best = (int)b;
-      }
-      // ... and, at size, every clean bucket of at least 2048 clean elements (the smaller buckets' elements stay two-phase): with thousands of clean elements per bucket the buckets' launches fill the chip and their
-      // latency no longer matters (level 5, 32 768 elements, graded p = 3 ... 9: two-phase 756 us, hybrid 691 us; hanging + plateaus 1033 -> 894 us;
-      // at level 4, 385 clean elements per bucket: 275 against 126 us)
-      const bool one_only = std::getenv("D4EST_HIP_HYBRID_ONE_BUCKET_ONLY") != nullptr;
-      if (std::getenv("D4EST_HIP_DEBUG_HYBRID")) {
-        std::fprintf(stderr, "[d4est_hip] hybrid classification: %d of %d elements clean, per bucket:", n_clean, ne);
-        for (size_t b = 0; b < cnt.size(); ++b) std::fprintf(stderr, " N=%d:%d/%d", plan->buckets[b].N, cnt[b], plan->buckets[b].n_elem);
-        std::fprintf(stderr, "\n");
-      }
-      // the buckets that are worth a launch of their own at size: at least 2048 clean elements each
-      int n_kept = 0;
-      size_t kept_sum = 0;
-      for (size_t b = 0; b < cnt.size(); ++b)
-        if (cnt[b] >= 2048) { ++n_kept; kept_sum += (size_t)cnt[b]; }
-      if (plan->tuning[D4EST_HIP_TUNE_HYBRID] < 0 && clean_buckets > 1 && !one_only && n_kept >= 2 && 2 * kept_sum >= (size_t)ne) {
-        for (int e = 0; e < ne; ++e)
-          if (clean[e] && cnt[bucket_of[e]] < 2048) { clean[e] = 0; --n_clean; }   // (small buckets' elements: two-phase)
-        all_buckets = true;
-      } else if (plan->tuning[D4EST_HIP_TUNE_HYBRID] < 0 && clean_buckets > 1 && best >= 0 && 2 * (size_t)cnt[best] >= (size_t)ne && !one_only) {
-        for (int e = 0; e < ne; ++e)
-          if (clean[e] && bucket_of[e] != best) { clean[e] = 0; --n_clean; }
-        clean_buckets = 1;
-      }
-    }
-    if (n_clean > 0 && (plan->tuning[D4EST_HIP_TUNE_HYBRID] > 0 || all_buckets || (clean_buckets == 1 && 2 * (size_t)n_clean >= (size_t)ne))) {
-      std::vector<int> oC(plan->buckets.size(), -1), oCD(plan->buckets.size(), -1), oE(plan->buckets.size(), -1);
-      for (size_t b = 0; b < plan->buckets.size(); ++b) {
-        if (!bucket_ok[b]) continue;
-        const int d = plan->buckets[b].deg, dq = plan->buckets[b].deg_quad;
-        oC[b] = get_C(d, dq); oCD[b] = get_CD(d, dq); oE[b] = get_E(d, d, dq);
-      }
-      std::vector<const double*> pC(plan->buckets.size(), nullptr), pCD(plan->buckets.size(), nullptr), pE(plan->buckets.size(), nullptr);
-      for (size_t b = 0; b < plan->buckets.size(); ++b)
-        if (oC[b] >= 0) { pC[b] = ops.data() + oC[b]; pCD[b] = ops.data() + oCD[b]; pE[b] = ops.data() + oE[b]; }
-      // (the flags describe the classification before the dominant-bucket rule demoted anybody: a label, not a contract)
-      hybrid_setup(plan, clean, pC, pCD, pE, any_ov ? &ov : nullptr,
-                   any_hang_ov ? (any_mixed_ov ? "hanging-aware, mixed-aware" : "hanging-aware") : "mixed-aware");
-      {
-        const int *dd0, *dr0;
-        int nd0, nr0;
-        hybrid_lists(plan, &dd0, &nd0, &dr0, &nr0);
-        fh.hy_dirty_any = dd0;
-      }
-      if (fh.family_split) {
-        std::vector<char> is_small(ne, 0);
-        for (int e = 0; e < ne; ++e) {
-          bool sm = plan->deg[e] + 1 <= 8;
-          for (int f = 0; f < 6 && sm; ++f) {
-            const size_t s_ = 6 * (size_t)e + f;
-            sm = deg_mq_of[s_] + 1 <= 8 && deg_p_of[s_] + 1 <= 8;
-          }
-          is_small[e] = sm;
-        }
-        const std::vector<int>*hd, *hr;
-        hybrid_host_lists(plan, &hd, &hr);
-        std::vector<int> rs, rb, ds, db;
-        for (int e : *hr) (is_small[e] ? rs : rb).push_back(e);
-        for (int e : *hd) (is_small[e] ? ds : db).push_back(e);
-        fh.d_ring_small = upload_vec(rs); fh.n_ring_small = (int)rs.size();
-        fh.d_ring_big = upload_vec(rb); fh.n_ring_big = (int)rb.size();
-        fh.d_dirty_small = upload_vec(ds); fh.n_dirty_small = (int)ds.size();
-        fh.d_dirty_big = upload_vec(db); fh.n_dirty_big = (int)db.size();
-        const int *dd, *dr;
-        int nd_, nr_;
-        hybrid_lists(plan, &dd, &nd_, &dr, &nr_);
-        fh.hy_dirty = dd; fh.hy_ring = dr;
-      }
-    }
-  }
-  const size_t tm = std::max<size_t>((size_t)plan->total_mortar_nodes, 1);
-  HIP_CHECK(hipMalloc(&plan->d_trace, std::max<size_t>((size_t)plan->local_trace_doubles, 1) * sizeof(double)));
-  HIP_CHECK(hipMalloc(&plan->d_bndry, tm * sizeof(double)));  // Dirichlet data at the mortar quadrature nodes, by geom stride
-  HIP_CHECK(hipMemset(plan->d_bndry, 0, tm * sizeof(double)));
-  HIP_CHECK(hipMalloc(&plan->d_face_geom, 7 * tm * sizeof(double)));
-  plan->has_faces = true;
-}
-
-void faces_set_geometry(d4est_hip_plan* plan, const double* sj, const double* n, const double* drst_m, const double* drst_p,
-                        const double* hm, const double* hp, int on_device) {
-  FaceHost& fh = g_face_host[plan];
-  const size_t T = (size_t)plan->total_mortar_nodes;
-  const double* src[6] = {sj, n, drst_m, drst_p, hm, hp};
-  const size_t mult[6] = {1, 3, 9, 9, 1, 1};
-  double* tmp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  const double* dev[6];
-  for (int i = 0; i < 6; ++i) {
-    if (!src[i]) D4EST_HIP_ABORT("plan_set_mortar_geometry: NULL array %d", i);
-    if (on_device) {
-      dev[i] = src[i];
-    } else {
-      HIP_CHECK(hipMalloc(&tmp[i], std::max<size_t>(mult[i] * T, 1) * sizeof(double)));
-      HIP_CHECK(hipMemcpy(tmp[i], src[i], mult[i] * T * sizeof(double), hipMemcpyHostToDevice));
-      dev[i] = tmp[i];
-    }
-  }
-  const int n_sides = 6 * plan->n_elements;
-  if (fh.hp) {
-    if (fh.n_rec > 0)
-      hipLaunchKernelGGL(face_geom_hp_kernel, dim3(std::min(fh.n_rec, 8192)), dim3(64), 0, plan->stream, fh.d_rec, fh.d_gsrc, fh.n_rec,
-                         dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], plan->sipg_prefactor, plan->sipg_penalty_fcn, plan->d_face_geom);
-    HIP_CHECK(hipGetLastError());
-  } else if (n_sides > 0) {
-    const int grid = n_sides < 8192 ? n_sides : 8192;
-    hipLaunchKernelGGL(face_geom_kernel, dim3(grid), dim3(64), 0, plan->stream, (const SideDesc*)plan->d_side_desc,
-                       fh.d_side_deg_m, fh.d_side_deg_p, n_sides, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5],
-                       plan->sipg_prefactor, plan->sipg_penalty_fcn, plan->d_face_geom);
-    HIP_CHECK(hipGetLastError());
-  }
-  // raw sj is kept for Robin boundary data (faces_set_robin)
-  if (!fh.d_sj) HIP_CHECK(hipMalloc(&fh.d_sj, std::max<size_t>(T, 1) * sizeof(double)));
-  if (T > 0) HIP_CHECK(hipMemcpyAsync(fh.d_sj, dev[0], T * sizeof(double), hipMemcpyDeviceToDevice, plan->stream));
-  // the estimator's factors (d4est_hip_plan_set_estimator): only on plans that asked for them
-  if (plan->est_requested) estimator_setup(plan, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5]);
-  // the IP energy norm's face factor (d4est_hip_plan_set_energy_norm): likewise
-  if (plan->norm_requested) norms_setup(plan, dev[0], dev[1], dev[4], dev[5]);
-  HIP_CHECK(hipStreamSynchronize(plan->stream));
-  for (int i = 0; i < 6; ++i)
-    if (tmp[i]) HIP_CHECK(hipFree(tmp[i]));
-  plan->has_face_geometry = true;
-}
-
-void faces_set_dirichlet(d4est_hip_plan* plan, const double* g_lobatto, int on_device) {
-  FaceHost& fh = g_face_host[plan];
-  const size_t tm = std::max<size_t>((size_t)plan->total_mortar_nodes, 1);
-  fh.dirichlet_nonzero = (g_lobatto != nullptr);
-  plan->bc_inhomogeneous = fh.dirichlet_nonzero || fh.robin;
-  if (!g_lobatto) {
-    HIP_CHECK(hipMemsetAsync(plan->d_bndry, 0, tm * sizeof(double), plan->stream));
-    return;
-  }
-  const size_t nb = (size_t)plan->total_bndry_nodes;
-  if (nb == 0) return;
-  const double* dev = g_lobatto;
-  double* tmp = nullptr;
-  if (!on_device) {
-    HIP_CHECK(hipMalloc(&tmp, nb * sizeof(double)));
-    HIP_CHECK(hipMemcpy(tmp, g_lobatto, nb * sizeof(double), hipMemcpyHostToDevice));
-    dev = tmp;
-  }
-  const int n_sides = 6 * plan->n_elements;
-  hipLaunchKernelGGL(bndry_interp_kernel, dim3(std::min(n_sides, 8192)), dim3(64), 0, plan->stream, dev, plan->d_bndry,
-                     (const SideDesc*)plan->d_side_desc, (const ElemDesc*)plan->d_elem_desc, fh.d_side_bndry_stride,
-                     plan->d_face_ops, n_sides);
-  HIP_CHECK(hipGetLastError());
-  if (tmp) {
-    HIP_CHECK(hipStreamSynchronize(plan->stream));
-    HIP_CHECK(hipFree(tmp));
-  }
-}
-
-// brick geometry on the mortars (d4est_mesh_compute_mortar_quadrature_quantities on the brick map): constant per mortar;
-// the mortar is the face of a cell of the MORTAR's size (half the element on the big side of a hanging face)
-__device__ inline void brick_fill_mortar(int f, double hx, double hy, double hz, size_t S, int off, int TT, int T,
-                                         double* sj, double* nrm, double* drst_m, double* drst_p, double* hm, double* hp) {
-  const int dir = f >> 1;
-  const double h[3] = {hx, hy, hz};
-  const double J = hx * hy * hz;
-  const double sjv = J * (1. / h[dir]);
-  for (int k = threadIdx.x; k < T; k += blockDim.x) {
-    sj[S + off + k] = sjv;
-    hm[S + off + k] = J / sjv;
-    hp[S + off + k] = J / sjv;
-    for (int d = 0; d < 3; ++d) nrm[3 * S + (size_t)d * TT + off + k] = (d == dir) ? ((f & 1) ? 1. : -1.) : 0.;
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) {
-        const double v = (i == j) ? 1. / h[i] : 0.;
-        drst_m[9 * S + (size_t)(i + 3 * j) * TT + off + k] = v;
-        drst_p[9 * S + (size_t)(i + 3 * j) * TT + off + k] = v;
-      }
-  }
-}
-
-__global__ __launch_bounds__(64) void brick_mortar_kernel(const SideDesc* __restrict__ sd, int n_sides, const int* __restrict__ elem_dq,
-                                                          double root_len, double ex, double ey, double ez, double* sj, double* nrm,
-                                                          double* drst_m, double* drst_p, double* hm, double* hp) {
-  for (int s = blockIdx.x; s < n_sides; s += gridDim.x) {
-    const SideDesc d = sd[s];
-    if (d.kind == 3) continue;   // hanging side: written by the record kernel
-    const double half = (double)elem_dq[s / 6] / root_len / 2.;
-    const int T = d.NQ * d.NQ;
-    brick_fill_mortar(s % 6, ex * half, ey * half, ez * half, (size_t)d.geom, 0, T, T, sj, nrm, drst_m, drst_p, hm, hp);
-  }
-}
-
-__global__ __launch_bounds__(64) void brick_mortar_hp_kernel(const HpMortar* __restrict__ md, const HpGeomSrc* __restrict__ gs, int n_rec,
-                                                             const int* __restrict__ elem_dq, double root_len, double ex, double ey,
-                                                             double ez, double* sj, double* nrm, double* drst_m, double* drst_p,
-                                                             double* hm, double* hp) {
-  for (int r = blockIdx.x; r < n_rec; r += gridDim.x) {
-    const HpMortar m = md[r];
-    const HpGeomSrc g = gs[r];
-    const double half = (double)elem_dq[m.elem] / root_len / 2. * (m.fm < 1.0 ? 0.5 : 1.0);   // big side: half-size mortar
-    brick_fill_mortar(m.face, ex * half, ey * half, ez * half, (size_t)g.S, g.off, g.Ttot, m.NQ * m.NQ, sj, nrm, drst_m, drst_p, hm, hp);
-  }
-}
-
-// The mortar faces of hm / hp with the elements whose size parameters d4est_mesh_calculate_mortar_h reads for them
-// (src/Mesh/d4est_mesh.c:689-856 as called at :629-644 and :1071-1103): (-) elements on f_m, (+) elements in (-) order on f_p; on a
-// hanging face the side of four gives each mortar face its own small element, the other side its one big element.
-// dq: p4est side length of the local elements, then of the ghost elements.
-static std::vector<MortarHUnit> mortar_h_units(d4est_hip_plan* plan, const std::vector<int>& dq, double root_len, const char* who) {
-  FaceHost& fh = g_face_host[plan];
-  const int ne = plan->n_elements, type = plan->face_h_type;
-  if ((type == D4EST_HIP_FACE_H_EQ_FACE_DIAM || type == D4EST_HIP_FACE_H_EQ_TOTAL_VOLUME_DIV_TOTAL_AREA) && plan->n_ghost > 0)
-    D4EST_HIP_ABORT("%s: face_h_type %d (%s) is not defined on a plan with ghost sides: the reference reads diam_face / area / volume without "
-                    "the ghost offset there (src/Mesh/d4est_mesh.c:801-802, :841)", who, type,
-                    type == D4EST_HIP_FACE_H_EQ_FACE_DIAM ? "FACE_H_EQ_FACE_DIAM" : "FACE_H_EQ_TOTAL_VOLUME_DIV_TOTAL_AREA");
-  auto idx = [&](int ref) {
-    if (ref == -1) D4EST_HIP_ABORT("%s: boundary reference on an interior side", who);
-    const int i = ref >= 0 ? ref : ne - (ref + 2);
-    if (i >= (int)dq.size()) D4EST_HIP_ABORT("%s: ghost element %d has no cell description", who, i - ne);
-    return i;
-  };
-  std::vector<MortarHUnit> units;
-  auto add = [&](int at, int T, int e, int f, int hang, size_t s, int i) {
-    MortarHUnit u{};
-    u.at = at; u.T = T;
-    u.one_m = e; u.f_m = f; u.n_m = 1; u.em[0] = e;
-    if (plan->side_nbr[s] == -1) {   // boundary: one h (:629-644)
-      u.one_p = e; u.f_p = f; u.n_p = 1; u.ep[0] = e;
-    } else {
-      u.f_p = plan->side_nbr_face[s];
-      if (hang == 0) {
-        u.one_p = idx(plan->side_nbr[s]); u.n_p = 1; u.ep[0] = u.one_p;
-      } else if (hang == 1) {        // (+) side: the four small elements in (-) order
-        u.n_p = 4;
-        for (int k = 0; k < 4; ++k) u.ep[k] = idx(plan->side_nbr4[4 * s + k]);
-        u.one_p = u.ep[i];
-      } else {                       // this element is one of the four (-) elements; (+) side: the big element
-        u.n_m = 4;
-        for (int k = 0; k < 4; ++k) u.em[k] = idx(plan->side_nbr4[4 * s + k]);
-        u.one_p = idx(plan->side_nbr[s]); u.n_p = 1; u.ep[0] = u.one_p;
-      }
-    }
-    u.tree_h_m = (double)dq[u.one_m] / root_len;
-    u.tree_h_p = (double)dq[u.one_p] / root_len;
-    units.push_back(u);
-  };
-  if (fh.hp) {
-    std::vector<HpMortar> rec((size_t)fh.n_rec);
-    std::vector<HpGeomSrc> gs((size_t)fh.n_rec);
-    if (fh.n_rec > 0) {
-      HIP_CHECK(hipMemcpy(rec.data(), fh.d_rec, rec.size() * sizeof(HpMortar), hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(gs.data(), fh.d_gsrc, gs.size() * sizeof(HpGeomSrc), hipMemcpyDeviceToHost));
-    }
-    for (int e = 0; e < ne; ++e)
-      for (int f = 0; f < 6; ++f) {
-        const size_t s = 6 * (size_t)e + f;
-        for (int r = plan->side_first_rec[s]; r < plan->side_first_rec[s + 1]; ++r)
-          add(gs[r].S + gs[r].off, rec[r].NQ * rec[r].NQ, e, f, plan->side_hang[s], s, r - plan->side_first_rec[s]);
-      }
-  } else {
-    std::vector<SideDesc> sd(6 * (size_t)ne);
-    if (!sd.empty()) HIP_CHECK(hipMemcpy(sd.data(), plan->d_side_desc, sd.size() * sizeof(SideDesc), hipMemcpyDeviceToHost));
-    for (size_t s = 0; s < sd.size(); ++s) add(sd[s].geom, sd[s].NQ * sd[s].NQ, (int)(s / 6), (int)(s % 6), 0, s, 0);
-  }
-  return units;
-}
-
-void faces_set_geometry_brick(d4est_hip_plan* plan, const int* d_elem_dq, const int* h_elem_dq, double root_len, const double* extents) {
-  FaceHost& fh = g_face_host[plan];
-  const size_t T = std::max<size_t>((size_t)plan->total_mortar_nodes, 1);
-  double* a[6];
-  const size_t mult[6] = {1, 3, 9, 9, 1, 1};
-  for (int i = 0; i < 6; ++i) {
-    HIP_CHECK(hipMalloc(&a[i], mult[i] * T * sizeof(double)));
-    HIP_CHECK(hipMemsetAsync(a[i], 0, mult[i] * T * sizeof(double), plan->stream));
-  }
-  const double ex = extents[1] - extents[0], ey = extents[3] - extents[2], ez = extents[5] - extents[4];
-  const int n_sides = 6 * plan->n_elements;
-  if (fh.hp) {
-    if (fh.n_rec > 0)
-      hipLaunchKernelGGL(brick_mortar_hp_kernel, dim3(std::min(fh.n_rec, 8192)), dim3(64), 0, plan->stream, fh.d_rec, fh.d_gsrc, fh.n_rec,
-                         d_elem_dq, root_len, ex, ey, ez, a[0], a[1], a[2], a[3], a[4], a[5]);
-  } else if (n_sides > 0) {
-    hipLaunchKernelGGL(brick_mortar_kernel, dim3(std::min(n_sides, 8192)), dim3(64), 0, plan->stream, (const SideDesc*)plan->d_side_desc,
-                       n_sides, d_elem_dq, root_len, ex, ey, ez, a[0], a[1], a[2], a[3], a[4], a[5]);
-  }
-  HIP_CHECK(hipGetLastError());
-  if (plan->face_h_type != D4EST_HIP_FACE_H_EQ_J_DIV_SJ_QUAD) {
-    // a ghost element's size follows from the side that refers to it (2:1 balance): the same, half (the small elements of a big
-    // side) or twice (the big element of a small side) the local element's
-    const int ne = plan->n_elements, ng = plan->n_ghost;
-    std::vector<int> dq(h_elem_dq, h_elem_dq + ne);
-    dq.resize((size_t)ne + ng, ne > 0 ? h_elem_dq[0] : 1);
-    auto set = [&](int ref, int v) { if (ref <= -2 && -(ref + 2) < ng) dq[(size_t)ne - (ref + 2)] = v; };
-    for (size_t s = 0; s < 6 * (size_t)ne; ++s) {
-      const int hang = plan->side_hang.empty() ? 0 : plan->side_hang[s], own = h_elem_dq[s / 6];
-      set(plan->side_nbr[s], hang == 2 ? 2 * own : hang == 1 ? own / 2 : own);
-      if (hang != 0)
-        for (int k = 0; k < 4; ++k) set(plan->side_nbr4[4 * s + k], hang == 1 ? own / 2 : own);
-    }
-    std::vector<CellDesc> cells(dq.size());
-    for (size_t i = 0; i < dq.size(); ++i) cells[i] = CellDesc{0, {0, 0, 0}, dq[i], 0};
-    const std::vector<MortarHUnit> units = mortar_h_units(plan, dq, root_len, "plan_set_mortar_geometry_brick");
-    if (plan->face_h_type != D4EST_HIP_FACE_H_EQ_TREE_H) sizes_compute(plan, nullptr, extents, cells, ng, root_len);
-    sizes_fill_mortar_h(plan, units, a[4], a[5]);
-  }
-  faces_set_geometry(plan, a[0], a[1], a[2], a[3], a[4], a[5], /*on_device=*/1);
-  for (int i = 0; i < 6; ++i) HIP_CHECK(hipFree(a[i]));
-}
-
-// ---------------------------------------------------------------------------
-// Mortar factors of an analytic tree map on the device (d4est_mesh_compute_mortar_quadrature_quantities with
-// DX_compute_method = GEOM_COMPUTE_ANALYTIC, src/Mesh/d4est_mesh.c:858-1108, src/Mesh/d4est_mortars.c:19-190): one unit per
-// conforming side / per mortar record.  The (-) cell gives sj, n (COMPUTE_NORMAL_USING_JACOBIAN), dr/dx and hm = J/sj at the
-// mortar's quadrature nodes in (-) order; the (+) cell -- evaluated in ITS tree, at ITS nodes -- gives drst_dxyz_p_porder in the
-// (+) side's own node and sub-face order and, re-oriented into (-) order, hp.  On the big side of a hanging face the cells are
-// the half-size virtual children of the element (d4est_mortars_compute_qcoords_on_mortar, :419-468).  The arrays are written in
-// the reference's layout and handed to the same pre-combination as host-supplied factors.
-// ---------------------------------------------------------------------------
-struct MortarUnit {
-  int S, off, off_p, Ttot, NQ, code, boundary, pad;
-  CellDesc m, p;
-};
-
-__device__ inline void face_ref_point(int f, double ta, double tb, double r[3]) {
-  const int dir = f >> 1;
-  r[dir] = (f & 1) ? 1.0 : -1.0;
-  r[dir == 0 ? 1 : 0] = ta;
-  r[dir == 2 ? 1 : 2] = tb;
-}
-
-__global__ __launch_bounds__(64) void analytic_mortar_kernel(const MortarUnit* __restrict__ units, int n_units, TreeMapParams P,
-                                                             double root_len, const double* __restrict__ quad_nodes /* [NQ][24] */,
-                                                             double* sj, double* nrm, double* drst_m, double* drst_p, double* hm, double* hp) {
-  for (int ui = blockIdx.x; ui < n_units; ui += gridDim.x) {
-    const MortarUnit un = units[ui];
-    const int NQ = un.NQ, T = NQ * NQ;
-    const double* t = quad_nodes + 24 * NQ;
-    const size_t S = (size_t)un.S;
-    for (int k = threadIdx.x; k < T; k += blockDim.x) {
-      const int a = k % NQ, b = k / NQ;
-      double r[3], dxdr[3][3], inv[3][3];
-      face_ref_point(un.m.face, t[a], t[b], r);
-      cell_dxdr(P, un.m, root_len, r, dxdr);
-      const double J = invert3(dxdr, inv);
-      const int dir = un.m.face >> 1;
-      const double sgn = (un.m.face & 1) ? 1.0 : -1.0;
-      double v[3], s2 = 0.0;
-      for (int d = 0; d < 3; ++d) { v[d] = sgn * J * inv[dir][d]; s2 += v[d] * v[d]; }
-      const double sjv = sqrt(s2);
-      sj[S + un.off + k] = sjv;
-      hm[S + un.off + k] = J / sjv;
-      for (int d = 0; d < 3; ++d) nrm[3 * S + (size_t)d * un.Ttot + un.off + k] = v[d] / sjv;
-      for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) drst_m[9 * S + (size_t)(i + 3 * j) * un.Ttot + un.off + k] = inv[i][j];
-      if (un.boundary) {
-        hp[S + un.off + k] = J / sjv;
-        for (int i = 0; i < 3; ++i)
-          for (int j = 0; j < 3; ++j) drst_p[9 * S + (size_t)(i + 3 * j) * un.Ttot + un.off_p + k] = inv[i][j];
-        continue;
-      }
-      // (+) side, its own node k
-      face_ref_point(un.p.face, t[a], t[b], r);
-      cell_dxdr(P, un.p, root_len, r, dxdr);
-      (void)invert3(dxdr, inv);
-      for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) drst_p[9 * S + (size_t)(i + 3 * j) * un.Ttot + un.off_p + k] = inv[i][j];
-      // hp at (-) node k = J/sj of the (+) side at its node reorder(k)
-      const int kp = reorder_index(un.code, NQ - 1, a, b);
-      face_ref_point(un.p.face, t[kp % NQ], t[kp / NQ], r);
-      cell_dxdr(P, un.p, root_len, r, dxdr);
-      const double Jp = invert3(dxdr, inv);
-      const int dirp = un.p.face >> 1;
-      double sp = 0.0;
-      for (int d = 0; d < 3; ++d) sp += (Jp * inv[dirp][d]) * (Jp * inv[dirp][d]);
-      hp[S + un.off + k] = Jp / sqrt(sp);
-    }
-  }
-}
-
-static CellDesc face_child(const CellDesc& c, int face, int child) {
-  // half-size virtual child `child` (z-order on the face) of cell c that touches face `face`
-  CellDesc r = c;
-  const int dir = face >> 1, h = c.dq / 2;
-  const int a0 = dir == 0 ? 1 : 0, a1 = dir == 2 ? 1 : 2;
-  r.dq = h;
-  r.q[a0] += (child & 1) * h;
-  r.q[a1] += (child >> 1) * h;
-  if (face & 1) r.q[dir] += h;
-  r.face = face;
-  return r;
-}
-
-void faces_set_geometry_analytic(d4est_hip_plan* plan, const TreeMapParams& P, const std::vector<CellDesc>& elem,
-                                 const std::vector<CellDesc>& ghost, double root_len) {
-  FaceHost& fh = g_face_host[plan];
-  const int ne = plan->n_elements;
-  auto cell_of = [&](int ref, int face) {
-    if (ref == -1) D4EST_HIP_ABORT("plan_set_mortar_geometry_analytic: boundary reference");
-    CellDesc c;
-    if (ref >= 0) c = elem[ref];
-    else {
-      const int g = -(ref + 2);
-      if (g >= (int)ghost.size()) D4EST_HIP_ABORT("plan_set_mortar_geometry_analytic: ghost element %d has no cell description", g);
-      c = ghost[g];
-    }
-    c.face = face;
-    return c;
-  };
-  std::vector<MortarUnit> units;
-  if (fh.hp) {
-    std::vector<HpMortar> rec((size_t)fh.n_rec);
-    std::vector<HpGeomSrc> gs((size_t)fh.n_rec);
-    HIP_CHECK(hipMemcpy(rec.data(), fh.d_rec, rec.size() * sizeof(HpMortar), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(gs.data(), fh.d_gsrc, gs.size() * sizeof(HpGeomSrc), hipMemcpyDeviceToHost));
-    for (int e = 0; e < ne; ++e)
-      for (int f = 0; f < 6; ++f) {
-        const size_t s = 6 * (size_t)e + f;
-        const int hang = plan->side_hang[s], nbr = plan->side_nbr[s], f_p = plan->side_nbr_face[s], o = plan->side_orientation[s];
-        const int r0 = plan->side_first_rec[s], r1 = plan->side_first_rec[s + 1];
-        for (int r = r0; r < r1; ++r) {
-          MortarUnit u{};
-          u.S = gs[r].S; u.off = gs[r].off; u.off_p = gs[r].off_p; u.Ttot = gs[r].Ttot; u.NQ = rec[r].NQ; u.code = rec[r].code;
-          u.boundary = (rec[r].kind == 0);
-          if (hang == 0) {
-            u.m = cell_of(e, f);
-            u.p = u.boundary ? u.m : cell_of(nbr, f_p);
-          } else if (hang == 1) {
-            const int i = r - r0;
-            u.m = face_child(cell_of(e, f), f, i);
-            u.p = cell_of(plan->side_nbr4[4 * s + i], f_p);
-          } else {
-            const int c = plan->side_sub[s];
-            u.m = cell_of(e, f);
-            u.p = face_child(cell_of(nbr, f_p), f_p, reorient_face_order(f, f_p, o, c));
-          }
-          units.push_back(u);
-        }
-      }
-  } else {
-    std::vector<SideDesc> sd(6 * (size_t)ne);
-    if (!sd.empty()) HIP_CHECK(hipMemcpy(sd.data(), plan->d_side_desc, sd.size() * sizeof(SideDesc), hipMemcpyDeviceToHost));
-    for (size_t s = 0; s < sd.size(); ++s) {
-      MortarUnit u{};
-      const int T = sd[s].NQ * sd[s].NQ;
-      u.S = sd[s].geom; u.off = 0; u.off_p = 0; u.Ttot = T; u.NQ = sd[s].NQ; u.code = sd[s].code; u.boundary = (sd[s].kind == 0);
-      u.m = cell_of((int)(s / 6), (int)(s % 6));
-      u.p = u.boundary ? u.m : cell_of(plan->side_nbr[s], plan->side_nbr_face[s]);
-      units.push_back(u);
-    }
-  }
-  // quadrature nodes of every mortar degree in use
-  std::vector<double> qn((size_t)25 * 24, 0.0);
-  for (const MortarUnit& u : units) {
-    if (u.NQ > 24) D4EST_HIP_ABORT("plan_set_mortar_geometry_analytic: mortar degree %d", u.NQ - 1);
-    if (qn[(size_t)24 * u.NQ + u.NQ - 1] == 0.0 || u.NQ == 1) {
-      std::vector<double> x, w;
-      if (plan->quad_type == QUAD_LEGENDRE) Tables1D::gauss(u.NQ - 1, x, w);
-      else Tables1D::lobatto(u.NQ - 1, x, w);
-      for (int i = 0; i < u.NQ; ++i) qn[(size_t)24 * u.NQ + i] = x[i];
-    }
-  }
-  const size_t T = std::max<size_t>((size_t)plan->total_mortar_nodes, 1);
-  double* a[6];
-  const size_t mult[6] = {1, 3, 9, 9, 1, 1};
-  for (int i = 0; i < 6; ++i) {
-    HIP_CHECK(hipMalloc(&a[i], mult[i] * T * sizeof(double)));
-    HIP_CHECK(hipMemsetAsync(a[i], 0, mult[i] * T * sizeof(double), plan->stream));
-  }
-  MortarUnit* d_units = upload_vec(units);
-  double* d_qn = upload_vec(qn);
-  if (!units.empty())
-    hipLaunchKernelGGL(analytic_mortar_kernel, dim3(std::min((int)units.size(), 8192)), dim3(64), 0, plan->stream, d_units, (int)units.size(), P,
-                       root_len, d_qn, a[0], a[1], a[2], a[3], a[4], a[5]);
-  HIP_CHECK(hipGetLastError());
-  if (plan->face_h_type != D4EST_HIP_FACE_H_EQ_J_DIV_SJ_QUAD) {
-    std::vector<CellDesc> cells(elem);
-    cells.insert(cells.end(), ghost.begin(), ghost.end());
-    std::vector<int> dq(cells.size());
-    for (size_t i = 0; i < cells.size(); ++i) dq[i] = cells[i].dq;
-    const std::vector<MortarHUnit> hunits = mortar_h_units(plan, dq, root_len, "plan_set_mortar_geometry_analytic");
-    if (plan->face_h_type != D4EST_HIP_FACE_H_EQ_TREE_H) sizes_compute(plan, &P, nullptr, cells, (int)ghost.size(), root_len);
-    sizes_fill_mortar_h(plan, hunits, a[4], a[5]);
-  }
-  faces_set_geometry(plan, a[0], a[1], a[2], a[3], a[4], a[5], /*on_device=*/1);
-  for (int i = 0; i < 6; ++i) HIP_CHECK(hipFree(a[i]));
-  HIP_CHECK(hipFree(d_units));
-  HIP_CHECK(hipFree(d_qn));
-}
-
-__global__ __launch_bounds__(256) void robin_setup_kernel(const double* __restrict__ sj, const double* __restrict__ coeff,
-                                                          const double* __restrict__ rhs, double* __restrict__ c,
-                                                          double* __restrict__ r, size_t n) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    c[i] = sj[i] * coeff[i];
-    r[i] = sj[i] * rhs[i];
-  }
-}
-
-// Robin boundary data at the mortar quadrature nodes of the boundary sides (indexed like sj: side stride S + k).
-// coeff_quad == NULL switches the boundary sides back to Dirichlet.
-void faces_set_robin(d4est_hip_plan* plan, const double* coeff_quad, const double* rhs_quad, int on_device) {
-  FaceHost& fh = g_face_host[plan];
-  if (!plan->has_face_geometry) D4EST_HIP_ABORT("plan_set_robin_values: call d4est_hip_plan_set_mortar_geometry first (needs sj)");
-  if (!coeff_quad) {
-    fh.robin = false;
-    plan->bc_inhomogeneous = fh.dirichlet_nonzero;   // back to Dirichlet: the values set earlier are still in d_bndry
-    return;
-  }
-  if (!rhs_quad) D4EST_HIP_ABORT("plan_set_robin_values: rhs_quad is NULL");
-  const size_t tm = (size_t)plan->total_mortar_nodes;
-  if (!fh.d_robin_c) {
-    HIP_CHECK(hipMalloc(&fh.d_robin_c, std::max<size_t>(tm, 1) * sizeof(double)));
-    HIP_CHECK(hipMalloc(&fh.d_robin_r, std::max<size_t>(tm, 1) * sizeof(double)));
-  }
-  fh.robin = true;
-  plan->bc_inhomogeneous = true;
-  if (tm == 0) return;
-  const double* dc = coeff_quad;
-  const double* dr = rhs_quad;
-  double *tc = nullptr, *tr = nullptr;
-  if (!on_device) {
-    HIP_CHECK(hipMalloc(&tc, tm * sizeof(double)));
-    HIP_CHECK(hipMalloc(&tr, tm * sizeof(double)));
-    HIP_CHECK(hipMemcpy(tc, coeff_quad, tm * sizeof(double), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(tr, rhs_quad, tm * sizeof(double), hipMemcpyHostToDevice));
-    dc = tc;
-    dr = tr;
-  }
-  hipLaunchKernelGGL(robin_setup_kernel, dim3(1024), dim3(256), 0, plan->stream, fh.d_sj, dc, dr, fh.d_robin_c, fh.d_robin_r, tm);
-  HIP_CHECK(hipGetLastError());
-  if (tc) {
-    HIP_CHECK(hipStreamSynchronize(plan->stream));
-    HIP_CHECK(hipFree(tc));
-    HIP_CHECK(hipFree(tr));
-  }
-}
-
-const double* faces_sj(d4est_hip_plan* plan, const char* who) {
-  if (!plan->has_face_geometry) D4EST_HIP_ABORT("%s: call d4est_hip_plan_set_mortar_geometry first (needs sj)", who);
-  return g_face_host[plan].d_sj;
-}
-
-void faces_robin_arrays(d4est_hip_plan* plan, const char* who, double** robin_c, double** robin_r) {
-  if (!plan->has_face_geometry) D4EST_HIP_ABORT("%s: call d4est_hip_plan_set_mortar_geometry first (needs sj)", who);
-  FaceHost& fh = g_face_host[plan];
-  const size_t tm = (size_t)plan->total_mortar_nodes;
-  if (!fh.d_robin_c) {
-    HIP_CHECK(hipMalloc(&fh.d_robin_c, std::max<size_t>(tm, 1) * sizeof(double)));
-    HIP_CHECK(hipMalloc(&fh.d_robin_r, std::max<size_t>(tm, 1) * sizeof(double)));
-  }
-  fh.robin = true;
-  plan->bc_inhomogeneous = true;
-  *robin_c = fh.d_robin_c;
-  *robin_r = fh.d_robin_r;
-}
 
 // resident workgroups per CU assumed by the persistent fast kernels (experiment knob: D4EST_HIP_FACE_WG_PER_CU)
 static int face_wg_per_cu() {
@@ -3372,13 +1861,15 @@ struct FamilyLists {
 };
 static FamilyLists family_lists(const FaceHost& fh, const int* elist, bool ring) {
   const int* hy = ring ? fh.hy_ring : fh.hy_dirty;
-  const int* hy_small = ring ? fh.d_ring_small : fh.d_dirty_small;
+  const ElemList& hy_small = ring ? fh.ring_small : fh.dirty_small;
+  const ElemList& small = elist ? hy_small : fh.fam_small;
+  const ElemList& big = elist ? (ring ? fh.ring_big : fh.dirty_big) : fh.fam_big;
   FamilyLists l;
-  l.on = fh.family_split && (!elist || (elist == hy && hy_small));
-  l.small = elist ? hy_small : fh.d_fam_small;
-  l.big = elist ? (ring ? fh.d_ring_big : fh.d_dirty_big) : fh.d_fam_big;
-  l.n_small = elist ? (ring ? fh.n_ring_small : fh.n_dirty_small) : fh.n_fam_small;
-  l.n_big = elist ? (ring ? fh.n_ring_big : fh.n_dirty_big) : fh.n_fam_big;
+  l.on = fh.family_split && (!elist || (elist == hy && hy_small.d));
+  l.small = small.d;
+  l.big = big.d;
+  l.n_small = small.n;
+  l.n_big = big.n;
   return l;
 }
 
@@ -3398,7 +1889,7 @@ static const double* robin_c_of(const FaceHost& fh) { return fh.robin ? fh.d_rob
 static const double* robin_r_of(const FaceHost& fh) { return fh.robin ? fh.d_robin_r : nullptr; }
 
 void faces_robin(d4est_hip_plan* plan, const double** robin_c, const double** robin_r) {
-  const FaceHost& fh = g_face_host[plan];
+  const FaceHost& fh = face_host(plan);
   *robin_c = robin_c_of(fh);
   *robin_r = robin_r_of(fh);
 }
@@ -3459,7 +1950,7 @@ static void run_trace_generic(d4est_hip_plan* plan, const FaceHost& fh, const do
 }
 
 void launch_traces(d4est_hip_plan* plan, const double* u, double* trace, bool ghost, const int* elist, int n_list, int parts) {
-  FaceHost& fh = g_face_host[plan];
+  FaceHost& fh = face_host(plan);
   if (ghost) {
     if (fh.hp) D4EST_HIP_ABORT("compute_ghost_traces: plans with hanging faces take their ghost traces from the trace exchange (d4est_hip_plan_*_sub offsets), not from whole ghost elements");
     if (fh.n_ghost_sides == 0) return;
@@ -3486,7 +1977,7 @@ void launch_traces(d4est_hip_plan* plan, const double* u, double* trace, bool gh
         else if (!run_trace_families(plan, fh, u, trace, elist)) run_trace_mfma16(plan, fh, u, trace, n, elist);
       }
       if ((parts & 2) && fh.n_units > 0) run_trace_unit(plan, fh, u, trace);
-      else if ((parts & 2) && fh.n_hang_elems > 0) run_trace_hp_mfma16(plan, fh, u, trace, fh.n_hang_elems, fh.d_hang_elems, 1);
+      else if ((parts & 2) && fh.hang_elems.n > 0) run_trace_hp_mfma16(plan, fh, u, trace, fh.hang_elems.n, fh.hang_elems.d, 1);
       break;
     case FaceFamily::HpTiled: run_trace_hp_mfma16(plan, fh, u, trace, n, elist, 0); break;
     case FaceFamily::HpGeneric: run_trace_hp_generic(plan, fh, u, trace, n); break;
@@ -3516,7 +2007,7 @@ void launch_traces(d4est_hip_plan* plan, const double* u, double* trace, bool gh
 static bool flux_can_fuse(d4est_hip_plan* plan, FaceFamily fam) {
   return plan->has_faces && plan->n_elements > 0 && !hybrid_active(plan) && flux_family_fuses(fam);
 }
-bool flux_can_fuse_update(d4est_hip_plan* plan) { return flux_can_fuse(plan, face_family(plan, g_face_host[plan])); }
+bool flux_can_fuse_update(d4est_hip_plan* plan) { return flux_can_fuse(plan, face_family(plan, face_host(plan))); }
 
 // p <= 7, 6 waves, persistent grid of face_wg_per_cu() workgroups per CU.  INPLACE = false: a Schwarz subdomain plan (see the kernel)
 template <bool FUSE, bool INPLACE>
@@ -3561,9 +2052,9 @@ static bool flux_families(d4est_hip_plan* plan, const FaceHost& fh, const double
 template <bool FUSE>
 static void run_flux_unit(d4est_hip_plan* plan, const FaceHost& fh, const double* trace, const double* ghost_trace, double* Au, const ChebyFuse& cf) {
   auto go = [&](auto kern, int per_cu) {
-    hipLaunchKernelGGL(kern, dim3(std::min(fh.n_hang_elems, per_cu * face_cus(plan))), dim3(256), 0, plan->stream, trace, ghost_trace, Au, fh.d_rec,
+    hipLaunchKernelGGL(kern, dim3(std::min(fh.hang_elems.n, per_cu * face_cus(plan))), dim3(256), 0, plan->stream, trace, ghost_trace, Au, fh.d_rec,
                        fh.d_units, fh.d_unit_first, (const ElemDesc*)fh.d_elem_desc_generic, plan->d_face_ops, fh.d_hp_ops, plan->d_face_geom,
-                       plan->d_bndry, robin_c_of(fh), robin_r_of(fh), fh.n_hang_elems, cf);
+                       plan->d_bndry, robin_c_of(fh), robin_r_of(fh), fh.hang_elems.n, cf);
   };
   if (fh.hp_max_N <= 8) go(flux_unit_kernel<FUSE, 8>, 8);
   else go(flux_unit_kernel<FUSE, 16>, 2);
@@ -3592,7 +2083,7 @@ static void run_flux_generic(d4est_hip_plan* plan, const FaceHost& fh, const dou
 
 void launch_flux(d4est_hip_plan* plan, const double* trace, const double* ghost_trace, double* Au, const ChebyFuse* cf, const int* elist,
                  int n_list, int parts) {
-  FaceHost& fh = g_face_host[plan];
+  FaceHost& fh = face_host(plan);
   const FaceFamily fam = face_family(plan, fh);
   if (cf && !(flux_can_fuse(plan, fam) || (elist && hybrid_active(plan) && !fh.hp))) D4EST_HIP_ABORT("launch_flux: fused update requested on a plan whose flux kernel cannot carry it");
   if (!plan->has_faces || !plan->has_face_geometry) D4EST_HIP_ABORT("apply flux: plan_set_faces / plan_set_mortar_geometry were not called");
@@ -3613,7 +2104,7 @@ void launch_flux(d4est_hip_plan* plan, const double* trace, const double* ghost_
         else if (!flux_families(plan, fh, trace, ghost_trace, Au, elist, nullptr)) flux_mfma16(plan, fh, trace, ghost_trace, Au, n, elist, nullptr, false);
       }
       if ((parts & 2) && fh.n_units > 0) run_flux_unit<false>(plan, fh, trace, ghost_trace, Au, ChebyFuse{});
-      else if ((parts & 2) && fh.n_hang_elems > 0) run_flux_hp_mfma16(plan, fh, trace, ghost_trace, Au, fh.n_hang_elems, fh.d_hang_elems, 1);
+      else if ((parts & 2) && fh.hang_elems.n > 0) run_flux_hp_mfma16(plan, fh, trace, ghost_trace, Au, fh.hang_elems.n, fh.hang_elems.d, 1);
       break;
     case FaceFamily::HpTiled: run_flux_hp_mfma16(plan, fh, trace, ghost_trace, Au, n, elist, 0); break;
     case FaceFamily::HpGeneric: run_flux_hp_generic(plan, fh, trace, ghost_trace, Au, n); break;
@@ -3632,65 +2123,23 @@ void launch_flux(d4est_hip_plan* plan, const double* trace, const double* ghost_
 }
 
 void launch_flux_units(d4est_hip_plan* plan, const double* trace, const double* ghost_trace, double* Au, const ChebyFuse* cf) {
-  FaceHost& fh = g_face_host[plan];
+  FaceHost& fh = face_host(plan);
   if (!(fh.hp && fh.hp_split)) D4EST_HIP_ABORT("launch_flux_units: the plan has no hp split");
   if (!cf) { launch_flux(plan, trace, ghost_trace, Au, nullptr, nullptr, 0, 2); return; }
-  if (fh.n_hang_elems == 0) return;
+  if (fh.hang_elems.n == 0) return;
   if (fh.n_units == 0) D4EST_HIP_ABORT("launch_flux_units: a fused update needs the unit form of the record kernels");
   if (!cf->u_out || cf->u_out == cf->u) D4EST_HIP_ABORT("launch_flux_units: the fused update needs a second vector");
   run_flux_unit<true>(plan, fh, trace, ghost_trace, Au, *cf);
   HIP_CHECK(hipGetLastError());
 }
-bool faces_hp(d4est_hip_plan* plan) { return g_face_host[plan].hp; }
+bool faces_hp(d4est_hip_plan* plan) { return face_host(plan).hp; }
 bool faces_hp_split(d4est_hip_plan* plan) {
-  FaceHost& fh = g_face_host[plan];
+  FaceHost& fh = face_host(plan);
   return fh.hp && fh.hp_split;
 }
 bool faces_have_units(d4est_hip_plan* plan) {
-  FaceHost& fh = g_face_host[plan];
-  return fh.hp && fh.hp_split && (fh.n_hang_elems == 0 || fh.n_units > 0);
-}
-
-void faces_estimator_mortars(d4est_hip_plan* plan, std::vector<EstMortar>& out, std::vector<int>& elem_first, const double** face_ops,
-                             const double** hp_ops) {
-  FaceHost& fh = g_face_host[plan];
-  const int ne = plan->n_elements;
-  out.clear();
-  elem_first.assign(ne + 1, 0);
-  *face_ops = plan->d_face_ops;
-  *hp_ops = fh.d_hp_ops;
-  if (fh.hp) {
-    // the records as faces_setup_hp built them (before the hp split re-labelled the small sides it hands to the conforming kernels)
-    for (int e = 0; e < ne; ++e) {
-      elem_first[e] = (int)out.size();
-      for (int r = plan->side_first_rec[6 * (size_t)e]; r < plan->side_first_rec[6 * (size_t)e + 6]; ++r) {
-        const HpMortar& m = fh.rec_host[r];
-        const HpGeomSrc& g = fh.gsrc_host[r];
-        const size_t s = 6 * (size_t)e + m.face;
-        EstMortar x{};
-        x.elem = e; x.kind = m.kind; x.code = m.code; x.NQ = m.NQ; x.gidx = m.gidx;
-        x.S = g.S; x.off = g.off; x.off_p = g.off_p; x.Ttot = g.Ttot; x.deg_m = g.deg_m; x.deg_p = g.deg_p;
-        x.N = m.N; x.offC = m.offCa; x.ops_hp = 1; x.bstride = plan->side_bndry_stride[s]; x.u_shift = m.u_shift;
-        x.fm = m.fm; x.fp = m.fp; x.qoff = m.qoff; x.nbr_qoff = m.nbr_qoff;
-        out.push_back(x);
-      }
-    }
-  } else {
-    for (int e = 0; e < ne; ++e) {
-      elem_first[e] = (int)out.size();
-      for (int f = 0; f < 6; ++f) {
-        const size_t s = 6 * (size_t)e + f;
-        const SideDesc& d = fh.sd_host[s];
-        EstMortar x{};
-        x.elem = e; x.kind = d.kind; x.code = d.code; x.NQ = d.NQ; x.gidx = d.geom;
-        x.S = d.geom; x.off = 0; x.off_p = 0; x.Ttot = d.NQ * d.NQ; x.deg_m = fh.side_deg_m[s]; x.deg_p = fh.side_deg_p[s];
-        x.N = plan->deg[e] + 1; x.offC = d.offC; x.ops_hp = 0; x.bstride = plan->side_bndry_stride[s]; x.u_shift = 0;
-        x.fm = 1.0; x.fp = 1.0; x.qoff = d.qoff; x.nbr_qoff = d.nbr_qoff;
-        out.push_back(x);
-      }
-    }
-  }
-  elem_first[ne] = (int)out.size();
+  FaceHost& fh = face_host(plan);
+  return fh.hp && fh.hp_split && (fh.hang_elems.n == 0 || fh.n_units > 0);
 }
 
 // a volume vector's values at the Lobatto face nodes of every boundary side, in the layout of the Dirichlet data (side_bndry_stride)
@@ -3705,13 +2154,13 @@ __global__ __launch_bounds__(64) void bndry_gather_kernel(const double* __restri
 }
 
 void launch_boundary_gather(d4est_hip_plan* plan, const double* vol, double* out) {
-  FaceHost& fh = g_face_host[plan];
+  FaceHost& fh = face_host(plan);
   const int n_sides = 6 * plan->n_elements;
   if (n_sides == 0 || plan->total_bndry_nodes == 0) return;
   if (!fh.d_is_bndry) {
     std::vector<int> b(n_sides);
     for (int s_ = 0; s_ < n_sides; ++s_) b[s_] = fh.sd_host[s_].kind == 0;   // (boundary sides; hanging sides are kind 3)
-    fh.d_is_bndry = upload_vec(b);
+    fh.d_is_bndry = fh.upload(b);
   }
   hipLaunchKernelGGL(bndry_gather_kernel, dim3(std::min(n_sides, 8192)), dim3(64), 0, plan->stream, vol, out, fh.d_is_bndry,
                      fh.d_side_bndry_stride, (const ElemDesc*)fh.d_elem_desc_generic, n_sides);
@@ -3719,34 +2168,12 @@ void launch_boundary_gather(d4est_hip_plan* plan, const double* vol, double* out
 }
 
 void launch_traces_all(d4est_hip_plan* plan, const double* u, double* trace) {
-  FaceHost& fh = g_face_host[plan];
+  FaceHost& fh = face_host(plan);
   const int n = plan->n_elements;
   if (n == 0) return;
   if (fh.hp) run_trace_hp_generic(plan, fh, u, trace, n);
   else run_trace_generic(plan, fh, u, trace, n);
   HIP_CHECK(hipGetLastError());
-}
-
-void faces_destroy(d4est_hip_plan* plan) {
-  estimator_destroy(plan);
-  norms_destroy(plan);
-  direct_destroy(plan);
-  hybrid_destroy(plan);
-  auto it = g_face_host.find(plan);
-  if (it != g_face_host.end()) {
-    FaceHost& fh = it->second;
-    (void)hipFree(fh.d_side_deg_m); (void)hipFree(fh.d_side_deg_p); (void)hipFree(fh.d_side_bndry_stride);
-    (void)hipFree(fh.d_ghost_sides); (void)hipFree(fh.d_elem_desc_generic);
-    (void)hipFree(fh.d_sj); (void)hipFree(fh.d_robin_c); (void)hipFree(fh.d_robin_r);
-    (void)hipFree(fh.d_fam_small); (void)hipFree(fh.d_fam_big);
-    (void)hipFree(fh.d_rec); (void)hipFree(fh.d_gsrc); (void)hipFree(fh.d_elem_first); (void)hipFree(fh.d_side_first); (void)hipFree(fh.d_hp_ops); (void)hipFree(fh.d_hang_elems);
-    (void)hipFree(fh.d_units); (void)hipFree(fh.d_unit_first); (void)hipFree(fh.d_is_bndry);
-    (void)hipFree(fh.d_ring_small); (void)hipFree(fh.d_ring_big); (void)hipFree(fh.d_dirty_small); (void)hipFree(fh.d_dirty_big);
-    g_face_host.erase(it);
-  }
-  (void)hipFree(plan->d_elem_desc);
-  (void)hipFree(plan->d_side_desc); (void)hipFree(plan->d_face_ops);
-  (void)hipFree(plan->d_face_geom); (void)hipFree(plan->d_bndry); (void)hipFree(plan->d_trace);
 }
 
 }  // namespace d4est_hip

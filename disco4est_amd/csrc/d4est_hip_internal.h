@@ -93,7 +93,7 @@ struct d4est_hip_plan {
   double* d_metric_affine = nullptr;  // 6 per element (bucket order): J (dr/dx)(dr/dx)^T of node 0
   int* d_nonaffine = nullptr;         // per bucket: set by the precombine kernel when an element is not affine     // 6 * local_nodes_quad, element-blocked: [e][c][n], c in (rr,rs,rt,ss,st,tt)
 
-  // ---- faces (d4est_hip_faces.hip) ----
+  // ---- faces (set-up: d4est_hip_faces_setup.hip; kernels and launchers: d4est_hip_faces.hip) ----
   bool has_faces = false, has_face_geometry = false;
   int n_ghost = 0;
   std::vector<int> ghost_deg, ghost_deg_quad;
@@ -101,7 +101,7 @@ struct d4est_hip_plan {
   std::vector<int> side_hang, side_sub, side_nbr4, side_orientation;  // hanging faces (d4est_hip_plan_set_hanging); empty = conforming
   int total_mortar_nodes = 0, total_bndry_nodes = 0;
   long long local_trace_doubles = 0, ghost_trace_doubles = 0;
-  int* d_side_desc = nullptr;        // SideDesc per side (see d4est_hip_faces.hip)
+  int* d_side_desc = nullptr;        // SideDesc per side (see d4est_hip_faces_host.h)
   void* d_elem_desc = nullptr;       // ElemDesc per element
   // per mortar record (hanging plans; empty on conforming plans where a side has exactly one block)
   std::vector<long long> rec_qoff, rec_goff;
@@ -303,18 +303,20 @@ void launch_slicer_lift(d4est_hip_plan* plan, const double* in, double* out, int
 void launch_dij(d4est_hip_plan* plan, const double* in, double* out, int dir, int transpose);
 void launch_dudr(d4est_hip_plan* plan, const double* u, double* d0, double* d1, double* d2);
 
-// d4est_hip_faces.hip
+// d4est_hip_faces_setup.hip: the host set-up of the face part (also faces_estimator_mortars and faces_destroy below)
 void faces_setup(d4est_hip_plan* plan);
-void faces_set_geometry(d4est_hip_plan* plan, const double* sj, const double* n, const double* drst_m, const double* drst_p,
-                        const double* hm, const double* hp, int on_device);
 int reorient_face_order(int f_m, int f_p, int o, int i);  // dGMath/d4est_reference.c:84-110
 int face_reorder_code(int f_m, int f_p, int o);            // dGMath/d4est_operators.c:2031-2050
+// d4est_hip_faces_geometry.hip: mortar geometry and boundary data (also faces_set_geometry_brick / _analytic above)
+void faces_set_geometry(d4est_hip_plan* plan, const double* sj, const double* n, const double* drst_m, const double* drst_p,
+                        const double* hm, const double* hp, int on_device);
 void faces_set_dirichlet(d4est_hip_plan* plan, const double* g_lobatto, int on_device);
 void faces_set_robin(d4est_hip_plan* plan, const double* coeff_quad, const double* rhs_quad, int on_device);
 // raw sj at the mortar nodes (side_mortar_stride[s] + k) and the plan's Robin arrays sj coeff / sj rhs, allocated if need be and switched
 // on as faces_set_robin does -- the caller fills the boundary sides' entries on the plan's stream; both abort with `who` without sj
 const double* faces_sj(d4est_hip_plan* plan, const char* who);
 void faces_robin_arrays(d4est_hip_plan* plan, const char* who, double** robin_c, double** robin_r);
+// d4est_hip_faces.hip: the trace / flux kernels and their launchers
 // the plan's Robin arrays as the kernels take them: both nullptr while the boundary sides are Dirichlet
 void faces_robin(d4est_hip_plan* plan, const double** robin_c, const double** robin_r);
 void launch_traces(d4est_hip_plan* plan, const double* u, double* trace, bool ghost, const int* elist = nullptr, int n_list = 0, int parts = 3 /* see launch_flux */);
@@ -391,7 +393,7 @@ void launch_hybrid_dirty_stiffness(d4est_hip_plan* plan, const double* u, double
 bool hybrid_sharded(const d4est_hip_plan* plan);
 void launch_hybrid_clean_ghost(d4est_hip_plan* plan, const double* u, double* Au, const DirectFuse* cf = nullptr);
 void faces_destroy(d4est_hip_plan* plan);
-// the estimator's view of the plan's mortars (d4est_hip_faces.hip builds it from its side descriptors / mortar records): one entry per
+// the estimator's view of the plan's mortars (d4est_hip_faces_setup.hip builds it from its side descriptors / mortar records): one entry per
 // conforming or boundary side, per sub-mortar of a big hanging side, per small hanging side; the entries of an element consecutive
 struct EstMortar {
   int elem;

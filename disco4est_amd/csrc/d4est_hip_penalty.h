@@ -1,5 +1,5 @@
 // The four SIPG penalty functions (penalty_calc_t) by the ids of d4est_hip_plan_set_sipg: shared by the operator's face factors
-// (d4est_hip_faces.hip) and the IP energy norm (d4est_hip_norms.hip).
+// (d4est_hip_faces_geometry.hip) and the IP energy norm (d4est_hip_norms.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

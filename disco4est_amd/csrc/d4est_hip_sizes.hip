@@ -6,7 +6,7 @@
 //   diam_face[6]           the same over the N^2 nodes of a face
 //   volume, area[6]        Lobatto inner product of 1 with J / with sj on the face
 //   j_div_sj_min/mean/max  of J / sj over the face's Lobatto nodes, J and sj as d4est_mortars_compute_geometric_data_on_mortar gives
-//                          them with COMPUTE_NORMAL_USING_JACOBIAN (the expressions of analytic_mortar_kernel, d4est_hip_faces.hip)
+//                          them with COMPUTE_NORMAL_USING_JACOBIAN (the expressions of analytic_mortar_kernel, d4est_hip_faces_geometry.hip)
 // Three kernels per degree, whatever the number of elements (local elements first, then the ghost elements of that degree):
 //   size_xyz_kernel     brick / analytic map: node coordinates into a plan-owned array (the coordinates-only form reads the caller's)
 //   size_diam_kernel    the pair distances.  A group of G threads (G = the power of two >= N^3, 8 ... 256) owns an element, 256 / G

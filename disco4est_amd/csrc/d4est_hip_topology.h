@@ -1,5 +1,5 @@
 // The integer topology tables of the hot path, in ONE place: p8est's face tables (p4est-2.8 src/p8est_connectivity.c:29-63, :145-152)
-// and d4est's face re-orientation tables (src/dGMath/d4est_reference.c:3-12).  Every use in the library (d4est_hip_faces.hip,
+// and d4est's face re-orientation tables (src/dGMath/d4est_reference.c:3-12).  Every use in the library (d4est_hip_faces_setup.hip,
 // d4est_hip_sides.cpp) reads these arrays; d4est_hip_topology_table() hands them out, and tests/test_topology_tables.py compares them
 // entry by entry with the originals extracted as data from the reference's own files (tests/golden/p8est_tables.json).
 #pragma once

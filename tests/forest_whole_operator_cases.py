@@ -136,7 +136,7 @@ def merge(total, cov):
 
 
 def clean_without_higher_neighbour(m, sides):
-    """The hybrid operator's rule on a conforming one-rank plan with every degree <= 7 and deg_quad = deg (csrc/d4est_hip_faces.hip,
+    """The hybrid operator's rule on a conforming one-rank plan with every degree <= 7 and deg_quad = deg (csrc/d4est_hip_faces_setup.hip,
     "the hybrid operator"): an element is clean -- the one-kernel path -- unless a neighbour has a HIGHER degree; a neighbour of lower
     degree is read from the trace array (mixed-aware form, override kind 2)."""
     clean = [True] * m.n_elements

@@ -263,7 +263,7 @@ def test_hanging_aware_form_on_oriented_faces(gpu, hiplib, oracle, half):
     orientation 0..3) on the hanging-aware hybrid form (keys 13 = 1, 14 = 1), the refined tree first (half 0) or second (half 1).
     One degree (p = 4): all nine elements are clean (asserted) -- the big element owns the oriented hanging side as kind 3 (left to the
     record kernels), the four small elements own it with the kind-2 override wherever the reference's re-orientation is geometric from
-    their side (csrc/d4est_hip_faces.hip: u_shift = 0 there; elsewhere the side stays with the record kernels, and the engine would abort
+    their side (csrc/d4est_hip_faces_setup.hip: u_shift = 0 there; elsewhere the side stays with the record kernels, and the engine would abort
     on sub-mortars of several quadrature degrees: one degree only).  Mixed degrees on the geometric views: small elements on the face and
     the big one at p = 4, the other small ones at p = 3 -- exactly five clean elements, the big one and the four with the kind-2
     override --, or, every other case, the big element at p = 5: it alone is clean, no small side can take the override."""

@@ -1,5 +1,5 @@
 """Integer work is bit-exact against reference-held data: the p8est face / corner tables and d4est's face re-orientation tables that the
-library (csrc/d4est_hip_topology.h, read by d4est_hip_faces.hip and d4est_hip_sides.cpp), the host-side mesh code (forest.py) and the
+library (csrc/d4est_hip_topology.h, read by d4est_hip_faces_setup.hip and d4est_hip_sides.cpp), the host-side mesh code (forest.py) and the
 oracle (d4est_oracle_flux.c) work with are compared ENTRY BY ENTRY with the originals, extracted as integers from the reference's own
 files by tests/golden/make_reference_tables.py (third_party/p4est-2.8.tar.gz: src/p8est_connectivity.c:29-63, :145-152;
 src/dGMath/d4est_reference.c:3-12) -- not with each other."""
