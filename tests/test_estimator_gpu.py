@@ -1,7 +1,9 @@
 """GPU tests of the device error estimator (d4est_hip_plan_set_estimator / d4est_hip_estimator_bi, csrc/d4est_hip_estimator.hip): every
 term per element against the numpy restatement of d4est_estimator_bi_compute (tests/dense_estimator.py) on conforming, curved,
 mixed-degree, hanging and cubed-sphere meshes; the ten penalty ids; shards with a trace exchange; determinism and independence of
-the operator's face path; no change to plans without the estimator."""
+the operator's face path; no change to plans without the estimator.  Faces between trees with an orientation other than 0 meet only
+the cubed sphere here (codes 0, 1, 2, 3, 7, p = 3, conforming, one rank): every gluing, all eight codes, NQ != N, p >= 8, degree jumps,
+hanging faces and ghost blocks on an oriented face are in tests/test_forest_estimator_gpu.py."""
 import numpy as np
 import pytest
 

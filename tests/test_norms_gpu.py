@@ -2,7 +2,9 @@
 d4est_hip_ip_energy_norm_sqr, d4est_hip_masked_sum) against the numpy restatement of the reference's formulas (tests/dense_norms.py):
 per-element values by term and the totals at the estimator tests' tolerance, Linfty and the error field exactly; uniform, graded,
 hanging and cubed-sphere meshes; the four SIPG penalty ids; skip masks; shards with a trace exchange; determinism and independence
-of the operator's face path; no change to plans without the energy norm."""
+of the operator's face path; no change to plans without the energy norm.  The energy norm's jump term on oriented faces between trees
+beyond the cubed sphere's (all eight reorder codes, NQ != N, p >= 8, degree jumps, hanging faces, ghost blocks):
+tests/test_forest_estimator_gpu.py."""
 import os
 import subprocess
 import sys
