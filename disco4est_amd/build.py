@@ -28,6 +28,7 @@ SOURCES = [
     "d4est_hip_transfer.hip",
     "d4est_hip_mgmatrix.hip",
     "d4est_hip_schwarz.hip",
+    "d4est_hip_schwarz_gmres.hip",
     "d4est_hip_comm.hip",
     "d4est_hip_estimator.hip",
     "d4est_hip_norms.hip",

@@ -99,6 +99,8 @@ SIGNATURES = {
     "d4est_hip_schwarz_smooth": (None, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double]),
     "d4est_hip_schwarz_get_info": (None, [_vp, _vp, _vp]),
     "d4est_hip_schwarz_host_reads": (ctypes.c_longlong, [_vp]),
+    "d4est_hip_schwarz_set_subdomain_solver": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "d4est_hip_schwarz_subdomain_solver": (None, [_vp, _vp, _vp, _vp]),
     "d4est_hip_schwarz_set_element_exchange": (None, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d4est_hip_schwarz_own_nodes": (ctypes.c_longlong, [_vp]),
     "d4est_hip_schwarz_exchange_first": (ctypes.c_longlong, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),

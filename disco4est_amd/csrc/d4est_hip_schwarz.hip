@@ -24,86 +24,10 @@
 #include <cmath>
 #include <vector>
 
-#include "d4est_hip_internal.h"
+#include "d4est_hip_schwarz_internal.h"
 #include "d4est_hip_tables.h"
 
-namespace {
-
-struct VirtDesc {
-  int dst;      // offset of the copy in a field over the subdomains
-  int src;      // nodal_stride of the mesh element
-  int N;        // deg + 1
-  int lo[3];    // restricted node range per direction: lo <= index < hi
-  int hi[3];
-  int woff[3];  // hat weight of node index i in direction d: weights[woff[d] + i]
-};
-
-}  // namespace
-
-struct d4est_hip_schwarz {
-  d4est_hip_plan_t* plan = nullptr;  // the subdomain plan (not owned)
-  int n_sub = 0, n_virtual = 0, n_mesh = 0, overlap = 0;
-  long long nodal_size = 0, restricted_nodal_size = 0;
-  int mesh_nodes = 0;
-  VirtDesc* d_vd = nullptr;
-  int* d_sub_first = nullptr;
-  int* d_mesh_first = nullptr;    // per mesh element: first entry of its contribution list (n_mesh + 1)
-  int* d_mesh_contrib = nullptr;  // subdomain elements that are copies of the mesh element, ascending (= ascending subdomain)
-  int* d_mesh_stride = nullptr;
-  int* d_mesh_N = nullptr;
-  double* d_weights = nullptr;
-  // workspace of iterate (lazy)
-  double *d_du = nullptr, *d_r = nullptr, *d_d = nullptr, *d_Ad = nullptr, *d_zero_ghost = nullptr;
-  double *d_delta = nullptr, *d_tol = nullptr;
-  int *d_active = nullptr, *d_final_iter = nullptr, *d_n_active = nullptr;
-  // flat list of the restricted nodes of every subdomain (field offsets), for the register-resident CG kernel
-  int* d_box_off = nullptr;
-  int* d_box_first = nullptr;        // n_sub + 1
-  int max_box_nodes = 0;
-  // condensed copies (see ensure_condensed): copies with a handful of restricted nodes whose rows of the subdomain operator are kept as
-  // small dense blocks instead of being applied matrix-free
-  std::vector<VirtDesc> h_vd;        // host copy of the copy descriptors
-  int condensed_state = 0;           // 0 not looked at yet, 1 in use, -1 not applicable / switched off
-  unsigned long long cond_generation = 0;   // the subdomain plan's op_generation the state above belongs to
-  int n_cond = 0;
-  void* d_cond = nullptr;            // CondDesc per condensed copy
-  double* d_cond_blocks = nullptr;
-  int* d_keep_list = nullptr;        // the copies that stay matrix-free
-  int n_keep = 0;
-  int* d_cond_off = nullptr;         // per condensed copy: field offsets of its inputs (own restricted nodes first, then the neighbours')
-  long long cond_block_doubles = 0;
-  // D4EST_HIP_SCHWARZ_FUSED_RESIDUAL=1 (read at create): the smoother loop (schwarz_smoother_run, schwarz_pc_run) forms rhs - A u
-  // inside the CG start instead of writing it to a mesh vector first -- same numbers.  Off by default: on the level-4, p = 7 cycle
-  // it measured no faster than the two-kernel sequence; D4EST_HIP_SCHWARZ_UNFUSED_RESIDUAL=1 forces it off.
-  bool fused_residual = false;
-  long long host_reads = 0;          // blocking reads of the device counters made so far (the "still iterating" looks and the public entry's sweep count)
-  // ---- whole-element exchange of a SHARDED handle (d4est_hip_schwarz_set_element_exchange); ex_fn == nullptr: one rank, nothing below is used.
-  // The mesh handed to create() is the rank's extended mesh; u / r of iterate, smooth and the pc are vectors of the own nodes, the prefix.
-  d4est_hip_element_exchange_fn ex_fn = nullptr;
-  void* ex_ctx = nullptr;
-  int n_own = 0, n_peers = 0;
-  long long own_nodes = 0;
-  std::vector<int> ex_peer;
-  std::vector<long long> own_first, ghost_first;   // per peer (+ total): first double of its segment among the own-element / ghost-layer blocks
-  double *d_r_ext = nullptr, *d_u_ext = nullptr;   // residual and correction on the extended mesh
-  // packed buffers: direction 0 sends `own` and receives `ghost`, direction 1 sends `ghost_back` and receives `own_back`
-  double *d_own_pack = nullptr, *d_ghost_pack = nullptr, *d_ghost_back = nullptr, *d_own_back = nullptr;
-  int* d_own_blk_first = nullptr;    // per own element (n_own + 1): its entries of d_own_blk_off, in ascending peer rank
-  int* d_own_blk_off = nullptr;      // offset of the element's block in the own-element packed layout of that peer
-  int n_ghost_blocks = 0;
-  int* d_ghost_blk_elem = nullptr;   // per ghost-layer block, peer after peer: its element ...
-  int* d_ghost_blk_off = nullptr;    // ... and the block's offset in the ghost-layer packed layout
-  std::vector<int> h_mesh_stride, h_mesh_N;
-};
-
 namespace d4est_hip {
-
-__device__ inline bool in_overlap(const VirtDesc& q, int n, int& i, int& j, int& k) {
-  i = n % q.N;
-  j = (n / q.N) % q.N;
-  k = n / (q.N * q.N);
-  return i >= q.lo[0] && i < q.hi[0] && j >= q.lo[1] && j < q.hi[1] && k >= q.lo[2] && k < q.hi[2];
-}
 
 // n-th restricted node of a copy (x fastest) -> its offset in a field over the subdomains; count = restricted_count(q)
 __device__ inline int restricted_count(const VirtDesc& q) { return (q.hi[0] - q.lo[0]) * (q.hi[1] - q.lo[1]) * (q.hi[2] - q.lo[2]); }
@@ -767,6 +691,7 @@ d4est_hip_schwarz_t* d4est_hip_schwarz_create(d4est_hip_plan_t* subdomain_plan, 
       if (box_off.size() > (size_t)0x7fffffff) { fits = false; break; }
       box_first[s_ + 1] = (int)box_off.size();
       sz->max_box_nodes = std::max(sz->max_box_nodes, box_first[s_ + 1] - box_first[s_]);
+      sz->min_box_nodes = s_ == 0 ? box_first[1] : std::min(sz->min_box_nodes, box_first[s_ + 1] - box_first[s_]);
     }
     if (fits) {
       sz->d_box_off = upload(box_off);
@@ -800,6 +725,7 @@ static void release_element_exchange(d4est_hip_schwarz* sz) {
 void d4est_hip_schwarz_destroy(d4est_hip_schwarz_t* sz) {
   if (!sz) return;
   release_element_exchange(sz);
+  schwarz_gmres_release(sz);
   void* ptrs[] = {sz->d_vd, sz->d_sub_first, sz->d_mesh_first, sz->d_mesh_contrib, sz->d_mesh_stride, sz->d_mesh_N, sz->d_weights,
                   sz->d_du, sz->d_r, sz->d_d, sz->d_Ad, sz->d_zero_ghost, sz->d_delta, sz->d_tol, sz->d_active, sz->d_final_iter,
                   sz->d_n_active, sz->d_cond, sz->d_cond_blocks, sz->d_keep_list, sz->d_cond_off, sz->d_box_off, sz->d_box_first};
@@ -872,6 +798,14 @@ static int iterate_body(d4est_hip_schwarz_t* sz, double* u_dev, const double* r_
   ensure_zero_ghost(sz);
   hipStream_t st = sz->plan->stream;
   HIP_CHECK(hipMemsetAsync(sz->d_n_active, 0, 2 * sizeof(int), st));
+  sz->last_solver = sz->solver_kind;
+  if (sz->solver_kind == 1) {
+    // restarted GMRES (d4est_hip_schwarz_gmres.hip): the count returned is the host's own, the number of batched operator applies
+    const int applies = schwarz_gmres_solve(sz, r_dev, Au_dev, subdomain_iter, subdomain_atol, subdomain_rtol);
+    if (store) store_correction(sz, sz->d_du, u_dev);
+    else d4est_hip_schwarz_add_correction(sz, sz->d_du, u_dev);
+    return read_sweeps ? applies : -1;
+  }
   if (Au_dev)
     hipLaunchKernelGGL(schwarz_cg_init_kernel<true>, dim3(sz->n_sub), dim3(256), 0, st, sz->d_vd, sz->d_sub_first, r_dev, Au_dev, sz->d_du,
                        sz->d_r, sz->d_d, sz->d_delta, sz->d_tol, sz->d_active, sz->d_final_iter, sz->d_n_active, subdomain_iter,
@@ -1089,7 +1023,9 @@ void d4est_hip_schwarz_get_info(d4est_hip_schwarz_t* sz, int* final_iter_host, d
   if (!sz->d_du) D4EST_HIP_ABORT("schwarz_get_info: call schwarz_iterate first");
   HIP_CHECK(hipStreamSynchronize(sz->plan->stream));
   if (final_iter_host) HIP_CHECK(hipMemcpy(final_iter_host, sz->d_final_iter, (size_t)sz->n_sub * sizeof(int), hipMemcpyDeviceToHost));
-  if (final_res_host) {
+  if (final_res_host && sz->last_solver == 1) {   // GMRES: rho itself (subdomain_solver_gmres.c:441-442)
+    HIP_CHECK(hipMemcpy(final_res_host, sz->d_gm_rho, (size_t)sz->n_sub * sizeof(double), hipMemcpyDeviceToHost));
+  } else if (final_res_host) {
     HIP_CHECK(hipMemcpy(final_res_host, sz->d_delta, (size_t)sz->n_sub * sizeof(double), hipMemcpyDeviceToHost));
     for (int s = 0; s < sz->n_sub; ++s) final_res_host[s] = std::sqrt(final_res_host[s]);
   }

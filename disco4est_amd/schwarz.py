@@ -297,6 +297,11 @@ def subdomain_sides(mesh, sides, md):
     return vs
 
 
+class SchwarzInfo(tuple):
+    """what Schwarz.info() returns: the pair (final_iter, final_res) with the subdomain solver's description as attributes"""
+    solver, inner_iter, workspace_bytes = 0, 0, 0
+
+
 class Schwarz:
     """d4est_solver_schwarz_t on the device: metadata + subdomain plan + the native smoother handle."""
 
@@ -354,7 +359,8 @@ class Schwarz:
         self.lib.d4est_hip_schwarz_add_correction(self.handle, capi._ptr(du), capi._ptr(u))
 
     def iterate(self, u, r):
-        """u += Schwarz correction of the residual r (d4est_solver_schwarz_iterate); returns the number of batched CG sweeps"""
+        """u += Schwarz correction of the residual r (d4est_solver_schwarz_iterate); returns the number of batched CG sweeps (under GMRES:
+        of batched operator applies)"""
         assert u.numel() == self.local_nodes and r.numel() == self.local_nodes
         return self.lib.d4est_hip_schwarz_iterate(self.handle, capi._ptr(u), capi._ptr(r), self.subdomain_iter, self.subdomain_atol,
                                                   self.subdomain_rtol)
@@ -408,11 +414,34 @@ class Schwarz:
         """blocking reads of device counters made so far (d4est_hip_schwarz_host_reads)"""
         return int(self.lib.d4est_hip_schwarz_host_reads(self.handle))
 
+    SOLVER_CG, SOLVER_GMRES = 0, 1
+
+    def set_subdomain_solver(self, kind, inner_iter=0):
+        """[d4est_solver_schwarz] subdomain_solver / subdomain_inner_iter (d4est_hip_schwarz_set_subdomain_solver): kind 0 or "cg" is the
+        batched CG (the default), 1 or "gmres" restarted GMRES with restart length inner_iter; iterate, smooth, the V-cycle's smoother and
+        PcSchwarz follow the choice.  Under GMRES subdomain_iter counts restart cycles.  Raises ValueError carrying the return code."""
+        kind = {"cg": 0, "gmres": 1}.get(kind, kind)
+        code = int(self.lib.d4est_hip_schwarz_set_subdomain_solver(self.handle, int(kind), int(inner_iter)))
+        if code != 0:
+            why = {1: "unknown kind", 2: "inner_iter <= 0", 3: "inner_iter exceeds the smallest restricted subdomain size",
+                   4: "inner_iter exceeds the compiled cap"}.get(code, "?")
+            raise ValueError("set_subdomain_solver(%r, %r): code %d (%s)" % (kind, inner_iter, code, why), code)
+
+    def subdomain_solver(self):
+        """(kind, inner_iter, workspace_bytes) of d4est_hip_schwarz_subdomain_solver"""
+        kind, inner, ws = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_longlong(-1)
+        self.lib.d4est_hip_schwarz_subdomain_solver(self.handle, ctypes.byref(kind), ctypes.byref(inner), ctypes.byref(ws))
+        return int(kind.value), int(inner.value), int(ws.value)
+
     def info(self):
+        """(final_iter, final_res) of the last iterate, per subdomain; the pair also carries .solver, .inner_iter and .workspace_bytes
+        (what subdomain_solver() returns)"""
         it = np.zeros(self.metadata.num_subdomains, dtype=np.int32)
         res = np.zeros(self.metadata.num_subdomains)
         self.lib.d4est_hip_schwarz_get_info(self.handle, it.ctypes.data_as(_vp), res.ctypes.data_as(_vp))
-        return it, res
+        out = SchwarzInfo((it, res))
+        out.solver, out.inner_iter, out.workspace_bytes = self.subdomain_solver()
+        return out
 
     def destroy(self):
         if getattr(self, "handle", None):
@@ -519,6 +548,10 @@ class SchwarzShard:
         self.u_ext = torch.zeros(m.local_nodes, dtype=torch.float64, device=device)
         self.back = torch.zeros(m.local_nodes, dtype=torch.float64, device=device)
 
+    def set_subdomain_solver(self, kind, inner_iter=0):
+        """the subdomain solver of this rank's handle (Schwarz.set_subdomain_solver); every rank makes the same choice"""
+        self.schwarz.set_subdomain_solver(kind, inner_iter)
+
     # the two halves of an exchange are separate calls so that in-process virtual ranks can be interleaved by the tests
     def begin_residual_exchange(self, r_own):
         self.r_ext[:self.own_nodes].copy_(r_own)
@@ -579,6 +612,10 @@ class SchwarzShardNative:
         self.own_nodes = int(((m.deg[:self.n_own].astype(np.int64) + 1) ** 3).sum())
         self.schedule = ElementSchedule(m, self.n_own, parts, needed_by)
         self.exchange = None                                  # what attach_schwarz / attach_schwarz_rccl returned (kept alive)
+
+    def set_subdomain_solver(self, kind, inner_iter=0):
+        """the subdomain solver of this rank's handle (Schwarz.set_subdomain_solver); every rank makes the same choice"""
+        self.schwarz.set_subdomain_solver(kind, inner_iter)
 
     def iterate(self, u_own, r_own):
         """one d4est_solver_schwarz_iterate on this rank (collective: every rank calls it); returns this rank's CG sweeps"""

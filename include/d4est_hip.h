@@ -978,6 +978,37 @@ void d4est_hip_schwarz_get_info(d4est_hip_schwarz_t* sz, int* final_iter_host, d
  * every 8th subdomain sweep, and the sweep count the public d4est_hip_schwarz_iterate returns.  The exchange ends add none. */
 long long d4est_hip_schwarz_host_reads(const d4est_hip_schwarz_t* sz);
 
+/* ---- the subdomain solver: batched CG (the default) or restarted GMRES (csrc/d4est_hip_schwarz_gmres.hip) -----------------------------
+ * [d4est_solver_schwarz] subdomain_solver = cg | gmres with subdomain_inner_iter.  kind 0: the CG of
+ * d4est_solver_schwarz_subdomain_solver_cg.c, subdomain_inner_iter is ignored and any GMRES workspace is freed.  kind 1:
+ * d4est_solver_schwarz_subdomain_solver_gmres (src/Solver/d4est_solver_schwarz_subdomain_solver_gmres.c:165-443) with restart length
+ * mr = subdomain_inner_iter.  A handle on which this was never called runs CG.  Returns
+ *   0  ok
+ *   1  unknown kind ("Not a supported subdomain solver", d4est_solver_schwarz_subdomain_solver.c:87; ksp has no device form)
+ *   2  mr <= 0 (subdomain_inner_iter is a required input, subdomain_solver_gmres.c:88; the options check of :93-97 leaves it out and a
+ *      restart length <= 0 reads g[k] / h[k][k] of an empty cycle at :399)
+ *   3  mr is larger than the smallest restricted_nodal_size of a subdomain (the reference aborts with "nodes < mr", :203-205)
+ *   4  mr > D4EST_HIP_SCHWARZ_GMRES_MAX_MR = 128.  The cap keeps what one subdomain carries between kernels -- the rotated upper triangle
+ *      of h, c, s, g and y: 70 KB at the cap -- below half of a CU's 160 KB of LDS; the kernels themselves stage one column (Arnoldi)
+ *      or one row (back-substitution) of it at a time, 2 KB at the cap.  It admits the full GMRES of the smallest corner subdomain
+ *      at p = 2, overlap 2 (125 restricted nodes).
+ * and leaves the handle as it was on a non-zero code.  Every entry that solves subdomain problems follows the choice without a change of
+ * signature: d4est_hip_schwarz_iterate and _smooth, the V-cycle's Schwarz smoother, the reuse_smoother bottom solver, d4est_hip_pc_schwarz_*,
+ * on one rank and on sharded handles.  Under GMRES subdomain_iter is the reference's itr_max (restart cycles), subdomain_atol / _rtol are
+ * tol_abs / tol_rel and a subdomain stops when rho <= rho_tol && rho <= tol_abs (:391, :418 -- both must hold);
+ * d4est_hip_schwarz_get_info returns final_iter = itr_used (inner steps made) and final_res = rho (:441-442);
+ * d4est_hip_schwarz_iterate returns the number of batched operator applies it made (mr per restart cycle plus one at the start of every
+ * cycle but the first, where x = 0), a count the host keeps itself; d4est_hip_schwarz_host_reads counts one look at the "still
+ * iterating" counter per restart cycle after the first.
+ * Deviation: the reference divides by rho = |rhs - A x| unguarded (:281), so a subdomain whose residual is exactly zero at a cycle start
+ * becomes NaN there; here it is finished: x unchanged, final_res = 0, final_iter as reached.
+ * The workspace ((mr + 1) basis vectors of nodal_size doubles and, per subdomain, (mr + 1) mr + 2 mr + (mr + 1) + 2 doubles and 2 ints)
+ * is allocated here, never by an iterate, and freed by kind 0 and by destroy; _subdomain_solver reports kind, mr (0 under CG) and its
+ * size in bytes (0 under CG); any of the three pointers may be NULL. */
+#define D4EST_HIP_SCHWARZ_GMRES_MAX_MR 128
+int d4est_hip_schwarz_set_subdomain_solver(d4est_hip_schwarz_t* sz, int kind, int subdomain_inner_iter);
+void d4est_hip_schwarz_subdomain_solver(const d4est_hip_schwarz_t* sz, int* kind, int* subdomain_inner_iter, long long* workspace_bytes);
+
 /* ---- the smoother on N ranks: the two whole-element exchanges of an iterate inside the handle --------------------------------------------
  * d4est_ghost_data_exchange of the residual before the subdomain solves (src/Solver/d4est_solver_schwarz.c:197-203; direction 0, owners
  * -> ghost copies) and d4est_solver_schwarz_transfer_ghost_data_and_add_corrections afterwards
