@@ -411,13 +411,11 @@ void d4est_hip_transfer_galerkin_blocks(d4est_hip_transfer_t* t, const double* f
 
 void d4est_hip_plan_set_lhs_element_blocks(d4est_hip_plan_t* plan, const double* blocks_dev, const long long* block_offset_host) {
   if (!plan) D4EST_HIP_ABORT("plan_set_lhs_element_blocks: NULL plan");
-  plan->op_generation++;
-  if (plan->cheby_graph) { HIP_CHECK(hipGraphExecDestroy(plan->cheby_graph)); plan->cheby_graph = nullptr; }
+  plan_operator_changed(plan);
   plan->d_lhs_blocks = blocks_dev;
   if (!blocks_dev) return;
   // one form of the zeroth-order term at a time
   plan->d_lhs_coeff = nullptr;
-  plan->lhs_wjc_valid = false;
   lhs_chain_destroy(plan);
   std::vector<long long> off(std::max(plan->n_elements, 1), 0);
   long long o = 0;
@@ -438,14 +436,12 @@ void d4est_hip_plan_set_lhs_element_blocks(d4est_hip_plan_t* plan, const double*
 void d4est_hip_plan_set_lhs_galerkin_chain(d4est_hip_plan_t* plan, int n_transfers, d4est_hip_transfer_t* const* transfers,
                                            d4est_hip_plan_t* fine_plan) {
   if (!plan) D4EST_HIP_ABORT("plan_set_lhs_galerkin_chain: NULL plan");
-  plan->op_generation++;
-  if (plan->cheby_graph) { HIP_CHECK(hipGraphExecDestroy(plan->cheby_graph)); plan->cheby_graph = nullptr; }
+  plan_operator_changed(plan);
   lhs_chain_destroy(plan);
   if (n_transfers <= 0 || !transfers || !fine_plan) return;   // chain off
   if (fine_plan == plan) D4EST_HIP_ABORT("plan_set_lhs_galerkin_chain: the fine plan is the plan itself (use plan_set_lhs_coefficient on the finest level)");
   if (!fine_plan->has_geometry) D4EST_HIP_ABORT("plan_set_lhs_galerkin_chain: the fine plan has no geometry");
   plan->d_lhs_coeff = nullptr;
-  plan->lhs_wjc_valid = false;
   plan->d_lhs_blocks = nullptr;
   LhsChain* ch = new LhsChain();
   ch->fine = fine_plan;

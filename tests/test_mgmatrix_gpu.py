@@ -9,8 +9,9 @@ fine mesh; apply_lhs, 5 Chebyshev iterations, cg_eigs, and the Schwarz subdomain
 import numpy as np
 import pytest
 
+from tests.mgmatrix_cases import RTOL, hierarchy as _hierarchy
+
 pytestmark = pytest.mark.gpu
-RTOL = 1e-12
 
 
 def _plan(m, mp, prefactor=10.0):
@@ -21,44 +22,6 @@ def _plan(m, mp, prefactor=10.0):
     plan.set_geometry(J, rst)
     plan.set_faces(sides, prefactor, 0)
     return plan, J, rst, sides
-
-
-def _hierarchy(kind):
-    """list of meshes, finest first, and the transfer item lists between consecutive levels (coarse <- fine)"""
-    from disco4est_amd import mesh as M
-    if kind == "hp3":
-        # level 2 brick (64 elements, p = 2..4 scattered so that the eight children of a parent differ) -> h-coarsened level 1 brick
-        # (degH = the smallest child degree, d4est_solver_multigrid_callbacks.h:52-75) -> p-coarsened (deg - 1, :9-20)
-        deg2 = (2 + (np.arange(64) * 7 + (np.arange(64) // 8)) % 3).astype(np.int32)
-        deg1 = deg2.reshape(8, 8).min(axis=1).astype(np.int32)
-        deg0 = np.maximum(deg1 - 1, 1).astype(np.int32)
-        meshes = [M.BrickMesh(2, deg2, deg_quad_inc=1), M.BrickMesh(1, deg1, deg_quad_inc=1), M.BrickMesh(1, deg0, deg_quad_inc=1)]
-        items = [(np.ones(8, np.int32), deg1, deg2.copy()),
-                 (np.zeros(8, np.int32), deg0, np.ascontiguousarray(np.stack([deg1] + [np.zeros(8, np.int32)] * 7, axis=1).reshape(-1)))]
-        return meshes, items
-    if kind == "hanging2":
-        # fine: level-1 brick with octants 1 and 6 refined (22 elements, hanging faces), p = 2 / 3; coarse: the level-1 brick -- the refined
-        # octants coarsen (eight children -> parent), the others are copied (the reference's third case) or lose one degree
-        refine = np.zeros(8, dtype=bool)
-        refine[[1, 6]] = True
-        n_el = 8 - 2 + 16
-        degf = (2 + (np.arange(n_el) * 5) % 2).astype(np.int32)
-        mf = M.HangingBrickMesh(1, refine, degf, deg_quad_inc=0)
-        hrefine, degH, degh = [], [], []
-        k = 0
-        for b in range(8):
-            dh = np.zeros(8, np.int32)
-            if refine[b]:
-                dh[:] = degf[k:k + 8]
-                hrefine.append(1); degH.append(int(dh.min())); k += 8
-            else:
-                dh[0] = degf[k]
-                hrefine.append(0); degH.append(int(degf[k]) - (1 if b % 2 == 0 else 0)); k += 1   # p-coarsened or copied
-            degh.append(dh)
-        degH = np.array(degH, np.int32)
-        mc = M.BrickMesh(1, degH, deg_quad_inc=0)
-        return [mf, mc], [(np.array(hrefine, np.int32), degH, np.concatenate(degh))]
-    raise ValueError(kind)
 
 
 @pytest.mark.parametrize("unfused", [False, True])
